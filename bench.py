@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- utterances/sec of the c2c-direct-mixed hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path (FastConformer-CTC forward -> greedy decode ->
 verse retrieval -> CTC rerank) over one batch of synthetic 16 kHz clips that is already resident
@@ -23,13 +23,21 @@ batch execute under the forward pass of the next (DESIGN.md "Batches in flight";
 gives the one-batch-at-a-time figure).  The timed region ends after every batch has finished
 (device synchronise) and, for N > 1, after every batch's rows have been gathered.
 
-Prints ONE JSON line on rank 0 (contract in the task description) including
+Prints ONE JSON line on rank 0 (contract in the task description): metric, value, unit,
+higher_is_better, dtype, ms_per_step (one timed step) and the configuration.  A plain run does only
+that: set up, warm up, time the K steps, write --dump-outputs, print.  --full adds everything else
+the line reports (null without it), each measured after the timed region:
   roofline      dominant kernel (the FFN-up GEMM class) measured with HIP events on its stream
   cpu_baseline  the CPU oracle (fp32 PyTorch forward + C restatement of the post-logits
                 stages) timed on this node's host cores on a bounded sample of the same clips
   post_logits   the post-logits stages alone on verse-shaped log-probs (the random-weight clips
                 decode to near-empty transcripts and never exercise retrieval): ms per batch
                 with every transcript passing the 0.80 text gate and with every one failing it
+  realistic_mix, ingest, long_region, extra   further legs of the default line (see below), and
+                the sanity pass that checks a fresh batch's results
+--dump-outputs DIR writes what the timed path returned for its LAST step to DIR/<field>.npy
+(float64, one entry per utterance: see rows_to_arrays); inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -81,6 +89,12 @@ def parse():
                          "the longest clip it may ever see (the plugin's default is 30 s) and must not pay for it on shorter ones")
     ap.add_argument("--contexts", type=int, default=4,
                     help="batches in flight per GPU (execution contexts of the engine, 1..8)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline (roofline, cpu_baseline, post_logits, realistic_mix, "
+                         "ingest, long_region, the extra legs of the default line) and run the sanity pass; a plain run only "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results the timed path returned for its last step as DIR/<field>.npy (float64)")
     ap.add_argument("--precision", choices=("fp16", "mixed", "ort"), default="fp16",
                     help="fp16 = BASELINE configs[1] (the headline line); mixed = int4 Linear + int8 pointwise-conv weights "
                          "dequantised to f16 operands (W4A16 / W8A16); ort = the arithmetic onnxruntime runs on the reference's "
@@ -484,7 +498,7 @@ def extra_legs():
     out = {}
     for name, flags in legs.items():
         try:
-            p = subprocess.run([sys.executable, str(ROOT / "bench.py"), *flags, "--no-cpu-baseline", "--no-post-logits", "--no-extra"],
+            p = subprocess.run([sys.executable, str(ROOT / "bench.py"), *flags, "--full", "--no-cpu-baseline", "--no-post-logits", "--no-extra"],
                                capture_output=True, text=True, timeout=420, cwd=str(ROOT))
             rows = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
             d = json.loads(rows[-1])
@@ -498,6 +512,51 @@ def extra_legs():
         except Exception as e:
             out[name] = {"error": f"{type(e).__name__}: {e}"}
     return out
+
+
+# string fields of the result dicts as numbers (0 = None / absent)
+_CODES = {"source": {None: 0, "text": 1, "ctc": 2}, "tta": {None: 0, "majority": 1, "score_pick": 2}}
+
+
+def rows_to_arrays(rows):
+    """result dicts of one step (Engine.fetch_results / the TTA decision rule; None = a padding row) -> {field: float64
+    array with one entry per row}: numbers and flags as they are, None / absent -> NaN, `source` / `tta` as _CODES, the
+    TTA per-copy fields as [n, 3] (tta_scores) / [n, 3, 2] (tta_preds); text fields are left out (the timed path runs with
+    want_text=False)."""
+    import numpy as np
+
+    keys = sorted({k for r in rows if r for k in r})
+    out = {}
+    for k in keys:
+        vals = [r.get(k) if r else None for r in rows]
+        if k in _CODES:
+            out[k] = np.array([_CODES[k][v] for v in vals], dtype=np.float64)
+        elif k in ("tta_scores", "tta_preds"):
+            shape = (3,) if k == "tta_scores" else (3, 2)
+            out[k] = np.stack([np.asarray(v, dtype=np.float64) if v is not None else np.full(shape, np.nan) for v in vals])
+        elif all(v is None or isinstance(v, (bool, int, float)) for v in vals):
+            out[k] = np.array([np.nan if v is None else float(v) for v in vals], dtype=np.float64)
+    return out
+
+
+def packed_to_arrays(packed):
+    """int32 rows [n, 4] = (surah, ayah, ayah_end, float-bits(score)) of the collective path -> {field: float64 array}"""
+    import numpy as np
+
+    packed = np.ascontiguousarray(packed, dtype=np.int32)
+    return {"surah": packed[:, 0].astype(np.float64), "ayah": packed[:, 1].astype(np.float64),
+            "ayah_end": packed[:, 2].astype(np.float64), "score": packed[:, 3].view(np.float32).astype(np.float64)}
+
+
+def dump_outputs(path: str, arrays: dict):
+    import numpy as np
+
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert arrays and total <= 64 << 20, (sorted(arrays), total)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def main():
@@ -592,6 +651,7 @@ def main():
         res = eng.fetch_results(ctx, B, t_frames)
         fetched["batches"] += 1
         fetched["rows"] += len(res)
+        fetched["last"] = res
 
     def step_clips():
         # every step runs the WHOLE hot path on one batch; with contexts > 1 up to that many batches
@@ -628,6 +688,7 @@ def main():
         from offline_tarteel_amd.plugin import tta_finish
 
         res = tta_finish(eng, st)
+        tta_stats["last"] = res
         tta_stats["clips"] += B
         tta_stats["gated"] += sum(1 for r in res if "tta" in r)
         if use_dist:
@@ -667,12 +728,16 @@ def main():
 
         s_lengths, s_order, s_mine = strong_plan(world, rank, args.deal)
 
+    strong_last = {}
+
     def step_strong():
         # the WHOLE global batch: this rank's share through the engine, then the path's one exchange (16 B per utterance)
         rows = strong_pass(eng, audio, s_lengths, s_mine, B)
+        strong_last["rows"] = rows
         if use_dist:
             full = qdist.all_gather_results(torch.from_numpy(qdist.pack_results(rows)).cuda(local_rank), s_order, len(s_lengths))
             assert full.shape == (len(s_lengths), 4)
+            strong_last["full"] = full
 
     step = step_tta if tta else step_strong if strong else step_clips
 
@@ -720,13 +785,23 @@ def main():
     value = (len(s_lengths) if strong else world * B) * args.steps / dt
     if not tta and not strong and not use_dist:
         assert fetched["batches"] == args.steps and fetched["rows"] == B * args.steps, fetched   # every timed batch came back
+    # what the timed path returned for its last step: the rows a caller receives (rank 0's all-gathered rows on the
+    # collective path), taken before anything else runs on the engine
+    if args.dump_outputs and rank == 0:
+        if strong:
+            outputs = packed_to_arrays(strong_last["full"]) if use_dist else rows_to_arrays(strong_last["rows"])
+        elif use_dist:
+            outputs = packed_to_arrays(gathered.cpu().numpy())
+        else:
+            outputs = rows_to_arrays(tta_stats["last"] if tta else fetched["last"])
+        dump_outputs(args.dump_outputs, outputs)
 
     # The driver's timed region is K = 20 steps (~73 ms): the same loop over a region two orders of magnitude longer, in
     # the same process on the same engine, so that the short region's number is corroborated in the same output line
     # (default line only: one GPU, configs[1]).
     long_region = None
-    if (world == 1 and not tta and not strong and not use_dist and args.precision == "fp16" and B == 64 and args.seconds == 10.0
-            and not args.no_extra):
+    if (args.full and world == 1 and not tta and not strong and not use_dist and args.precision == "fp16" and B == 64
+            and args.seconds == 10.0 and not args.no_extra):
         n_long = 2000
         fetched["batches"] = fetched["rows"] = 0
         sync_all()
@@ -739,14 +814,18 @@ def main():
         long_region = {"steps": n_long, "ms_per_step": round(dt_long / n_long * 1e3, 3), "value": round(B * n_long / dt_long, 2),
                        "unit": "utterances/s", "note": "same step() as the timed region, run after it"}
 
-    # sanity: results come back and look like predictions
+    # sanity (--full): results come back and look like predictions
     if strong:
         audio, lengths = audio[: min(B, 64)].contiguous(), [n] * min(B, 64)
         B = len(lengths)
-    res = eng.predict_batch(audio, lengths, want_text=False)
-    if not os.environ.get("QVERSE_SKIP"):   # (timing experiments drop kernels: results are meaningless then)
-        assert len(res) == B and all(r["t_frames"] == eng.frames_for(n) for r in res)
-    used_ctc = sum(r["use_ctc"] for r in res)
+    if args.full:
+        res = eng.predict_batch(audio, lengths, want_text=False)
+        if not os.environ.get("QVERSE_SKIP"):   # (timing experiments drop kernels: results are meaningless then)
+            assert len(res) == B and all(r["t_frames"] == eng.frames_for(n) for r in res)
+        used_ctc = sum(r["use_ctc"] for r in res)
+    else:   # a plain run counts them in the timed path's last batch (the TTA / collective rows do not carry the flag)
+        last = fetched.get("last") if not (tta or strong or use_dist) else None
+        used_ctc = sum(r["use_ctc"] for r in last) if last else None
     rows_per_launch = B * eng.frames_for(n)   # M of the encoder GEMMs
 
     # ---- roofline of the dominant kernel -----------------------------------------------------
@@ -757,7 +836,7 @@ def main():
     # timing of EVERY GEMM class of a few full steps is reported next to it (that one includes the
     # event/launch gap of each launch, so it reads lower).
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # Dominant kernel by time in rocprofv3's table of this very command (profiles/r0*_kernel_stats.csv): the
         # RESIDUAL-epilogue GEMM class -- FFN-down [M,2048]x[2048,512] (2 per layer) and the attention out-projection /
         # second pointwise convolution [M,512]x[512,512] (1 + 1 per layer), one kernel name, 68 launches per step.  It is
@@ -855,12 +934,12 @@ def main():
     post = None
     mix = None
     ingest = None
-    if rank == 0 and not args.no_post_logits and not tta and not strong and world == 1:
+    if rank == 0 and args.full and not args.no_post_logits and not tta and not strong and world == 1:
         try:
             ingest = ingest_leg(eng, audio_np, lengths, B, eng.frames_for(n), max(10, min(args.steps, 30)), value)
         except Exception as e:
             ingest = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and not args.no_post_logits:
+    if rank == 0 and args.full and not args.no_post_logits:
         try:
             post = post_logits_legs(eng, min(B, 64), min(126, eng.frames_for(cap)))
         except Exception as e:
@@ -872,7 +951,7 @@ def main():
                 mix = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(audio_np, args.cpu_sample,
                                f"{args.seconds:g} s clips" + (" (anchor pass only, no TTA copies)" if tta else ""))
@@ -882,7 +961,7 @@ def main():
 
     extra = None
     default_line = (world == 1 and not tta and not strong and args.precision == "fp16" and B == 64 and args.seconds == 10.0)
-    if rank == 0 and default_line and not args.no_extra:
+    if rank == 0 and args.full and default_line and not args.no_extra:
         eng.close()   # the legs create engines of their own on this GPU
         extra = extra_legs()
 

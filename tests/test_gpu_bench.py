@@ -22,7 +22,7 @@ def _line(out: str) -> dict:
 
 
 def test_bench_single_process_contract():
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "8",
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--batch", "8",
                         "--seconds", "5", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
@@ -41,12 +41,40 @@ def test_bench_single_process_contract():
     assert pl["gate_fail"]["ms_per_batch"] > pl["gate_pass"]["ms_per_batch"] > 0
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline only (every secondary block null) and --dump-outputs writes the
+    rows the timed path returned for its last step, one float64 entry per utterance"""
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                        "--seconds", "5", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _line(p.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "utterances/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "post_logits", "realistic_mix", "ingest", "long_region", "extra"):
+        assert d[k] is None, k
+    import numpy as np
+
+    arrs = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert {"surah", "ayah", "ayah_end", "score", "source", "use_ctc", "t_frames"} <= set(arrs), sorted(arrs)
+    assert all(a.dtype == np.float64 and a.shape[0] == 8 for a in arrs.values())
+    assert np.isfinite(arrs["score"]).all() and (arrs["t_frames"] == arrs["t_frames"][0]).all() and arrs["t_frames"][0] > 0
+    assert d["config"]["gate_failed_utterances_per_batch"] == int(arrs["use_ctc"].sum())
+
+
+def _own_queues_env() -> dict:
+    """the caller's environment without GPU_MAX_HW_QUEUES, so that the child runs on the hardware queues the package
+    exports (8) and not on whatever the calling shell chose: the four-context assertions below are about that setup"""
+    return {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+
+
 def test_bench_tta30_workload_small():
     """--workload tta30 (BASELINE configs[4]) at a reduced size: anchor pass, gate, GPU-resampled copies,
     decision rule; seeded random weights gate every clip."""
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tta30", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--workload", "tta30", "--steps", "2", "--warmup", "1",
                         "--batch", "4", "--seconds", "6", "--no-cpu-baseline", "--no-post-logits"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+                       capture_output=True, text=True, timeout=600, cwd=ROOT, env=_own_queues_env())
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)
     assert "TTA" in d["metric"] and d["config"]["tta_gated_fraction"] == 1.0 and d["value"] > 0
@@ -56,7 +84,7 @@ def test_bench_tta30_workload_small():
 def test_bench_tta30_with_the_reference_gate_ratio_small():
     """--tta-mix: the anchor pass reads verse-shaped log-probs at the v1 run's 46 : 7 branch ratio, so only about one clip in
     eight fails the 0.5 gate and gets its 0.9x / 1.1x copies (seeded random weights alone gate every clip)."""
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "tta30", "--tta-mix", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--workload", "tta30", "--tta-mix", "--steps", "3", "--warmup", "1",
                         "--batch", "16", "--seconds", "8", "--no-cpu-baseline", "--no-post-logits"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -68,7 +96,7 @@ def test_bench_tta30_with_the_reference_gate_ratio_small():
 def test_bench_under_torchrun_with_collective_path():
     env = dict(os.environ, QVERSE_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-                        "--master-addr", "127.0.0.1", "--master-port", "29731", str(ROOT / "bench.py"), "--gpus", "1",
+                        "--master-addr", "127.0.0.1", "--master-port", "29731", str(ROOT / "bench.py"), "--full", "--gpus", "1",
                         "--steps", "5", "--warmup", "2", "--batch", "8", "--seconds", "5", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
@@ -82,7 +110,7 @@ def test_bench_tta30_under_torchrun_with_collective_path():
     side stream (bench.py tta_done) -- the one multi-GPU path no test had executed."""
     env = dict(os.environ, QVERSE_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-                        "--master-addr", "127.0.0.1", "--master-port", "29733", str(ROOT / "bench.py"), "--gpus", "1",
+                        "--master-addr", "127.0.0.1", "--master-port", "29733", str(ROOT / "bench.py"), "--full", "--gpus", "1",
                         "--workload", "tta30", "--steps", "3", "--warmup", "1", "--batch", "4", "--seconds", "6",
                         "--no-cpu-baseline", "--no-post-logits"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
@@ -146,7 +174,7 @@ def test_engine_created_before_any_other_device_work_runs_at_full_speed():
 
     def run(order):
         out = subprocess.run([sys.executable, str(ROOT / "tools" / "init_order_probe.py"), order, "--steps", "40"],
-                             capture_output=True, text=True, timeout=300, cwd=str(ROOT))
+                             capture_output=True, text=True, timeout=300, cwd=str(ROOT), env=_own_queues_env())
         assert out.returncode == 0, out.stderr[-2000:]
         return json.loads(out.stdout.strip().splitlines()[-1])
 
@@ -161,7 +189,7 @@ def test_bench_strong2048_under_torchrun_with_the_sharded_gather():
     un-permutes the rows over RCCL -- the functions the sharded runner entry ships, at the size of BASELINE configs[3]."""
     env = dict(os.environ, QVERSE_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-                        "--master-addr", "127.0.0.1", "--master-port", "29563", str(ROOT / "bench.py"), "--gpus", "1",
+                        "--master-addr", "127.0.0.1", "--master-port", "29563", str(ROOT / "bench.py"), "--full", "--gpus", "1",
                         "--workload", "strong2048", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-post-logits"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -174,7 +202,7 @@ def test_bench_strong2048_under_torchrun_with_the_sharded_gather():
 def test_bench_ingest_leg_small():
     """the `ingest` leg of the default line at a reduced size: distinct pinned host batches cross PCIe on a copy stream into a ring
     of device buffers one step ahead of the engine; every timed forward is accounted for (graph replays + plain launches)."""
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "10", "--warmup", "2", "--batch", "8",
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--batch", "8",
                         "--seconds", "5", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _line(p.stdout)

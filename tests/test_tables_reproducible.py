@@ -1,7 +1,9 @@
 """The committed static tables (offline-tarteel_amd/data/qverse_tables.bin) are exactly what
 tools/build_tables.py derives from the reference's DATA files (data/quran.json and the
-SentencePiece model).  Runs only where the reference checkout is mounted (the build container)."""
+SentencePiece model web/frontend/public/tokenizer.model), stored byte for byte as xz fixtures
+under tests/golden/."""
 
+import lzma
 import subprocess
 import sys
 from pathlib import Path
@@ -9,12 +11,22 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
-QURAN = Path("/root/reference/data/quran.json")
-TOKENIZER = Path("/root/reference/web/frontend/public/tokenizer.model")
+GOLDEN = ROOT / "tests" / "golden"
 
 
-@pytest.mark.skipif(not (QURAN.exists() and TOKENIZER.exists()), reason="reference data files not mounted")
-def test_tables_rebuild_bit_identical(tmp_path):
+@pytest.fixture
+def ref_data(tmp_path):
+    """(quran.json, tokenizer.model) unpacked from the committed fixtures into tmp_path"""
+    out = []
+    for name in ("quran.json", "tokenizer.model"):
+        dst = tmp_path / name
+        dst.write_bytes(lzma.decompress((GOLDEN / f"{name}.xz").read_bytes()))
+        out.append(dst)
+    return out
+
+
+def test_tables_rebuild_bit_identical(tmp_path, ref_data):
+    QURAN, TOKENIZER = ref_data
     out = tmp_path / "tables.bin"
     r = subprocess.run([sys.executable, str(ROOT / "tools" / "build_tables.py"), "--quran", str(QURAN),
                         "--tokenizer", str(TOKENIZER), "--out", str(out)], capture_output=True, text=True, timeout=900)
@@ -23,8 +35,7 @@ def test_tables_rebuild_bit_identical(tmp_path):
     assert out.read_bytes() == committed
 
 
-@pytest.mark.skipif(not (QURAN.exists() and TOKENIZER.exists()), reason="reference data files not mounted")
-def test_emit_json_matches_the_upstream_artefact_shape(tmp_path):
+def test_emit_json_matches_the_upstream_artefact_shape(tmp_path, ref_data):
     """--emit-json writes quran_ctc_tokens.json as PLAN.md:102-103 describes the upstream file: 35,717 keys
     "surah:ayah:ayah_end", 29,481 of them multi-ayah spans -- which is every span of at most SIX ayat inside
     a surah (five would give 30,043 keys; the prose at PLAN.md:121-124 says five, the counts say six) -- ids of
@@ -36,6 +47,7 @@ def test_emit_json_matches_the_upstream_artefact_shape(tmp_path):
     import offline_tarteel_amd
     from offline_tarteel_amd.tables import Tables
 
+    QURAN, TOKENIZER = ref_data
     out, js = tmp_path / "tables.bin", tmp_path / "quran_ctc_tokens.json"
     r = subprocess.run([sys.executable, str(ROOT / "tools" / "build_tables.py"), "--quran", str(QURAN), "--tokenizer",
                         str(TOKENIZER), "--out", str(out), "--emit-json", str(js)], capture_output=True, text=True, timeout=900)

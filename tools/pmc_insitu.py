@@ -2,7 +2,7 @@
 """Matrix-pipe utilisation of the GEMM family IN SITU: fold the counter CSV of
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d DIR -o p -- \
-        python bench.py --contexts 1 [--batch 256] --steps 3 --warmup 1 --no-cpu-baseline --no-post-logits --no-extra
+        python bench.py --full --contexts 1 [--batch 256] --steps 3 --warmup 1 --no-cpu-baseline --no-post-logits --no-extra
 
 (the bench command itself, one batch at a time: counter collection serialises dispatches anyway) into one number per GEMM
 kernel and one for ALL GEMM launches together, weighted by what each launch offered:

@@ -4,7 +4,7 @@ R=$(pwd)
 timeout 1500 python -m pytest tests/test_gpu_postlogits.py tests/test_gpu_tracker.py tests/test_gpu_tta.py tests/test_gpu_audio.py -x -q > $O/tests.log 2>&1; tail -5 $O/tests.log
 timeout 300 python tools/post_bench.py > $O/post_bench.jsonl 2>&1; cut -c1-150 $O/post_bench.jsonl
 timeout 300 python tools/post_bench.py --frames 376 > $O/post_bench_376.jsonl 2>&1; cut -c1-150 $O/post_bench_376.jsonl
-A="--no-cpu-baseline --no-extra"
+A="--full --no-cpu-baseline --no-extra"
 timeout 300 python bench.py --steps 20 --warmup 5 $A > $O/bench_default.json 2> $O/bench_default.err
 timeout 300 python bench.py --workload tta30 --steps 5 --warmup 2 $A --no-post-logits > $O/bench_tta30.json 2> $O/bench_tta30.err
 timeout 300 python bench.py --workload tta30 --tta-mix --steps 8 --warmup 3 $A --no-post-logits > $O/bench_tta30_mix.json 2> $O/bench_tta30_mix.err

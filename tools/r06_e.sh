@@ -1,7 +1,7 @@
 set -u
 O=gpurun_out/r06_e; mkdir -p $O
 timeout 2400 python -m pytest tests/test_gpu_audio.py tests/test_gpu_bench.py tests/test_gpu_tta.py -x -q > $O/tests.log 2>&1; tail -15 $O/tests.log
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_default.json 2> $O/bench_default.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06_e/bench_default.json").read().strip().splitlines()[-1])
