@@ -44,7 +44,8 @@ extern "C" {
 
 #define QV_VOCAB 1025
 #define QV_BLANK 1024
-#define QV_MAX_TRANSCRIPT 1024 /* normalised transcript chars handled on device */
+#define QV_MAX_TRANSCRIPT 1024      /* normalised transcript chars handled on device: the default window */
+#define QV_MAX_TRANSCRIPT_WIDE 2048 /* ... and the opt-in wide one (qv_config.max_transcript) */
 
 enum {
     QV_OK = 0,
@@ -60,7 +61,7 @@ enum { QV_SOURCE_NONE = 0, QV_SOURCE_TEXT = 1, QV_SOURCE_CTC = 2 };
 /* flags in qv_result.flags */
 enum {
     QV_FLAG_EMPTY_TRANSCRIPT = 1,   /* greedy decode produced nothing -> _empty("") */
-    QV_FLAG_TRANSCRIPT_TRUNCATED = 2,/* > QV_MAX_TRANSCRIPT chars: prediction withheld (surah 0) */
+    QV_FLAG_TRANSCRIPT_TRUNCATED = 2,/* more chars than the engine's window (qv_max_transcript): prediction withheld (surah 0) */
     QV_FLAG_USED_CTC = 4,           /* gate failed (base.score < threshold): rerank ran */
     QV_FLAG_CAND_OVERFLOW = 8       /* candidate list clipped at engine capacity */
 };
@@ -104,6 +105,11 @@ typedef struct {
                                    contexts (own activations, workspace and internal stream), so
                                    the latency-bound decode/retrieval/CTC kernels of one batch run
                                    under the forward pass of the next.  Memory scales with it. */
+    int32_t max_transcript;     /* matching window in normalised chars: 0 or 1024 (QV_MAX_TRANSCRIPT, the default) or
+                                   2048 (QV_MAX_TRANSCRIPT_WIDE: a second set of matching kernels with a 32-word
+                                   pattern; about 12 KB more state per utterance and context).  Anything else is
+                                   QV_ERR_ARG.  Appended after the first published layout: qv_create() accepts a
+                                   struct_size that ends with n_contexts and reads this field as 0. */
 } qv_config;
 
 /* One prediction; mirrors the dict of experiments/c2c-direct-mixed/run.py:126-133. */
@@ -124,6 +130,8 @@ void qv_config_default(qv_config *cfg);
 int qv_create(const qv_config *cfg, qv_engine **out);
 void qv_destroy(qv_engine *e);
 const char *qv_last_error(const qv_engine *e); /* e may be NULL: last create() error */
+/* The engine's matching window: 1024 or 2048 normalised chars (qv_config.max_transcript); 0 for a NULL engine. */
+int32_t qv_max_transcript(const qv_engine *e);
 
 /* Encoder frames produced for n_samples of 16 kHz audio (three stride-2 stages over
  * floor(n/160)+1 mel frames). */
@@ -230,8 +238,9 @@ int qv_fetch_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, int32_t t_max
  * bonus_verse_host[b] = global index of the verse that gets the continuation bonus
  * (QuranDB.get_next_verse of the last emission, shared/quran_db.py:81-90) or -1.
  * out_host[b].verse = -1 when no verse scores above 0.0; the minimum-emit-score and
- * minimum-word-count gates of the caller are NOT applied here.  Texts longer than
- * QV_MAX_TRANSCRIPT codes are refused (QV_ERR_CAPACITY).  SYNCHRONOUS on `stream`. */
+ * minimum-word-count gates of the caller are NOT applied here.  Texts longer than the
+ * engine's window (qv_max_transcript() codes) are refused (QV_ERR_CAPACITY), as they are by
+ * qv_match_verse and qv_debug_retrieve.  SYNCHRONOUS on `stream`. */
 typedef struct qv_track_match {
     int32_t verse;     /* global verse index, -1 = none */
     int32_t surah, ayah;

@@ -174,6 +174,7 @@ extern "C" void qv_config_default(qv_config *c) {
     c->span_penalty = 0.5;
     c->skip_unused_passes = 1;
     c->n_contexts = 1;
+    c->max_transcript = QV_MAX_TRANSCRIPT;
 }
 
 extern "C" int32_t qv_frames_for_samples(int64_t n) {
@@ -438,9 +439,10 @@ static int alloc_work(qv_engine *eng, int k) {
     QV_TRY(dalloc(eng, Bz, &w.utt));
     QV_TRY(dalloc(eng, Bz * w.t_cap, &w.frame_ids));
     QV_TRY(dalloc(eng, Bz * w.t_cap, &w.greedy));
-    QV_TRY(dalloc(eng, Bz * QV_MAXQ + 64, &w.q));
-    QV_TRY(dalloc(eng, Bz * QV_MAXQ + 64, &w.qs));
-    QV_TRY(dalloc(eng, Bz * 2 * QV_NSYM * QV_MAXW, &w.pm));
+    const size_t maxq = (size_t)eng->max_q;   // the engine's window: pitch of q / qs, 64 bits of it per mask word
+    QV_TRY(dalloc(eng, Bz * maxq + 64, &w.q));
+    QV_TRY(dalloc(eng, Bz * maxq + 64, &w.qs));
+    QV_TRY(dalloc(eng, Bz * 2 * QV_NSYM * (maxq / 64), &w.pm));
     QV_TRY(dalloc(eng, Bz * N, &w.cand1));
     QV_TRY(dalloc(eng, Bz * N * 3, &w.lcsf));
     QV_TRY(dalloc(eng, Bz * N * 3, &w.fs));
@@ -506,13 +508,22 @@ static int alloc_work(qv_engine *eng, int k) {
     return QV_OK;
 }
 
-extern "C" int qv_create(const qv_config *cfg, qv_engine **out) {
-    if (!cfg || !out || cfg->struct_size != (int32_t)sizeof(qv_config)) {
+extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
+    const qv_config *cfg = cfg_in;
+    // struct_size: the layout the caller was compiled against.  Fields are only ever appended, so a shorter struct is an
+    // older caller -- accepted from the first published layout (everything up to and including n_contexts) on, with the
+    // fields it does not know at 0 -- and a longer one is a caller newer than this library, which is refused.
+    const int32_t size_v1 = (int32_t)(offsetof(qv_config, n_contexts) + sizeof(int32_t));
+    if (!cfg || !out || cfg->struct_size < size_v1 || cfg->struct_size > (int32_t)sizeof(qv_config)) {
         qv_set_error(nullptr, "qv_create: bad config (struct_size mismatch?)");
         return QV_ERR_ARG;
     }
     qv_engine *eng = new qv_engine();
-    eng->cfg = *cfg;
+    memset(&eng->cfg, 0, sizeof eng->cfg);
+    memcpy(&eng->cfg, cfg_in, (size_t)cfg_in->struct_size);
+    eng->cfg.struct_size = (int32_t)sizeof(qv_config);
+    cfg = &eng->cfg;
+    eng->max_q = cfg->max_transcript == 0 ? QV_MAX_TRANSCRIPT : cfg->max_transcript;
     eng->model = nullptr;
     eng->t_host_scratch = nullptr;
     eng->last_batch = eng->last_tmax = 0;
@@ -536,6 +547,11 @@ extern "C" int qv_create(const qv_config *cfg, qv_engine **out) {
         qv_destroy(eng);
         return rc;
     };
+    if (eng->max_q != QV_MAX_TRANSCRIPT && eng->max_q != QV_MAX_TRANSCRIPT_WIDE) {
+        eng->max_q = QV_MAX_TRANSCRIPT;
+        qv_set_error(eng, "max_transcript must be 0, 1024 or 2048");
+        return fail(QV_ERR_ARG);
+    }
     if (cfg->max_span < 2 || cfg->max_span > QV_MAX_SPAN) { qv_set_error(eng, "CTC_DIRECT_MAX_SPAN must be in [2,6]"); return fail(QV_ERR_ARG); }
     // c2c-direct/run.py:67 takes any float (negative weights included); only a non-finite one is refused here: inf * 0.0
     // text scores would put NaNs into the final scores and leave the winner undefined
@@ -595,14 +611,14 @@ extern "C" int qv_create(const qv_config *cfg, qv_engine **out) {
     }
     {   // verse tracker workspace (qv_tracker_match)
         QvTrack &t = eng->track;
-        if ((rc = dalloc(eng, (size_t)QV_TRACK_CAP * QV_MAXQ, &t.q)) || (rc = dalloc(eng, (size_t)QV_TRACK_CAP * 4, &t.meta)) ||
+        if ((rc = dalloc(eng, (size_t)QV_TRACK_CAP * eng->max_q + 64, &t.q)) || (rc = dalloc(eng, (size_t)QV_TRACK_CAP * 4, &t.meta)) ||
             (rc = dalloc(eng, (size_t)QV_TRACK_CAP * QV_TRACK_BLOCKS, &t.part_s)) ||
             (rc = dalloc(eng, (size_t)QV_TRACK_CAP * QV_TRACK_BLOCKS, &t.part_k)) ||
             (rc = dalloc(eng, (size_t)QV_TRACK_CAP, &t.out)))
             return fail(rc);
     }
     if (cfg->with_model) {
-        rc = qv_model_create(eng, cfg, &eng->model);
+        rc = qv_model_create(eng, &eng->cfg, &eng->model);
         if (rc) return fail(rc);
     }
     qv_select_ctx(eng, 0);
@@ -645,7 +661,7 @@ extern "C" int qv_decode_retrieve_rerank_async(qv_engine *eng, const float *lp, 
     if (!eng || !lp || !t_host || batch < 1) return QV_ERR_ARG;
     qv_stage_mark(eng, 0, (hipStream_t)stream);   // no forward in this call: forward = 0
     qv_stage_mark(eng, 1, (hipStream_t)stream);
-    return qv_post_run(eng, lp, t_max, t_host, batch, (hipStream_t)stream);
+    return QV_POST(eng, qv_post_run)(eng, lp, t_max, t_host, batch, (hipStream_t)stream);
 }
 
 void qv_stage_mark(qv_engine *eng, int i, hipStream_t s) {
@@ -752,9 +768,9 @@ extern "C" int qv_predict_batch_async(qv_engine *eng, const float *audio_dev, co
     qv_stage_mark(eng, 1, run);
     if (eng->inject_lp) {
         if (batch > eng->inject_batch) { qv_set_error(eng, "injected log-probs hold fewer utterances than the batch"); return QV_ERR_ARG; }
-        rc = qv_post_run(eng, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
+        rc = QV_POST(eng, qv_post_run)(eng, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
     } else
-    rc = qv_post_run(eng, eng->logprobs_ws, t_max, t_out.data(), batch, run);
+    rc = QV_POST(eng, qv_post_run)(eng, eng->logprobs_ws, t_max, t_out.data(), batch, run);
     if (rc) return rc;
     if (eng->n_ctx > 1) {
         QvCtx &c = eng->ctx[eng->cur_ctx];
@@ -866,6 +882,7 @@ extern "C" int qv_mixdown_batch(qv_engine *eng, const float *x_dev, int64_t x_pi
 
 extern "C" const int32_t *qv_packed_results_dev(qv_engine *eng) { return eng ? eng->work.packed : nullptr; }
 
+extern "C" int32_t qv_max_transcript(const qv_engine *eng) { return eng ? eng->max_q : 0; }   // fixed at qv_create
 extern "C" int32_t qv_context_count(const qv_engine *eng) { return eng ? eng->n_ctx : 0; }   // fixed at qv_create
 extern "C" int32_t qv_last_context(const qv_engine *eng) {
     if (!eng) return -1;
@@ -914,7 +931,7 @@ extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int3
     QV_ORDERED(eng, stream_);
     hipStream_t stream = (hipStream_t)stream_;
     if (!eng) return QV_ERR_ARG;
-    int rc = qv_post_debug_retrieve(eng, codes_host, n_codes, stream);
+    int rc = QV_POST(eng, qv_post_debug_retrieve)(eng, codes_host, n_codes, stream);
     if (rc) return rc;
     QvUtt u;
     QV_HIP(hipMemcpy(&u, eng->work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));
@@ -950,9 +967,9 @@ extern "C" int qv_tracker_match(qv_engine *eng, const uint8_t *codes_host, const
             qv_set_error(eng, "qv_tracker_match: bad offsets / word count / bonus verse");
             return QV_ERR_ARG;
         }
-        if (n > QV_MAXQ) { qv_set_error(eng, "qv_tracker_match: text longer than QV_MAX_TRANSCRIPT"); return QV_ERR_CAPACITY; }
+        if (n > eng->max_q) { qv_set_error(eng, "qv_tracker_match: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     }
-    return qv_post_tracker_match(eng, codes_host, offsets_host, n_words_host, bonus_verse_host, batch, out_host,
+    return QV_POST(eng, qv_post_tracker_match)(eng, codes_host, offsets_host, n_words_host, bonus_verse_host, batch, out_host,
                                  (hipStream_t)stream);
 }
 
@@ -978,9 +995,9 @@ extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t
     }
     for (int i = 0; i < n_bonus; ++i)
         if (bonus_verse[i] < 0 || bonus_verse[i] >= eng->tab.n_verses) { qv_set_error(eng, "qv_match_verse: bonus verse out of range"); return QV_ERR_ARG; }
-    if (n_codes > QV_MAXQ) { qv_set_error(eng, "qv_match_verse: text longer than QV_MAX_TRANSCRIPT"); return QV_ERR_CAPACITY; }
+    if (n_codes > eng->max_q) { qv_set_error(eng, "qv_match_verse: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     QV_TRY(quiesce_contexts(eng));
-    int rc = qv_post_match_verse(eng, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
+    int rc = QV_POST(eng, qv_post_match_verse)(eng, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
     if (rc) return rc;
     QvUtt u;
     QV_HIP(hipMemcpy(&u, eng->work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));

@@ -13,7 +13,13 @@
 
 #define QV_NSYM 40          // alphabet codes 0..39 (0 = ' '); 63 = matches nothing
 #define QV_OTHER 63
+// The matching window is a compile-time constant of the post-logits kernels (buffer pitches, LDS arrays, the word counts the
+// LCS core is instantiated for).  qv_postlogits.hip is compiled twice: as itself with the default window, and through
+// qv_postlogits_wide.hip with QV_MAXQ = QV_MAX_TRANSCRIPT_WIDE, kernels in namespace qv_wide and launchers named qv_post_*_wide.
+// An engine picks one set at qv_create (qv_engine::max_q, QV_POST).
+#ifndef QV_MAXQ
 #define QV_MAXQ QV_MAX_TRANSCRIPT
+#endif
 #define QV_MAXW (QV_MAXQ / 64)
 #define QV_MAX_SPAN 6
 #define QV_CAND_CAP 2048
@@ -127,7 +133,7 @@ struct QvWork {
     QvUtt *utt;              // [B]
     int16_t *frame_ids;      // [B][t_cap]
     int32_t *greedy;         // [B][t_cap]
-    uint8_t *q;              // [B][QV_MAXQ]
+    uint8_t *q;              // [B][QV_MAXQ]   (QV_MAXQ, QV_MAXW: of the kernel set the engine runs -- eng->max_q and max_q / 64)
     uint8_t *qs;             // [B][QV_MAXQ] spaceless
     uint64_t *pm;            // [B][2][QV_NSYM][QV_MAXW]  (0: q, 1: spaceless q)
     int32_t *cand1;          // [B][N]
@@ -191,6 +197,16 @@ int qv_post_match_verse(qv_engine *eng, const uint8_t *codes_host, int n, int n_
                         const double *bonus_value, int max_span, hipStream_t stream);
 int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg, const int32_t *lens, int n,
                       float *loss_host, hipStream_t stream);
+// the same launchers over the kernel set of the wide window (qv_postlogits_wide.hip)
+int qv_post_tracker_match_wide(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
+                               const int32_t *n_words_host, const int32_t *bonus_host, int batch,
+                               qv_track_match *out_host, hipStream_t stream);
+int qv_post_run_wide(qv_engine *eng, const float *logprobs_dev, int t_max, const int32_t *t_host, int batch,
+                     hipStream_t stream);
+int qv_post_debug_retrieve_wide(qv_engine *eng, const uint8_t *codes_host, int n, hipStream_t stream);
+int qv_post_match_verse_wide(qv_engine *eng, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
+                             const double *bonus_value, int max_span, hipStream_t stream);
+#define QV_POST(eng, fn) ((eng)->max_q > QV_MAX_TRANSCRIPT ? fn##_wide : fn)
 
 // acoustic model (qv_model.hip)
 struct QvModel;
@@ -237,7 +253,7 @@ struct QvCtx {
     bool stage_valid;
     // the post-logits chain (k_decode .. k_result, 13 kernels) as ONE hipGraph launch, keyed by what the kernel
     // arguments depend on; captured the first time a key is seen on this context
-    struct PostGraph { const float *lp; int batch, t_max, variants; hipGraphExec_t exec; } post_graph[4];   // variants: the kernel variants in force (spans, CTC)
+    struct PostGraph { const float *lp; int batch, t_max, variants; hipGraphExec_t exec; } post_graph[4];   // variants: the kernel variants in force (spans, CTC) and the engine's window
     bool post_graph_off = false;   // a capture / instantiate failed on this context: plain launches from then on
     int n_post_graph;
 };
@@ -253,6 +269,7 @@ struct qv_engine {
     hipStream_t tail_stream = nullptr;
     bool tail_valid = false;
     qv_config cfg;
+    int max_q = QV_MAX_TRANSCRIPT;   // the matching window, 1024 or 2048: which set of post-logits kernels runs (QV_POST)
     QvKnobs knobs;
     int device;
     std::string last_error;

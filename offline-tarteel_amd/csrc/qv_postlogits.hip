@@ -23,7 +23,14 @@
 #include <algorithm>
 #include <type_traits>
 
-namespace {
+// This file is compiled twice (qv_common.h, QV_MAXQ): as itself for the default window of 1,024 characters, and through
+// qv_postlogits_wide.hip for the window of 2,048.  What only the wide set needs is under `#if QV_MAXW > 16` or a template
+// argument the default set never instantiates: the default kernels compile to the instructions they were before the wide
+// window existed (tools/dev_kernel_diff.sh compares the disassembly of two libraries kernel by kernel).
+#ifndef QV_POST_NS
+#define QV_POST_NS   // default set: anonymous namespace
+#endif
+namespace QV_POST_NS {
 
 // ------------------------------------------------------------------ small helpers ------
 
@@ -283,7 +290,10 @@ __device__ __forceinline__ int lcs_core(const uint64_t *__restrict__ pm, int str
     return lcs_count<W>(V, m);
 }
 
-template <bool ZROW = false>
+// WMAX: the longest pattern the call site can have.  Verse texts are at most QV_MAX_VW words, so only the sites whose
+// pattern is the TRANSCRIPT instantiate the 24- and 32-word cores of the wide window (V[W] and one step's W mask words
+// live in VGPRs: 64 + 64 registers at 32 words, CH = 1; the kernel's register count is that of its widest core).
+template <bool ZROW = false, int WMAX = QV_MAXW>
 __device__ __forceinline__ int lcs_dispatch(int W, const uint64_t *pm, int stride, const uint8_t *text, int n, int m) {
     if (n <= 0 || m <= 0) return 0;
     if (W <= 1) return lcs_core<1, ZROW>(pm, stride, text, n, m);
@@ -293,6 +303,13 @@ __device__ __forceinline__ int lcs_dispatch(int W, const uint64_t *pm, int strid
     if (W <= 6) return lcs_core<6, ZROW>(pm, stride, text, n, m);
     if (W <= 8) return lcs_core<8, ZROW>(pm, stride, text, n, m);
     if (W <= 11) return lcs_core<11, ZROW>(pm, stride, text, n, m);
+#if QV_MAXW > 16
+    if constexpr (WMAX > 16) {
+        if (W <= 16) return lcs_core<16, ZROW>(pm, stride, text, n, m);
+        if (W <= 24) return lcs_core<24, ZROW>(pm, stride, text, n, m);
+        return lcs_core<32, ZROW>(pm, stride, text, n, m);
+    }
+#endif
     return lcs_core<16, ZROW>(pm, stride, text, n, m);
 }
 
@@ -302,6 +319,15 @@ __device__ __forceinline__ int lcs_dispatch(int W, const uint64_t *pm, int strid
 // W of them: the span pass and the window scans last as long as their LONGEST lane, and for transcripts of several hundred
 // characters (W = 4..7) that lane used to walk 1,000+ codes x W words.  Same integer result as lcs_core.
 // All G lanes pass the same text / n / m / W; the return value is valid in every lane of the group.
+// G = 32 (wide window, 17..32 words): row_shr:1 stops at the 16-lane DPP row, so lane 16 of a group would never see lane
+// 15's carry; there the carry moves with a wave-wide shuffle (ds_bpermute_b32) -- lcs_carry_in.
+template <int G>
+__device__ __forceinline__ unsigned lcs_carry_in(unsigned cout) {
+#if QV_MAXW > 16
+    if constexpr (G > 16) return (unsigned)__shfl_up((int)cout, 1);
+#endif
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)cout, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
+}
 template <int G>
 __device__ __forceinline__ int lcs_systolic(const uint64_t *__restrict__ pm, int stride, const uint8_t *__restrict__ text, int n,
                                             int m, int W, int w) {
@@ -323,7 +349,7 @@ __device__ __forceinline__ int lcs_systolic(const uint64_t *__restrict__ pm, int
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            unsigned cin = (unsigned)__builtin_amdgcn_update_dpp(0, (int)cout, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
+            unsigned cin = lcs_carry_in<G>(cout);
             if (w == 0) cin = 0;
             unsigned long long carry;
             const uint64_t s2 = __builtin_addcll(V, V & mk[e], (unsigned long long)cin, &carry);
@@ -731,10 +757,21 @@ __device__ __forceinline__ TextRef text_of(const QvTables &tab, int v, int varia
 #ifndef FRAG_STEP
 #define FRAG_STEP 4          // anchor spacing of the coarse pass (power of two, >= 4)
 #endif
+#if QV_MAXW > 16
+// wide window: up to 2,048 windows of a verse-sized pattern over the transcript -- 514 anchors, then the refine list
+#define FRAG_LIST_OFF 520
+#define FRAG_SCRATCH (FRAG_LIST_OFF + QV_MAXQ)
+#else
 #define FRAG_SCRATCH 2112      // int16 per wave: anchors [QV_MAXQ / 4 + 2] + refine list [QV_MAXQ]
+#define FRAG_LIST_OFF (FRAG_SCRATCH / 2)
+#endif
 #define FRAG_HEAVY 1200       // word-steps per lane above which a window scan counts as expensive (k_lcs_full's two-ended list)
 #define FRAG_GRID 1024         // blocks of k_frag (4 waves each): four per CU, the list is consumed by whoever is free
-#define FRAG_PM_STRIDE (QV_MAXW + 1)   // u64 per symbol row of the wave's LDS copy of the pattern masks (odd: rows spread over the banks)
+// u64 per symbol row of the wave's LDS copy of the pattern masks (odd: rows spread over the banks).  The pattern of a window
+// scan is the SHORTER string, i.e. never longer than the longest verse text (QV_MAX_VW = 11 words): the slice does not grow
+// with the window, only the scratch lists do (4 waves: 22.3 KB of masks + 20.5 KB of lists at 2,048, three blocks per CU).
+#define FRAG_PM_STRIDE 17
+static_assert(FRAG_PM_STRIDE > QV_MAX_VW, "k_frag's mask slice holds a verse-sized pattern");
 __device__ __forceinline__ void frag_job(const QvTables &tab, const QvWork &wk, int b, int v, int variant, int lane, int16_t *scratch, uint64_t *lpm) {
     const QvUtt &u = wk.utt[b];
     double *out = wk.fs + ((size_t)b * tab.n_verses + v) * 3 + variant;
@@ -796,7 +833,7 @@ __device__ __forceinline__ void frag_job(const QvTables &tab, const QvWork &wk, 
             best = x;
         }
     }
-    int16_t *cv = scratch, *list = scratch + FRAG_SCRATCH / 2;
+    int16_t *cv = scratch, *list = scratch + FRAG_LIST_OFF;
     if (nwin > 0) {
         // Round 6: the pattern's match masks (40 symbols x W words) move into the wave's own LDS slice for the scan (row
         // QV_NSYM of the slice stays all zero: lcs_chunk<W, true>).  Every step of every window reads W mask words of ITS code:
@@ -815,7 +852,7 @@ __device__ __forceinline__ void frag_job(const QvTables &tab, const QvWork &wk, 
     for (int pass = 0; pass < 2; ++pass) {
         for (int i = lane; i < nlist; i += 64) {
             int w = pass ? (int)list[i] : (direct ? i : (i < nco ? FRAG_STEP * i : nwin - 1));
-            int r = lcs_dispatch<true>(W, lpm, FRAG_PM_STRIDE, lt + w, s, s);
+            int r = lcs_dispatch<true, QV_MAX_VW>(W, lpm, FRAG_PM_STRIDE, lt + w, s, s);
             if (!pass && !direct) cv[i] = (int16_t)r;
             best = max(best, r);
         }
@@ -998,7 +1035,7 @@ __global__ __launch_bounds__(64) void k_hint_sp(QvTables tab, QvWork wk, int b) 
             }
             const int ls = m - start;
             const uint64_t *pm = tab.pmv + tab.pmv_off[t.tid];
-            int l = lcs_dispatch((plen + 63) >> 6, pm, qv_tmpl_w((t.n + 63) >> 6), q + start, ls, plen);
+            int l = lcs_dispatch<false, QV_MAX_VW>((plen + 63) >> 6, pm, qv_tmpl_w((t.n + 63) >> 6), q + start, ls, plen);
             best = ratio_from(l, ls, plen);
         }
     }
@@ -1170,6 +1207,9 @@ __global__ __launch_bounds__(256) void k_spans(QvTables tab, QvWork wk, QvKnobs 
             };
             if (W <= 4) run(std::integral_constant<int, 4>{});
             else if (W <= 8) run(std::integral_constant<int, 8>{});
+#if QV_MAXW > 16
+            else if (W > 16) run(std::integral_constant<int, 32>{});   // half a wave per walk, one word per lane
+#endif
             else run(std::integral_constant<int, 16>{});
         }
     }
@@ -1214,7 +1254,7 @@ __device__ __forceinline__ uint64_t lcs_systolic_chunks(const uint64_t *__restri
     int e = 1, next_end = (int)(off8[j.v0 + 1] - j.a0) >> 3;       // chunks up to the end of ayah e
     for (int t = 0; t < nch + G - 1; ++t) {
         const int c = t - w;
-        unsigned cin8 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)cout8, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
+        unsigned cin8 = lcs_carry_in<G>(cout8);   // (G = 32: one shuffle per CHUNK of 8 codes)
         if (w == 0) cin8 = 0;
         uint64_t chunk = ~0ull;                 // filler: matches nothing
         if (c >= 0 && c < nch) chunk = *(const uint64_t *)(c8 + j.a0 + 8 * (size_t)c);
@@ -1356,6 +1396,9 @@ __global__ __launch_bounds__(256) void k_spans2(QvTables tab, QvWork wk, QvKnobs
             };
             if (W <= 4) run(std::integral_constant<int, 4>{});
             else if (W <= 8) run(std::integral_constant<int, 8>{});
+#if QV_MAXW > 16
+            else if (W > 16) run(std::integral_constant<int, 32>{});   // half a wave per walk, one word per lane
+#endif
             else run(std::integral_constant<int, 16>{});
         }
     }
@@ -2082,7 +2125,7 @@ __global__ void k_track_final(QvTables tab, QvTrack tw, int batch, int nblk) {
     tw.out[b] = r;
 }
 
-}  // namespace
+}  // namespace QV_POST_NS
 
 // ====================================================================== host side =======
 
@@ -2171,7 +2214,7 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
     if (use_graph && !gc.post_graph_off && eng->n_ctx > 1 && stream == gc.stream && lp == eng->logprobs_ws && !eng->profile_stages) {
         // (the kernel variants that pick launches inside the chain are part of the key: a graph captured under another span pass
         // or CTC wave program must not be replayed after qv_debug_kernel_variant changed it)
-        const int variants = qv_kernel_variant(QV_KV_SPANS) | (qv_kernel_variant(QV_KV_CTC) << 4);
+        const int variants = qv_kernel_variant(QV_KV_SPANS) | (qv_kernel_variant(QV_KV_CTC) << 4) | ((QV_MAXW > 16) << 8);
         QvCtx::PostGraph *hit = nullptr;
         for (int i = 0; i < gc.n_post_graph; ++i)
             if (gc.post_graph[i].lp == lp && gc.post_graph[i].batch == batch && gc.post_graph[i].t_max == t_max && gc.post_graph[i].variants == variants)
@@ -2218,7 +2261,7 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
 
 int qv_post_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int n, hipStream_t stream) {
     QvWork &wk = eng->work;
-    if (n > QV_MAXQ) { qv_set_error(eng, "transcript longer than QV_MAX_TRANSCRIPT"); return QV_ERR_CAPACITY; }
+    if (n > QV_MAXQ) { qv_set_error(eng, "transcript longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     int32_t zero = 0;
     QV_HIP(hipMemcpyAsync(eng->t_dev, &zero, sizeof(int32_t), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_init_utts, dim3(1), dim3(64), 0, stream, wk, eng->t_dev, 1);
@@ -2231,6 +2274,7 @@ int qv_post_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int n, hip
     return QV_OK;
 }
 
+#if QV_MAXW <= 16   // (does not depend on the window: only the default set defines it)
 int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg, const int32_t *lens, int n,
                       float *loss_host, hipStream_t stream) {
     std::vector<int32_t> off(n + 1, 0);
@@ -2253,6 +2297,7 @@ int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg
     (void)hipFree(d_t); (void)hipFree(d_o); (void)hipFree(d_l);
     return QV_OK;
 }
+#endif
 
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,

@@ -18,7 +18,8 @@ from .normalizer import normalize_arabic
 from .tables import Tables
 
 QV_SOURCE = {0: None, 1: "text", 2: "ctc"}
-QV_MAX_TRANSCRIPT = 1024   # include/qverse.h: characters the device matchers hold per text
+QV_MAX_TRANSCRIPT = 1024   # include/qverse.h: characters the device matchers hold per text (the default window)
+QV_MAX_TRANSCRIPT_WIDE = 2048   # ... and with Engine(max_transcript=2048)
 
 
 def front_window(text: str, limit: int = QV_MAX_TRANSCRIPT) -> str:
@@ -47,6 +48,7 @@ class QvConfig(C.Structure):
         ("top_text", C.c_int32), ("top_span_refs", C.c_int32), ("max_span", C.c_int32),
         ("threshold", C.c_double), ("text_weight", C.c_double), ("span_penalty", C.c_double),
         ("skip_unused_passes", C.c_int32), ("n_contexts", C.c_int32),
+        ("max_transcript", C.c_int32),
     ]
 
 
@@ -110,6 +112,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_upfirdn_batch.argtypes = [vp, vp, i64, vp, vp, i32, vp, i32, i32, i32, i64, vp, i64, vp]
     lib.qv_mixdown_batch.argtypes = [vp, vp, i64, vp, i32, i32, vp, i64, vp]
     lib.qv_context_count.argtypes = [vp]
+    lib.qv_max_transcript.argtypes = [vp]
+    lib.qv_max_transcript.restype = i32
     lib.qv_probe_concurrent_streams.argtypes = []
     lib.qv_last_context.argtypes = [vp]
     lib.qv_wait_ctx.argtypes = [vp, i32]
@@ -166,7 +170,8 @@ class Engine:
 
     def __init__(self, device: int = 0, with_model: bool = True, weights_path: str | None = None,
                  seed: int = 20260630, precision: int = 0, max_batch: int = 64, max_samples: int = 480000,
-                 tables_path: str | None = None, skip_unused_passes: bool = True, contexts: int = 1, **knobs):
+                 tables_path: str | None = None, skip_unused_passes: bool = True, contexts: int = 1,
+                 max_transcript: int = QV_MAX_TRANSCRIPT, **knobs):
         import torch
 
         if not torch.cuda.is_available():
@@ -191,6 +196,7 @@ class Engine:
         cfg.max_samples = max_samples
         cfg.skip_unused_passes = int(skip_unused_passes)
         cfg.n_contexts = int(contexts)
+        cfg.max_transcript = int(max_transcript)   # matching window: 1024, or 2048 for the wide kernel set
         self.contexts = int(contexts)
         kn = env_knobs()
         kn.update(knobs)
@@ -208,6 +214,7 @@ class Engine:
         self.h = h
         # the engine may run fewer batches in flight than asked for (qv_probe_concurrent_streams, include/qverse.h)
         self.contexts = int(self.lib.qv_context_count(h))
+        self.max_transcript = int(self.lib.qv_max_transcript(h))
         self.max_batch = max_batch
         self.tables = Tables(self.tables_path)
 
@@ -531,7 +538,7 @@ class Engine:
         if n == 0:
             return []
         last_refs = last_refs or [None] * n
-        texts = [front_window(t) for t in texts]   # > 1,024 characters: matched on the front window
+        texts = [front_window(t, self.max_transcript) for t in texts]   # beyond the engine's window: matched on the front window
         enc = [self.tables.encode(t) for t in texts]
         off = np.zeros(n + 1, np.int32)
         off[1:] = np.cumsum([len(e) for e in enc])
@@ -581,7 +588,7 @@ class Engine:
         text = normalize_arabic(text)
         if not text.strip():
             return None
-        codes = np.ascontiguousarray(self.tables.encode(front_window(text)))
+        codes = np.ascontiguousarray(self.tables.encode(front_window(text, self.max_transcript)))
         bon = self.continuation_bonuses(hint)
         bv = np.ascontiguousarray(np.array([b[0] for b in bon] + [0] * (3 - len(bon)), np.int32))
         bb = np.ascontiguousarray(np.array([b[1] for b in bon] + [0.0] * (3 - len(bon)), np.float64))

@@ -28,6 +28,8 @@ _PROFILE = os.getenv("C2C_DIRECT_MIXED_PROFILE", "") not in ("", "0", "false", "
 CONFIDENCE_SKIP_THRESHOLD = 0.5  # c2c-direct-mixed-tta/run.py:57
 MAX_SAMPLES = int(os.getenv("QVERSE_MAX_SAMPLES", str(16000 * 60)))
 MAX_BATCH = int(os.getenv("QVERSE_MAX_BATCH", "16"))
+# matching window in normalised characters: 1024 (default) or 2048 (the wide kernel set; include/qverse.h qv_config.max_transcript)
+MAX_TRANSCRIPT = int(os.getenv("QVERSE_MAX_TRANSCRIPT", "1024"))
 
 # QVERSE_PRECISION: "fp16" (default), "mixed" (the engine's own W4A16 / W8A16 kernels) or "ort" -- the arithmetic
 # onnxruntime runs on the reference's fastconformer_full_mixed.onnx (include/qverse.h QV_PREC_ORT_MIXED); with a weight
@@ -60,9 +62,11 @@ def _ensure_engine():
     prec_name = os.getenv("QVERSE_PRECISION", "fp16")
     if prec_name not in _PRECISIONS:
         raise ValueError(f"QVERSE_PRECISION={prec_name!r}: expected one of {sorted(_PRECISIONS)}")
+    if MAX_TRANSCRIPT not in (1024, 2048):
+        raise ValueError(f"QVERSE_MAX_TRANSCRIPT={MAX_TRANSCRIPT}: expected 1024 or 2048")
     print(f"[c2c-direct-mixed/qverse] loading {'synthetic weights' if wp is None else wp.name} on cuda:{device} ({prec_name})...")
     _engine = Engine(device=device, with_model=True, weights_path=str(wp) if wp else None, precision=_PRECISIONS[prec_name],
-                     max_batch=MAX_BATCH, max_samples=MAX_SAMPLES)
+                     max_batch=MAX_BATCH, max_samples=MAX_SAMPLES, max_transcript=MAX_TRANSCRIPT)
     if _PROFILE:
         _engine.profile_stages(True)
     return _engine
