@@ -268,6 +268,40 @@ int qv_match_verse(qv_engine *e, const uint8_t *codes_host, int32_t n_codes, int
                    const int32_t *bonus_verse, const double *bonus_value, int32_t max_span,
                    int32_t *start, int32_t *span, double *score, void *stream);
 
+/* ---- word timings: CTC forced alignment ----------------------------------------------------
+ * Which frames did every token of a target occupy?  A Viterbi pass (max in place of the CTC loss's log-sum-exp) over
+ * the blank-extended target, float32 in natural-log units: v[0][0] = lp[0][blank], v[0][1] = lp[0][tgt[0]], every other
+ * state -1e30;  v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if s is odd, s > 1 and tgt[s/2] != tgt[s/2-1])
+ * + lp[t][ext[s]].  Ties go to the smaller step (stay, then s-1, then s-2).  The path ends in state S-1 = 2L if
+ * v[T-1][S-1] >= v[T-1][S-2], else in S-2.  The only float operation per state and frame is that one add, so `score`
+ * (the value of the final state) is reproducible bit for bit.  Per token i: first[i] / last[i] = first and last frame
+ * (inclusive) spent in state 2i+1, logp[i] = the float32 sum of lp[t][tgt[i]] over those frames divided by their count.
+ * A frame is 1,280 samples (0.08 s).  Rows with a flag set hold -1 in first / last / ids, 0 in logp and score; so do the
+ * entries past a row's n_tokens.  Output rows are `pitch` entries apart, pitch >= QV_ALIGN_MAX_TOKENS (else QV_ERR_ARG).
+ * The back-pointer workspace (max_batch * t_cap * 256 bytes per context) is allocated by the first alignment call that
+ * uses the context.  Both calls are SYNCHRONOUS. */
+#define QV_ALIGN_MAX_TOKENS 383          /* 2L+1 <= 767 states, the CTC rerank's own bound */
+enum { QV_ALIGN_NO_TARGET = 1,           /* L == 0 / the row has no prediction (surah 0) */
+       QV_ALIGN_TOO_LONG = 2,            /* L > QV_ALIGN_MAX_TOKENS or 2L+1 above the engine's state capacity (384 states for an
+                                            engine of at most 384 frames, 30 s; 768 above) */
+       QV_ALIGN_INFEASIBLE = 4 };        /* T < L + number of adjacent equal tokens: no path */
+typedef struct { int32_t n_tokens, flags, t_frames, start_verse, span, reserved; float score, reserved_f; } qv_align_info;
+
+/* explicit targets (any ids 0..1023), like qv_debug_ctc_loss but batched: row b aligns targets[off[b]..] (off = running sum
+ * of lens_host) to log-prob row b of logprobs_dev f32[batch, t_max, 1025], t_host[b] valid frames.  start_verse = -1,
+ * span = 0.  t_max above the engine's frame capacity or batch above max_batch: QV_ERR_CAPACITY. */
+int qv_align(qv_engine *e, const float *logprobs_dev, const int32_t *t_host, int32_t batch, int32_t t_max,
+             const uint16_t *targets_host, const int32_t *lens_host,
+             qv_align_info *info_host, int16_t *first_host, int16_t *last_host, float *logp_host, int32_t pitch, void *stream);
+/* the winners of context ctx's last batch against the log-probs that batch was decoded from: each row's (start verse, span)
+ * is read from the device-side result (QV_SOURCE_TEXT and QV_SOURCE_CTC winners alike), its token list is the table's --
+ * what the CTC rerank scores; ids_host receives it.  After qv_predict_batch[_async[_ctx]] the log-probs are the context's
+ * own workspace; after qv_decode_retrieve_rerank[_async] they are the CALLER's tensor, which must still be alive and
+ * unchanged.  Like qv_fetch_results_ctx it must be called before the context is reused (the next batch on it, or
+ * qv_match_verse / qv_debug_retrieve, which run on the current context's workspace); it waits for the batch itself. */
+int qv_align_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, qv_align_info *info_host, uint16_t *ids_host,
+                         int16_t *first_host, int16_t *last_host, float *logp_host, int32_t pitch);
+
 /* Device pointer of the packed (surah, ayah, ayah_end, float-bits(score)) i32[B,4] rows of the
  * last async call -- the payload of the per-batch RCCL all-gather. */
 const int32_t *qv_packed_results_dev(qv_engine *e);

@@ -634,6 +634,8 @@ extern "C" void qv_destroy(qv_engine *e) {
     for (void *p : e->allocs) (void)hipFree(p);
     for (QvCtx &c : e->ctx) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
+        if (c.align.out_host) (void)hipHostFree(c.align.out_host);
+        if (c.align.in_host) (void)hipHostFree(c.align.in_host);
         if (c.stream) (void)hipStreamDestroy(c.stream);
         if (c.in_ready) (void)hipEventDestroy(c.in_ready);
         if (c.done) (void)hipEventDestroy(c.done);
@@ -654,6 +656,12 @@ extern "C" int qv_forward(qv_engine *eng, const float *audio_dev, const int64_t 
                             (hipStream_t)stream, /*zero_pad_rows=*/true);
 }
 
+// what qv_align_results_ctx aligns against: the log-probs the current context's batch was just decoded from
+static void align_note(qv_engine *eng, const float *lp, int t_max, int batch, hipStream_t stream) {
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    c.al_lp = lp; c.al_tmax = t_max; c.al_batch = batch; c.al_stream = stream;
+}
+
 extern "C" int qv_decode_retrieve_rerank_async(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch,
                                                int32_t t_max, void *stream) {
     QV_SERIALISE(eng);
@@ -661,7 +669,9 @@ extern "C" int qv_decode_retrieve_rerank_async(qv_engine *eng, const float *lp, 
     if (!eng || !lp || !t_host || batch < 1) return QV_ERR_ARG;
     qv_stage_mark(eng, 0, (hipStream_t)stream);   // no forward in this call: forward = 0
     qv_stage_mark(eng, 1, (hipStream_t)stream);
-    return QV_POST(eng, qv_post_run)(eng, lp, t_max, t_host, batch, (hipStream_t)stream);
+    int rc = QV_POST(eng, qv_post_run)(eng, lp, t_max, t_host, batch, (hipStream_t)stream);
+    if (rc == QV_OK) align_note(eng, lp, t_max, batch, (hipStream_t)stream);
+    return rc;
 }
 
 void qv_stage_mark(qv_engine *eng, int i, hipStream_t s) {
@@ -769,8 +779,11 @@ extern "C" int qv_predict_batch_async(qv_engine *eng, const float *audio_dev, co
     if (eng->inject_lp) {
         if (batch > eng->inject_batch) { qv_set_error(eng, "injected log-probs hold fewer utterances than the batch"); return QV_ERR_ARG; }
         rc = QV_POST(eng, qv_post_run)(eng, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
-    } else
-    rc = QV_POST(eng, qv_post_run)(eng, eng->logprobs_ws, t_max, t_out.data(), batch, run);
+        if (rc == QV_OK) align_note(eng, eng->inject_lp, eng->inject_tmax, batch, run);
+    } else {
+        rc = QV_POST(eng, qv_post_run)(eng, eng->logprobs_ws, t_max, t_out.data(), batch, run);
+        if (rc == QV_OK) align_note(eng, eng->logprobs_ws, t_max, batch, run);
+    }
     if (rc) return rc;
     if (eng->n_ctx > 1) {
         QvCtx &c = eng->ctx[eng->cur_ctx];
@@ -931,6 +944,7 @@ extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int3
     QV_ORDERED(eng, stream_);
     hipStream_t stream = (hipStream_t)stream_;
     if (!eng) return QV_ERR_ARG;
+    eng->ctx[eng->cur_ctx].al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
     int rc = QV_POST(eng, qv_post_debug_retrieve)(eng, codes_host, n_codes, stream);
     if (rc) return rc;
     QvUtt u;
@@ -997,6 +1011,7 @@ extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t
         if (bonus_verse[i] < 0 || bonus_verse[i] >= eng->tab.n_verses) { qv_set_error(eng, "qv_match_verse: bonus verse out of range"); return QV_ERR_ARG; }
     if (n_codes > eng->max_q) { qv_set_error(eng, "qv_match_verse: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     QV_TRY(quiesce_contexts(eng));
+    eng->ctx[eng->cur_ctx].al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
     int rc = QV_POST(eng, qv_post_match_verse)(eng, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
     if (rc) return rc;
     QvUtt u;
@@ -1011,6 +1026,38 @@ extern "C" int qv_debug_ctc_loss(qv_engine *eng, const float *lp, int32_t T, con
     QV_ORDERED(eng, stream);
     if (!eng || n < 1) return QV_ERR_ARG;
     return qv_post_debug_ctc(eng, lp, T, tg, lens, n, loss_host, (hipStream_t)stream);
+}
+
+// ---- forced alignment (qv_align.hip) --------------------------------------------------------------------------------
+extern "C" int qv_align(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch, int32_t t_max,
+                        const uint16_t *targets_host, const int32_t *lens_host, qv_align_info *info_host, int16_t *first_host,
+                        int16_t *last_host, float *logp_host, int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    QV_ORDERED(eng, stream);
+    if (!eng) return QV_ERR_ARG;
+    if (!lp || !t_host || !lens_host || !info_host || !first_host || !last_host || !logp_host || batch < 1 || t_max < 1 ||
+        pitch < QV_ALIGN_MAX_TOKENS) {
+        qv_set_error(eng, "qv_align: null argument, empty batch or pitch < QV_ALIGN_MAX_TOKENS");
+        return QV_ERR_ARG;
+    }
+    int64_t total = 0;
+    for (int b = 0; b < batch; ++b) total += lens_host[b] > 0 ? lens_host[b] : 0;
+    if (total > 0 && !targets_host) { qv_set_error(eng, "qv_align: targets_host is null"); return QV_ERR_ARG; }
+    return qv_align_explicit(eng, lp, t_host, batch, t_max, targets_host, lens_host, info_host, first_host, last_host, logp_host,
+                             pitch, (hipStream_t)stream);
+}
+
+extern "C" int qv_align_results_ctx(qv_engine *eng, int32_t k, int32_t batch, qv_align_info *info_host, uint16_t *ids_host,
+                                    int16_t *first_host, int16_t *last_host, float *logp_host, int32_t pitch) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (k < 0 || k >= eng->n_ctx || batch < 1 || !info_host || !ids_host || !first_host || !last_host || !logp_host ||
+        pitch < QV_ALIGN_MAX_TOKENS) {
+        qv_set_error(eng, "qv_align_results_ctx: bad context, null argument, empty batch or pitch < QV_ALIGN_MAX_TOKENS");
+        return QV_ERR_ARG;
+    }
+    if (batch > eng->ctx[k].work.max_batch) { qv_set_error(eng, "qv_align_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    return qv_align_results(eng, k, batch, info_host, ids_host, first_host, last_host, logp_host, pitch);
 }
 
 extern "C" int qv_debug_forward_tap(qv_engine *eng, int32_t what, int32_t layer, float *out_dev, void *stream) {

@@ -186,6 +186,29 @@ struct QvTrack {
     qv_track_match *out; // [CAP]
 };
 
+// forced alignment (qv_align.hip).  One row of the launch plan: which token list (offset into the token buffer the kernel
+// is given: the table's, or the staged explicit targets), how many tokens, how many frames.
+#define QV_ALIGN_PITCH 384   // entries per row of the device-side outputs (>= QV_ALIGN_MAX_TOKENS)
+struct QvAlignRow { int32_t tok_off, L, T, flags, start, span; };
+// per-context alignment workspace, allocated by the first alignment call on that context (bp == nullptr: not yet).
+// Outputs are one record per row -- qv_align_info, then logp / first / last / ids with QV_ALIGN_PITCH entries each -- so a
+// batch comes back in ONE copy into a pinned buffer, from where the host scatters it into the caller's arrays; plan and
+// explicit targets travel the same way in the other direction.
+#define QV_ALIGN_ROW_BYTES (sizeof(qv_align_info) + QV_ALIGN_PITCH * (sizeof(float) + 3 * sizeof(int16_t)))
+struct QvAlignWs {
+    uint32_t *bp;            // [B][t_cap][64] back-pointers: two bits per state, a lane's NS states in one word
+    unsigned char *out;      // [B][QV_ALIGN_ROW_BYTES]
+    QvAlignRow *plan;        // [B], followed in the same allocation by
+    uint16_t *targets;       // [B * QV_ALIGN_PITCH] explicit targets of qv_align, back to back
+    unsigned char *out_host; // pinned mirror of out
+    unsigned char *in_host;  // pinned mirror of plan + targets
+};
+int qv_align_explicit(qv_engine *eng, const float *lp, const int32_t *t_host, int batch, int t_max, const uint16_t *targets_host,
+                      const int32_t *lens_host, qv_align_info *info_host, int16_t *first_host, int16_t *last_host,
+                      float *logp_host, int pitch, hipStream_t stream);
+int qv_align_results(qv_engine *eng, int k, int batch, qv_align_info *info_host, uint16_t *ids_host, int16_t *first_host,
+                     int16_t *last_host, float *logp_host, int pitch);
+
 // post-logits launcher (qv_postlogits.hip)
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,
@@ -256,6 +279,13 @@ struct QvCtx {
     struct PostGraph { const float *lp; int batch, t_max, variants; hipGraphExec_t exec; } post_graph[4];   // variants: the kernel variants in force (spans, CTC) and the engine's window
     bool post_graph_off = false;   // a capture / instantiate failed on this context: plain launches from then on
     int n_post_graph;
+    // forced alignment (qv_align_results_ctx): what the context's last batch was decoded from -- log-prob tensor (the
+    // context's workspace or the caller's), its row pitch in frames, batch size, the stream the chain ran on -- and the
+    // lazily allocated workspace.  al_lp == nullptr: nothing to align (no batch yet, or the workspace was reused).
+    const float *al_lp = nullptr;
+    int al_tmax = 0, al_batch = 0;
+    hipStream_t al_stream = nullptr;
+    QvAlignWs align = {};
 };
 
 struct qv_engine {

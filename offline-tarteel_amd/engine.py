@@ -67,6 +67,18 @@ class QvTrackMatch(C.Structure):
                 ("n_words", C.c_int32), ("reserved", C.c_int32), ("score", C.c_double)]
 
 
+class QvAlignInfo(C.Structure):
+    """include/qverse.h: qv_align_info"""
+    _fields_ = [("n_tokens", C.c_int32), ("flags", C.c_int32), ("t_frames", C.c_int32), ("start_verse", C.c_int32),
+                ("span", C.c_int32), ("reserved", C.c_int32), ("score", C.c_float), ("reserved_f", C.c_float)]
+
+
+ALIGN_MAX_TOKENS = 383   # include/qverse.h: QV_ALIGN_MAX_TOKENS
+ALIGN_NO_TARGET, ALIGN_TOO_LONG, ALIGN_INFEASIBLE = 1, 2, 4
+ALIGN_INFO_DTYPE = np.dtype([("n_tokens", "<i4"), ("flags", "<i4"), ("t_frames", "<i4"), ("start_verse", "<i4"),
+                             ("span", "<i4"), ("reserved", "<i4"), ("score", "<f4"), ("reserved_f", "<f4")])
+assert ALIGN_INFO_DTYPE.itemsize == C.sizeof(QvAlignInfo)
+
 RESULT_DTYPE = np.dtype([
     ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("source", "<i4"),
     ("score", "<f8"), ("base_score", "<f8"), ("ctc_norm_loss", "<f4"),
@@ -120,6 +132,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_packed_results_ctx.argtypes = [vp, i32, vp]
     lib.qv_packed_results_ctx.restype = vp
     lib.qv_fetch_results_ctx.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.qv_align.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_align_results_ctx.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32]
     lib.qv_tracker_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -282,7 +296,9 @@ class Engine:
         self._check(rc, "qv_forward")
         return lp, t_out.tolist()
 
-    def decode_retrieve_rerank(self, log_probs, t_frames, want_text: bool = True) -> list[dict]:
+    def decode_retrieve_rerank(self, log_probs, t_frames, want_text: bool = True, align: bool = False) -> list[dict]:
+        """align=True: every result dict gains an "alignment" entry (align_results) -- the winner's token ids and the
+        frames each of them occupies in `log_probs`."""
         torch = self.torch
         assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous()
         B, t_max, V = log_probs.shape
@@ -295,9 +311,9 @@ class Engine:
             res.ctypes.data_as(C.c_void_p),
             greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
         self._check(rc, "qv_decode_retrieve_rerank")
-        return self._results(res, greedy)
+        return self._with_alignment(self._results(res, greedy), align)
 
-    def predict_batch(self, audio, lengths, want_text: bool = True) -> list[dict]:
+    def predict_batch(self, audio, lengths, want_text: bool = True, align: bool = False) -> list[dict]:
         torch = self.torch
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
         B, N = audio.shape
@@ -310,7 +326,71 @@ class Engine:
             res.ctypes.data_as(C.c_void_p),
             greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
         self._check(rc, "qv_predict_batch")
-        return self._results(res, greedy)
+        return self._with_alignment(self._results(res, greedy), align)
+
+    # ---------------------------------------------------------------- word timings
+    def _with_alignment(self, results: list[dict], align: bool) -> list[dict]:
+        if align:
+            for d, a in zip(results, self.align_results(batch=len(results))):
+                d["alignment"] = a
+        return results
+
+    @staticmethod
+    def _alignments(info, ids, first, last, logp) -> list[dict]:
+        out = []
+        for b in range(len(info)):
+            flags = int(info[b]["flags"])
+            n = 0 if flags else int(info[b]["n_tokens"])
+            out.append({"ids": ids[b, :n].astype(np.int32), "first": first[b, :n].astype(np.int32),
+                        "last": last[b, :n].astype(np.int32), "logp": logp[b, :n].copy(), "score": float(info[b]["score"]),
+                        "flags": flags, "n_tokens": int(info[b]["n_tokens"]), "t_frames": int(info[b]["t_frames"]),
+                        "start": int(info[b]["start_verse"]), "span": int(info[b]["span"])})
+        return out
+
+    def align(self, log_probs, t_frames, targets) -> list[dict]:
+        """CTC forced alignment (qv_align) of explicit token lists: targets[b] (ids 0..1023) against row b of the float32
+        cuda tensor log_probs [B, t_max, 1025] with t_frames[b] valid frames.  Per row a dict: "ids", "first", "last"
+        (first / last encoder frame of every token, inclusive; a frame is 0.08 s), "logp" (mean log-prob of the token over
+        its frames), "score" (log-prob of the whole path), "flags" (ALIGN_NO_TARGET / ALIGN_TOO_LONG / ALIGN_INFEASIBLE:
+        the arrays are then empty and score is 0), "n_tokens", "t_frames"."""
+        torch = self.torch
+        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        B, t_max, V = log_probs.shape
+        assert V == 1025 and len(targets) == B and len(t_frames) == B
+        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        lens = np.ascontiguousarray(np.array([len(x) for x in targets], np.int32))
+        tg = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint16).reshape(-1) for x in targets] + [np.zeros(1, np.uint16)]))
+        pitch = ALIGN_MAX_TOKENS
+        info = np.zeros(B, dtype=ALIGN_INFO_DTYPE)
+        first, last = np.zeros((B, pitch), np.int16), np.zeros((B, pitch), np.int16)
+        logp = np.zeros((B, pitch), np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_align(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, p(tg), p(lens), p(info), p(first), p(last),
+                               p(logp), pitch, self._stream())
+        self._check(rc, "qv_align")
+        ids = np.full((B, pitch), -1, np.int32)
+        for b, x in enumerate(targets):
+            if not info[b]["flags"]:
+                ids[b, : len(x)] = np.asarray(x, np.int32)
+        return self._alignments(info, ids, first, last, logp)
+
+    def align_results(self, ctx: int | None = None, batch: int = 1) -> list[dict]:
+        """Forced alignment of the winners of context `ctx`'s last batch (default: the most recent call's) against the
+        log-probs that batch was decoded from (qv_align_results_ctx): dicts as align() returns, plus "start" / "span" --
+        the winner's first verse (global index) and number of ayat; "ids" are the table's token ids of that text
+        (tables.token_ids(start, span)).  Rows without a prediction carry ALIGN_NO_TARGET.  Call it before the context is
+        reused; after decode_retrieve_rerank the caller's log-prob tensor must still be alive."""
+        if ctx is None:
+            ctx = int(self.lib.qv_last_context(self.h))
+        pitch = ALIGN_MAX_TOKENS
+        info = np.zeros(batch, dtype=ALIGN_INFO_DTYPE)
+        ids = np.zeros((batch, pitch), np.uint16)
+        first, last = np.zeros((batch, pitch), np.int16), np.zeros((batch, pitch), np.int16)
+        logp = np.zeros((batch, pitch), np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_align_results_ctx(self.h, int(ctx), int(batch), p(info), p(ids), p(first), p(last), p(logp), pitch)
+        self._check(rc, "qv_align_results_ctx")
+        return self._alignments(info, ids, first, last, logp)
 
     def predict_batch_async(self, audio, lengths):
         B, N = audio.shape

@@ -35,6 +35,9 @@ MAX_TRANSCRIPT = int(os.getenv("QVERSE_MAX_TRANSCRIPT", "1024"))
 # onnxruntime runs on the reference's fastconformer_full_mixed.onnx (include/qverse.h QV_PREC_ORT_MIXED); with a weight
 # file converted from that ONNX (marked pre-quantised) "ort" computes on the file's own integers
 _PRECISIONS = {"fp16": 0, "mixed": 1, "ort": 2}
+# QVERSE_WORDS=1: predict() adds "words" -- per-word timings of the recognised verse from the device's forced alignment
+# (Engine.align_results + words.words_from_alignment); [] when there is no prediction or the alignment carries a flag
+_WORDS = os.getenv("QVERSE_WORDS", "") not in ("", "0", "false", "False")
 _engine = None
 _last_raw: list[dict] = []   # engine-level dicts of the most recent predict_arrays() call (profile line)
 
@@ -87,8 +90,26 @@ def _to_dict(r: dict, round_score: bool) -> dict:
     }
 
 
-def predict_arrays(arrays, round_score: bool = True) -> list[dict]:
-    """audio arrays (float32, 16 kHz) -> predict()-shaped dicts, one engine call per <= MAX_BATCH."""
+def _words_of(eng, r: dict) -> list[dict]:
+    from .words import words_from_alignment
+
+    a = r.get("alignment")
+    if not r["surah"] or not a or a["flags"]:
+        return []
+    return words_from_alignment(eng.tables, a["start"], a["span"], a)
+
+
+def _finish(eng, raw: list[dict], round_score: bool, words: bool) -> list[dict]:
+    out = [_to_dict(r, round_score) for r in raw]
+    if words:
+        for d, r in zip(out, raw):
+            d["words"] = _words_of(eng, r)
+    return out
+
+
+def predict_arrays(arrays, round_score: bool = True, words: bool = False) -> list[dict]:
+    """audio arrays (float32, 16 kHz) -> predict()-shaped dicts, one engine call per <= MAX_BATCH.
+    words=True: every dict gains "words" (see predict_words)."""
     import torch
 
     eng = _ensure_engine()
@@ -100,40 +121,49 @@ def predict_arrays(arrays, round_score: bool = True) -> list[dict]:
         for i, a in enumerate(chunk):
             buf[i, : len(a)] = a
         dev = torch.from_numpy(buf).cuda(eng.device)
-        raw = eng.predict_batch(dev, lens)
+        raw = eng.predict_batch(dev, lens, align=words)
         _last_raw[:] = raw
-        out.extend(_to_dict(r, round_score) for r in raw)
+        out.extend(_finish(eng, raw, round_score, words))
     return out
 
 
-def predict_device(dev, lens, round_score: bool = True) -> list[dict]:
+def predict_device(dev, lens, round_score: bool = True, words: bool = False) -> list[dict]:
     """a zero-padded float32 cuda matrix of 16 kHz clips -> predict()-shaped dicts, one engine call per <= MAX_BATCH rows"""
     eng = _ensure_engine()
     out = []
     for s in range(0, len(lens), eng.max_batch):
         chunk = lens[s: s + eng.max_batch]
-        raw = eng.predict_batch(dev[s: s + len(chunk), : max(chunk)].contiguous(), chunk)
+        raw = eng.predict_batch(dev[s: s + len(chunk), : max(chunk)].contiguous(), chunk, align=words)
         _last_raw[:] = raw
-        out.extend(_to_dict(r, round_score) for r in raw)
+        out.extend(_finish(eng, raw, round_score, words))
     return out
 
 
-def predict_batch(audio_paths) -> list[dict]:
+def predict_batch(audio_paths, words: bool = False) -> list[dict]:
     """files -> dicts.  The ingest (mix-down, resampling to 16 kHz) runs on the GPU (audio.load_audio_device: the same float32
-    arithmetic as the host load_audio, bit for bit); QVERSE_INGEST=host keeps it on the host."""
+    arithmetic as the host load_audio, bit for bit); QVERSE_INGEST=host keeps it on the host.
+    words=True: every dict gains "words" (see predict_words); without it the dicts are unchanged."""
     if os.getenv("QVERSE_INGEST", "device") == "host":
-        return predict_arrays([load_audio(p) for p in audio_paths])
+        return predict_arrays([load_audio(p) for p in audio_paths], words=words)
     from .audio import load_audio_device
 
     dev, lens = load_audio_device(list(audio_paths), _ensure_engine())
-    return predict_device(dev, lens)
+    return predict_device(dev, lens, words=words)
+
+
+def predict_words(audio_path: str) -> dict:
+    """predict() plus "words": for every word of the recognised verse or span {"ayah", "word" (1-based within the ayah),
+    "text", "start", "end" (seconds), "logp"} from the forced alignment of the verse's tokens to the encoder frames
+    (0.08 s per frame); [] when nothing was recognised or no alignment exists (text longer than 383 tokens, fewer
+    frames than tokens)."""
+    return predict_arrays([load_audio(audio_path)], words=True)[0]
 
 
 def predict(audio_path: str) -> dict:
     t0 = time.perf_counter()
     audio = load_audio(audio_path)
     t1 = time.perf_counter()
-    res = predict_arrays([audio])[0]
+    res = predict_arrays([audio], words=_WORDS)[0]
     if _PROFILE:
         # the reference's line (mixed/run.py:76-81,117-124): forward= decode= build= rerank= total=
         # candidates= use_ctc= source= -- stage times from HIP events around the device stages of this
