@@ -267,11 +267,11 @@ __global__ void k_align_plan(QvTables tab, QvWork wk, int batch, int t_max, QvAl
 // The alignment workspace of one context, allocated on the first alignment call that uses it: an engine that never
 // aligns pays nothing.  Device bytes: max_batch * (t_cap * 256 for the back-pointers + 3,872 for the output records +
 // 792 for plan and targets); the two pinned mirrors add max_batch * 4,664 bytes of host memory.
-static int align_ws(qv_engine *eng, int k, QvAlignWs **out) {
-    QvAlignWs &w = eng->ctx[k].align;
+static int align_ws(qv_engine *eng, QvCtx &c, QvAlignWs **out) {
+    QvAlignWs &w = c.align;
     *out = &w;
     if (w.bp) return QV_OK;
-    const size_t B = (size_t)eng->ctx[k].work.max_batch, tc = (size_t)eng->ctx[k].work.t_cap;
+    const size_t B = (size_t)c.work.max_batch, tc = (size_t)c.work.t_cap;
     const size_t n_out = B * QV_ALIGN_ROW_BYTES, n_in = B * (sizeof(QvAlignRow) + QV_ALIGN_PITCH * sizeof(uint16_t));
     void *bp = nullptr, *o = nullptr, *in = nullptr, *oh = nullptr, *ih = nullptr;
     if (hipMalloc(&bp, B * tc * 64 * sizeof(uint32_t)) != hipSuccess || hipMalloc(&o, n_out) != hipSuccess ||
@@ -325,10 +325,10 @@ static int align_run(qv_engine *eng, QvAlignWs &w, int t_cap, const float *lp, i
     return QV_OK;
 }
 
-int qv_align_explicit(qv_engine *eng, const float *lp, const int32_t *t_host, int batch, int t_max, const uint16_t *targets_host,
+int qv_align_explicit(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max, const uint16_t *targets_host,
                       const int32_t *lens_host, qv_align_info *info_host, int16_t *first_host, int16_t *last_host,
                       float *logp_host, int pitch, hipStream_t stream) {
-    const QvWork &wk = eng->ctx[eng->cur_ctx].work;
+    const QvWork &wk = c.work;
     if (batch > wk.max_batch || t_max > wk.t_cap) {
         qv_set_error(eng, "qv_align: batch or frame count exceeds engine capacity");
         return QV_ERR_CAPACITY;
@@ -336,7 +336,7 @@ int qv_align_explicit(qv_engine *eng, const float *lp, const int32_t *t_host, in
     for (int b = 0; b < batch; ++b)
         if (lens_host[b] < 0 || t_host[b] < 0 || t_host[b] > t_max) { qv_set_error(eng, "qv_align: lens_host[b] / t_host[b] out of range"); return QV_ERR_ARG; }
     QvAlignWs *w = nullptr;
-    int rc = align_ws(eng, eng->cur_ctx, &w);
+    int rc = align_ws(eng, c, &w);
     if (rc) return rc;
     // plan and targets are laid out in the pinned mirror as on the device and go up in one copy (the previous call has
     // finished with the mirror: alignment calls are synchronous and serialised by the engine's lock)
@@ -368,7 +368,7 @@ int qv_align_results(qv_engine *eng, int k, int batch, qv_align_info *info_host,
         return QV_ERR_ARG;
     }
     QvAlignWs *w = nullptr;
-    int rc = align_ws(eng, k, &w);
+    int rc = align_ws(eng, c, &w);
     if (rc) return rc;
     // ordered behind the batch: on the context's own stream when the batch ran there, else after a device-wide join (the
     // batch ran on a caller stream we were not given -- as qv_fetch_results_ctx)

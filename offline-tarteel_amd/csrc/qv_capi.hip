@@ -413,25 +413,10 @@ static int load_tables(qv_engine *eng, const char *path) {
     return QV_OK;
 }
 
-// make context k the current one: the flat engine fields (and the model's activation pointers)
-// are what every launcher reads
-static void qv_select_ctx(qv_engine *eng, int k) {
-    QvCtx &old = eng->ctx[eng->cur_ctx];
-    old.last_batch = eng->last_batch;
-    old.last_tmax = eng->last_tmax;
-    QvCtx &c = eng->ctx[k];
-    eng->work = c.work;
-    eng->logprobs_ws = c.logprobs_ws;
-    eng->t_host_scratch = c.t_host_scratch;
-    eng->t_dev = c.t_dev;
-    eng->last_batch = c.last_batch;
-    eng->last_tmax = c.last_tmax;
-    eng->cur_ctx = k;
-    if (eng->model) qv_model_select_ctx(eng->model, k);
-}
-
+// workspace, staging buffers, stream and events of execution context k
 static int alloc_work(qv_engine *eng, int k) {
-    QvWork &w = eng->work;
+    QvCtx &c = eng->ctx[k];
+    QvWork &w = c.work;
     int B = eng->cfg.max_batch, N = eng->tab.n_verses;
     w.max_batch = B;
     w.t_cap = qv_frames_for_samples(eng->cfg.max_samples) + 2;
@@ -470,23 +455,10 @@ static int alloc_work(qv_engine *eng, int k) {
     QV_TRY(dalloc(eng, Bz * 4, &w.packed));
     QV_TRY(dalloc(eng, Bz, &w.fail_list));
     QV_TRY(dalloc(eng, (size_t)1, &w.n_fail));
-    QV_TRY(dalloc(eng, Bz, &eng->t_dev));
-    QV_HIP(hipHostMalloc((void **)&eng->t_host_scratch, sizeof(int32_t) * Bz * QV_STAGE_SLOTS, hipHostMallocDefault));
-    eng->ctx[k].t_host_scratch = eng->t_host_scratch;  // owned by the context from here on
-    eng->logprobs_ws = nullptr;
-    if (eng->cfg.with_model) QV_TRY(dalloc(eng, Bz * w.t_cap * QV_VOCAB, &eng->logprobs_ws));
-    QvCtx &c = eng->ctx[k];
-    c.work = w;
-    c.logprobs_ws = eng->logprobs_ws;
-    c.t_host_scratch = eng->t_host_scratch;
-    c.t_dev = eng->t_dev;
-    c.busy = false;
-    c.last_batch = c.last_tmax = 0;
-    for (int i = 0; i < QV_STAGE_SLOTS; ++i) {
-        QV_HIP(hipEventCreateWithFlags(&c.t_copied[i], hipEventDisableTiming));
-        c.t_pending[i] = false;
-    }
-    c.t_slot = 0;
+    QV_TRY(dalloc(eng, Bz, &c.t_dev));
+    QV_HIP(hipHostMalloc((void **)&c.t_host_scratch, sizeof(int32_t) * Bz * QV_STAGE_SLOTS, hipHostMallocDefault));
+    if (eng->cfg.with_model) QV_TRY(dalloc(eng, Bz * w.t_cap * QV_VOCAB, &c.logprobs_ws));
+    for (int i = 0; i < QV_STAGE_SLOTS; ++i) QV_HIP(hipEventCreateWithFlags(&c.t_copied[i], hipEventDisableTiming));
     if (eng->n_ctx > 1) {
         // QVERSE_CU_PARTITION=1 (experiment, DESIGN.md "Batches in flight"): context k's stream only sees its share of
         // the CUs of EVERY XCD (mask bit c * 8 + x = CU c of XCD x, tools/cumask_probe.hip; an XCD with an empty mask
@@ -525,23 +497,11 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
     cfg = &eng->cfg;
     eng->max_q = cfg->max_transcript == 0 ? QV_MAX_TRANSCRIPT : cfg->max_transcript;
     eng->model = nullptr;
-    eng->t_host_scratch = nullptr;
-    eng->last_batch = eng->last_tmax = 0;
     eng->n_ctx = cfg->n_contexts < 1 ? 1 : cfg->n_contexts;
     eng->cur_ctx = eng->next_ctx = 0;
     eng->profile_stages = false;
     eng->inject_lp = nullptr;
     eng->inject_tmax = eng->inject_batch = 0;
-    for (QvCtx &c : eng->ctx) {
-        c = QvCtx();
-        c.t_host_scratch = nullptr;
-        c.stream = nullptr;
-        c.in_ready = c.done = nullptr;
-        for (hipEvent_t &e : c.t_copied) e = nullptr;
-        for (hipEvent_t &e : c.stage_ev) e = nullptr;
-        c.stage_valid = false;
-        c.n_post_graph = 0;
-    }
     auto fail = [&](int rc) {
         { std::lock_guard<std::mutex> lk(g_create_error_mu); g_create_error = eng->last_error; }
         qv_destroy(eng);
@@ -621,7 +581,6 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
         rc = qv_model_create(eng, &eng->cfg, &eng->model);
         if (rc) return fail(rc);
     }
-    qv_select_ctx(eng, 0);
     *out = eng;
     return QV_OK;
 }
@@ -652,13 +611,12 @@ extern "C" int qv_forward(qv_engine *eng, const float *audio_dev, const int64_t 
     QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
-    return qv_model_forward(eng, eng->model, audio_dev, lengths_host, batch, n_max, logprobs_dev, t_max, t_out_host,
-                            (hipStream_t)stream, /*zero_pad_rows=*/true);
+    return qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, logprobs_dev, t_max,
+                            t_out_host, (hipStream_t)stream, /*zero_pad_rows=*/true);
 }
 
-// what qv_align_results_ctx aligns against: the log-probs the current context's batch was just decoded from
-static void align_note(qv_engine *eng, const float *lp, int t_max, int batch, hipStream_t stream) {
-    QvCtx &c = eng->ctx[eng->cur_ctx];
+// what qv_align_results_ctx aligns against: the log-probs the context's batch was just decoded from
+static void align_note(QvCtx &c, const float *lp, int t_max, int batch, hipStream_t stream) {
     c.al_lp = lp; c.al_tmax = t_max; c.al_batch = batch; c.al_stream = stream;
 }
 
@@ -667,16 +625,16 @@ extern "C" int qv_decode_retrieve_rerank_async(qv_engine *eng, const float *lp, 
     QV_SERIALISE(eng);
     QV_ORDERED(eng, stream);
     if (!eng || !lp || !t_host || batch < 1) return QV_ERR_ARG;
-    qv_stage_mark(eng, 0, (hipStream_t)stream);   // no forward in this call: forward = 0
-    qv_stage_mark(eng, 1, (hipStream_t)stream);
-    int rc = QV_POST(eng, qv_post_run)(eng, lp, t_max, t_host, batch, (hipStream_t)stream);
-    if (rc == QV_OK) align_note(eng, lp, t_max, batch, (hipStream_t)stream);
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    qv_stage_mark(eng, c, 0, (hipStream_t)stream);   // no forward in this call: forward = 0
+    qv_stage_mark(eng, c, 1, (hipStream_t)stream);
+    int rc = QV_POST(eng, qv_post_run)(eng, c, lp, t_max, t_host, batch, (hipStream_t)stream);
+    if (rc == QV_OK) align_note(c, lp, t_max, batch, (hipStream_t)stream);
     return rc;
 }
 
-void qv_stage_mark(qv_engine *eng, int i, hipStream_t s) {
+void qv_stage_mark(qv_engine *eng, QvCtx &c, int i, hipStream_t s) {
     if (!eng->profile_stages) return;
-    QvCtx &c = eng->ctx[eng->cur_ctx];
     if (!c.stage_ev[i]) return;
     if (i == 0) c.stage_valid = false;
     if (hipEventRecord(c.stage_ev[i], s) == hipSuccess && i == 4) c.stage_valid = true;
@@ -686,7 +644,7 @@ extern "C" int qv_profile_inject_logprobs(qv_engine *eng, const float *logprobs_
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
     if (!logprobs_dev) { eng->inject_lp = nullptr; eng->inject_batch = 0; return QV_OK; }
-    if (!t_host || batch < 1 || t_max < 1 || t_max > eng->work.t_cap) { qv_set_error(eng, "qv_profile_inject_logprobs: bad shape"); return QV_ERR_ARG; }
+    if (!t_host || batch < 1 || t_max < 1 || t_max > eng->ctx[eng->cur_ctx].work.t_cap) { qv_set_error(eng, "qv_profile_inject_logprobs: bad shape"); return QV_ERR_ARG; }
     eng->inject_t.assign(t_host, t_host + batch);
     eng->inject_lp = logprobs_dev;
     eng->inject_tmax = t_max;
@@ -715,17 +673,14 @@ extern "C" int qv_stage_times(qv_engine *eng, int32_t k, float *ms4) {
     return QV_OK;
 }
 
-extern "C" int qv_fetch_results(qv_engine *eng, int32_t batch, int32_t t_max, qv_result *res, int32_t *greedy_host,
-                                void *stream_) {
-    QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream_);
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!eng || !res || batch < 1 || batch > eng->work.max_batch) return QV_ERR_ARG;
-    QV_HIP(hipMemcpyAsync(res, eng->work.results, sizeof(qv_result) * batch, hipMemcpyDeviceToHost, stream));
+// results (and greedy ids) of context c's last batch, copied on `stream`; SYNCHRONOUS
+static int fetch_results(qv_engine *eng, QvCtx &c, int batch, int t_max, qv_result *res, int32_t *greedy_host, hipStream_t stream) {
+    if (!res || batch < 1 || batch > c.work.max_batch) return QV_ERR_ARG;
+    QV_HIP(hipMemcpyAsync(res, c.work.results, sizeof(qv_result) * batch, hipMemcpyDeviceToHost, stream));
     if (greedy_host) {
-        int tc = eng->work.t_cap;
+        int tc = c.work.t_cap;
         int w = t_max < tc ? t_max : tc;
-        QV_HIP(hipMemcpy2DAsync(greedy_host, sizeof(int32_t) * t_max, eng->work.greedy, sizeof(int32_t) * tc,
+        QV_HIP(hipMemcpy2DAsync(greedy_host, sizeof(int32_t) * t_max, c.work.greedy, sizeof(int32_t) * tc,
                                 sizeof(int32_t) * w, batch, hipMemcpyDeviceToHost, stream));
     }
     QV_HIP(hipStreamSynchronize(stream));
@@ -736,6 +691,14 @@ extern "C" int qv_fetch_results(qv_engine *eng, int32_t batch, int32_t t_max, qv
         if (res[b].flags & QV_FLAG_TRANSCRIPT_TRUNCATED) { res[b].surah = res[b].ayah = res[b].ayah_end = 0; }
     }
     return QV_OK;
+}
+
+extern "C" int qv_fetch_results(qv_engine *eng, int32_t batch, int32_t t_max, qv_result *res, int32_t *greedy_host,
+                                void *stream) {
+    QV_SERIALISE(eng);
+    QV_ORDERED(eng, stream);
+    if (!eng) return QV_ERR_ARG;
+    return fetch_results(eng, eng->ctx[eng->cur_ctx], batch, t_max, res, greedy_host, (hipStream_t)stream);
 }
 
 extern "C" int qv_decode_retrieve_rerank(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch,
@@ -752,41 +715,42 @@ extern "C" int qv_predict_batch_async(qv_engine *eng, const float *audio_dev, co
     QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
-    if (batch > eng->work.max_batch) { qv_set_error(eng, "batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    // (every context has the same capacities)
+    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
     int64_t lmax = 0;
     for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
     int t_max = qv_frames_for_samples(lmax);
-    if (t_max > eng->work.t_cap) { qv_set_error(eng, "audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "audio longer than engine capacity"); return QV_ERR_CAPACITY; }
     std::vector<int32_t> t_out(batch);
     hipStream_t run = (hipStream_t)stream;
     if (eng->n_ctx > 1) {
         // rotate to the next context; the host blocks only if that context's previous batch is
         // still in flight (bounds the queue and protects its pinned staging buffers)
-        int k = eng->next_ctx;
+        const int k = eng->next_ctx;
         eng->next_ctx = (k + 1) % eng->n_ctx;
         QvCtx &c = eng->ctx[k];
         if (c.busy) QV_HIP(hipEventSynchronize(c.done));
-        qv_select_ctx(eng, k);
+        eng->cur_ctx = k;
         QV_HIP(hipEventRecord(c.in_ready, (hipStream_t)stream));
         QV_HIP(hipStreamWaitEvent(c.stream, c.in_ready, 0));
         run = c.stream;
     }
-    qv_stage_mark(eng, 0, run);
-    int rc = qv_model_forward(eng, eng->model, audio_dev, lengths_host, batch, n_max, eng->logprobs_ws, t_max,
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    qv_stage_mark(eng, c, 0, run);
+    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max,
                               t_out.data(), run, /*zero_pad_rows=*/false, /*may_graph=*/eng->n_ctx > 1);
     if (rc) return rc;
-    qv_stage_mark(eng, 1, run);
+    qv_stage_mark(eng, c, 1, run);
     if (eng->inject_lp) {
         if (batch > eng->inject_batch) { qv_set_error(eng, "injected log-probs hold fewer utterances than the batch"); return QV_ERR_ARG; }
-        rc = QV_POST(eng, qv_post_run)(eng, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
-        if (rc == QV_OK) align_note(eng, eng->inject_lp, eng->inject_tmax, batch, run);
+        rc = QV_POST(eng, qv_post_run)(eng, c, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
+        if (rc == QV_OK) align_note(c, eng->inject_lp, eng->inject_tmax, batch, run);
     } else {
-        rc = QV_POST(eng, qv_post_run)(eng, eng->logprobs_ws, t_max, t_out.data(), batch, run);
-        if (rc == QV_OK) align_note(eng, eng->logprobs_ws, t_max, batch, run);
+        rc = QV_POST(eng, qv_post_run)(eng, c, c.logprobs_ws, t_max, t_out.data(), batch, run);
+        if (rc == QV_OK) align_note(c, c.logprobs_ws, t_max, batch, run);
     }
     if (rc) return rc;
     if (eng->n_ctx > 1) {
-        QvCtx &c = eng->ctx[eng->cur_ctx];
         QV_HIP(hipEventRecord(c.done, c.stream));
         c.busy = true;
     }
@@ -806,8 +770,9 @@ extern "C" int qv_predict_batch(qv_engine *eng, const float *audio_dev, const in
     QV_SERIALISE(eng);
     int rc = qv_predict_batch_async(eng, audio_dev, lengths_host, batch, n_max, stream);
     if (rc) return rc;
-    if (eng->n_ctx > 1) return qv_fetch_results_ctx(eng, eng->cur_ctx, batch, eng->last_tmax, res, greedy_host);
-    return qv_fetch_results(eng, batch, eng->last_tmax, res, greedy_host, stream);
+    const int last_tmax = eng->ctx[eng->cur_ctx].last_tmax;
+    if (eng->n_ctx > 1) return qv_fetch_results_ctx(eng, eng->cur_ctx, batch, last_tmax, res, greedy_host);
+    return qv_fetch_results(eng, batch, last_tmax, res, greedy_host, stream);
 }
 
 static int fir_for(qv_engine *eng, const float *taps, int32_t n_taps, int32_t up, const qv_engine::Fir **out);
@@ -893,7 +858,7 @@ extern "C" int qv_mixdown_batch(qv_engine *eng, const float *x_dev, int64_t x_pi
     return QV_OK;
 }
 
-extern "C" const int32_t *qv_packed_results_dev(qv_engine *eng) { return eng ? eng->work.packed : nullptr; }
+extern "C" const int32_t *qv_packed_results_dev(qv_engine *eng) { return eng ? eng->ctx[eng->cur_ctx].work.packed : nullptr; }
 
 extern "C" int32_t qv_max_transcript(const qv_engine *eng) { return eng ? eng->max_q : 0; }   // fixed at qv_create
 extern "C" int32_t qv_context_count(const qv_engine *eng) { return eng ? eng->n_ctx : 0; }   // fixed at qv_create
@@ -927,13 +892,11 @@ extern "C" int qv_fetch_results_ctx(qv_engine *eng, int32_t k, int32_t batch, in
                                     int32_t *greedy_host) {
     QV_SERIALISE(eng);
     if (!eng || k < 0 || k >= eng->n_ctx) return QV_ERR_ARG;
-    int keep = eng->cur_ctx;
     if (eng->n_ctx == 1) QV_HIP(hipDeviceSynchronize());  // the batch ran on a caller stream we were not given
-    qv_select_ctx(eng, k);
     // on the context's own stream, so the copy is ordered after its batch
-    int rc = qv_fetch_results(eng, batch, t_max, res, greedy_host, eng->n_ctx > 1 ? eng->ctx[k].stream : nullptr);
-    qv_select_ctx(eng, keep);
-    return rc;
+    hipStream_t stream = eng->n_ctx > 1 ? eng->ctx[k].stream : nullptr;
+    QV_ORDERED(eng, stream);
+    return fetch_results(eng, eng->ctx[k], batch, t_max, res, greedy_host, stream);
 }
 
 extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int32_t n_codes, int32_t *base_start,
@@ -944,23 +907,24 @@ extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int3
     QV_ORDERED(eng, stream_);
     hipStream_t stream = (hipStream_t)stream_;
     if (!eng) return QV_ERR_ARG;
-    eng->ctx[eng->cur_ctx].al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
-    int rc = QV_POST(eng, qv_post_debug_retrieve)(eng, codes_host, n_codes, stream);
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    c.al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
+    int rc = QV_POST(eng, qv_post_debug_retrieve)(eng, c, codes_host, n_codes, stream);
     if (rc) return rc;
     QvUtt u;
-    QV_HIP(hipMemcpy(&u, eng->work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));
+    QV_HIP(hipMemcpy(&u, c.work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));
     *base_start = u.base_start; *base_span = u.base_span; *base_score = u.base_score;
     int n = u.n_cand < cand_cap ? u.n_cand : cand_cap;
     *n_cand = u.n_cand;
     if (n > 0) {
-        QV_HIP(hipMemcpy(cand_start, eng->work.cand_start, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-        QV_HIP(hipMemcpy(cand_span, eng->work.cand_span, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-        QV_HIP(hipMemcpy(cand_score, eng->work.cand_score, sizeof(double) * n, hipMemcpyDeviceToHost));
+        QV_HIP(hipMemcpy(cand_start, c.work.cand_start, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        QV_HIP(hipMemcpy(cand_span, c.work.cand_span, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        QV_HIP(hipMemcpy(cand_score, c.work.cand_score, sizeof(double) * n, hipMemcpyDeviceToHost));
     }
     *n_runners = u.n_runners;
     if (u.n_runners > 0) {
-        QV_HIP(hipMemcpy(runner_idx, eng->work.runner_idx, sizeof(int32_t) * u.n_runners, hipMemcpyDeviceToHost));
-        QV_HIP(hipMemcpy(runner_score, eng->work.runner_score, sizeof(double) * u.n_runners, hipMemcpyDeviceToHost));
+        QV_HIP(hipMemcpy(runner_idx, c.work.runner_idx, sizeof(int32_t) * u.n_runners, hipMemcpyDeviceToHost));
+        QV_HIP(hipMemcpy(runner_score, c.work.runner_score, sizeof(double) * u.n_runners, hipMemcpyDeviceToHost));
     }
     return QV_OK;
 }
@@ -987,7 +951,7 @@ extern "C" int qv_tracker_match(qv_engine *eng, const uint8_t *codes_host, const
                                  (hipStream_t)stream);
 }
 
-// Entry points that run a single text through the CURRENT context's workspace on the caller's
+// Entry points that run a single text through the workspace of ctx[cur_ctx] on the caller's
 // stream: with batches in flight, wait until no internal stream is still using a workspace.
 static int quiesce_contexts(qv_engine *eng) {
     if (eng->n_ctx > 1)
@@ -1011,11 +975,12 @@ extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t
         if (bonus_verse[i] < 0 || bonus_verse[i] >= eng->tab.n_verses) { qv_set_error(eng, "qv_match_verse: bonus verse out of range"); return QV_ERR_ARG; }
     if (n_codes > eng->max_q) { qv_set_error(eng, "qv_match_verse: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     QV_TRY(quiesce_contexts(eng));
-    eng->ctx[eng->cur_ctx].al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
-    int rc = QV_POST(eng, qv_post_match_verse)(eng, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    c.al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
+    int rc = QV_POST(eng, qv_post_match_verse)(eng, c, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
     if (rc) return rc;
     QvUtt u;
-    QV_HIP(hipMemcpy(&u, eng->work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));
+    QV_HIP(hipMemcpy(&u, c.work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));
     *start = u.base_start; *span = u.base_span; *score = u.base_score;
     return QV_OK;
 }
@@ -1043,8 +1008,8 @@ extern "C" int qv_align(qv_engine *eng, const float *lp, const int32_t *t_host, 
     int64_t total = 0;
     for (int b = 0; b < batch; ++b) total += lens_host[b] > 0 ? lens_host[b] : 0;
     if (total > 0 && !targets_host) { qv_set_error(eng, "qv_align: targets_host is null"); return QV_ERR_ARG; }
-    return qv_align_explicit(eng, lp, t_host, batch, t_max, targets_host, lens_host, info_host, first_host, last_host, logp_host,
-                             pitch, (hipStream_t)stream);
+    return qv_align_explicit(eng, eng->ctx[eng->cur_ctx], lp, t_host, batch, t_max, targets_host, lens_host, info_host, first_host,
+                             last_host, logp_host, pitch, (hipStream_t)stream);
 }
 
 extern "C" int qv_align_results_ctx(qv_engine *eng, int32_t k, int32_t batch, qv_align_info *info_host, uint16_t *ids_host,
@@ -1065,7 +1030,7 @@ extern "C" int qv_debug_forward_tap(qv_engine *eng, int32_t what, int32_t layer,
     QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!eng->model) { qv_set_error(eng, "engine created without a model"); return QV_ERR_NO_MODEL; }
-    return qv_model_tap(eng, eng->model, what, layer, out_dev, (hipStream_t)stream);
+    return qv_model_tap(eng, eng->model, eng->cur_ctx, what, layer, out_dev, (hipStream_t)stream);
 }
 
 // ---- measurement hooks -------------------------------------------------------------------
@@ -1087,7 +1052,7 @@ extern "C" int qv_profile_replay_kernel(qv_engine *eng, int32_t which, char *nam
     QV_SERIALISE(eng);
     if (!eng || !name_out || name_cap < 8) return QV_ERR_ARG;
     if (!eng->model) { qv_set_error(eng, "engine created without a model"); return QV_ERR_NO_MODEL; }
-    return qv_model_replay_kernel(eng, eng->model, which, name_out, name_cap);
+    return qv_model_replay_kernel(eng, eng->model, eng->cur_ctx, which, name_out, name_cap);
 }
 
 extern "C" int qv_weights_info(qv_engine *eng, char *out, int32_t cap) {
@@ -1139,5 +1104,5 @@ extern "C" int qv_profile_replay_gemm(qv_engine *eng, int32_t which, int32_t ite
     QV_SERIALISE(eng);
     if (!eng || !avg_us || !flops_per_launch) return QV_ERR_ARG;
     if (!eng->model) { qv_set_error(eng, "engine created without a model"); return QV_ERR_NO_MODEL; }
-    return qv_model_replay_gemm(eng, eng->model, which, iters, avg_us, flops_per_launch, (hipStream_t)stream);
+    return qv_model_replay_gemm(eng, eng->model, eng->cur_ctx, which, iters, avg_us, flops_per_launch, (hipStream_t)stream);
 }

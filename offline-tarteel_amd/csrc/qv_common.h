@@ -203,20 +203,21 @@ struct QvAlignWs {
     unsigned char *out_host; // pinned mirror of out
     unsigned char *in_host;  // pinned mirror of plan + targets
 };
-int qv_align_explicit(qv_engine *eng, const float *lp, const int32_t *t_host, int batch, int t_max, const uint16_t *targets_host,
+struct QvCtx;
+int qv_align_explicit(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max, const uint16_t *targets_host,
                       const int32_t *lens_host, qv_align_info *info_host, int16_t *first_host, int16_t *last_host,
                       float *logp_host, int pitch, hipStream_t stream);
 int qv_align_results(qv_engine *eng, int k, int batch, qv_align_info *info_host, uint16_t *ids_host, int16_t *first_host,
                      int16_t *last_host, float *logp_host, int pitch);
 
-// post-logits launcher (qv_postlogits.hip)
+// post-logits launchers (qv_postlogits.hip); `c` is the execution context whose workspace and staging slots the call uses
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,
                           qv_track_match *out_host, hipStream_t stream);
-int qv_post_run(qv_engine *eng, const float *logprobs_dev, int t_max, const int32_t *t_host, int batch,
+int qv_post_run(qv_engine *eng, QvCtx &c, const float *logprobs_dev, int t_max, const int32_t *t_host, int batch,
                 hipStream_t stream);
-int qv_post_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int n, hipStream_t stream);
-int qv_post_match_verse(qv_engine *eng, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
+int qv_post_debug_retrieve(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, hipStream_t stream);
+int qv_post_match_verse(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
                         const double *bonus_value, int max_span, hipStream_t stream);
 int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg, const int32_t *lens, int n,
                       float *loss_host, hipStream_t stream);
@@ -224,10 +225,10 @@ int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg
 int qv_post_tracker_match_wide(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                                const int32_t *n_words_host, const int32_t *bonus_host, int batch,
                                qv_track_match *out_host, hipStream_t stream);
-int qv_post_run_wide(qv_engine *eng, const float *logprobs_dev, int t_max, const int32_t *t_host, int batch,
+int qv_post_run_wide(qv_engine *eng, QvCtx &c, const float *logprobs_dev, int t_max, const int32_t *t_host, int batch,
                      hipStream_t stream);
-int qv_post_debug_retrieve_wide(qv_engine *eng, const uint8_t *codes_host, int n, hipStream_t stream);
-int qv_post_match_verse_wide(qv_engine *eng, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
+int qv_post_debug_retrieve_wide(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, hipStream_t stream);
+int qv_post_match_verse_wide(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
                              const double *bonus_value, int max_span, hipStream_t stream);
 #define QV_POST(eng, fn) ((eng)->max_q > QV_MAX_TRANSCRIPT ? fn##_wide : fn)
 
@@ -235,22 +236,23 @@ int qv_post_match_verse_wide(qv_engine *eng, const uint8_t *codes_host, int n, i
 struct QvModel;
 int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out);
 void qv_model_destroy(QvModel *m);
-int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio_dev, const int64_t *len_host, int batch,
+// `k` is the execution context whose activations (and forward graphs) the call works on
+int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio_dev, const int64_t *len_host, int batch,
                      int64_t n_max, float *logprobs_dev, int t_max, int32_t *t_out_host, hipStream_t stream,
                      bool zero_pad_rows = false,    // true: rows t >= T[b] of logprobs_dev are zeroed (the public qv_forward)
                      bool may_graph = false);       // true: `stream` is one of the engine's own (capturable) context streams
-int qv_model_tap(qv_engine *eng, QvModel *m, int what, int layer, float *out_dev, hipStream_t stream);
-int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int which, int iters, double *avg_us, double *flops, hipStream_t s);
-int qv_model_replay_kernel(qv_engine *eng, QvModel *m, int which, char *name_out, int cap);
+int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *out_dev, hipStream_t stream);
+int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int k, int which, int iters, double *avg_us, double *flops, hipStream_t s);
+int qv_model_replay_kernel(qv_engine *eng, QvModel *m, int k, int which, char *name_out, int cap);
 
 void qv_model_weights_info(const QvModel *m, char *out, int cap);
 void qv_model_graph_stats(const QvModel *m, int64_t *replays, int64_t *captures);
 int64_t qv_model_graph_failures(const QvModel *m);   // captures / instantiations that failed (the context then runs plain launches)
-void qv_model_select_ctx(QvModel *m, int k);
-// records stage event `i` of the current context on `s` when stage profiling is on (qv_capi.hip)
-void qv_stage_mark(qv_engine *eng, int i, hipStream_t s);
+// records stage event `i` of context `c` on `s` when stage profiling is on (qv_capi.hip)
+void qv_stage_mark(qv_engine *eng, QvCtx &c, int i, hipStream_t s);
 
-// One execution context = everything a batch in flight owns (activations live in QvModel).
+// One execution context = everything a batch in flight owns; this struct is the only home of its post-logits state (the
+// model keeps the activations of context k in QvModel::ctx_acts[k]).  Functions that work on a context are handed it.
 // With n_ctx > 1, qv_predict_batch_async() round-robins the contexts, each on its own internal
 // stream, so the latency-bound post-logits kernels of one batch run under the forward of the next.
 #define QV_MAX_CTX 8
@@ -260,25 +262,25 @@ void qv_stage_mark(qv_engine *eng, int i, hipStream_t s);
 // on one context (n_contexts = 1 included) never overwrite lengths a queued copy has yet to read.
 #define QV_STAGE_SLOTS 2
 struct QvCtx {
-    QvWork work;
-    float *logprobs_ws;
-    int32_t *t_host_scratch;   // [QV_STAGE_SLOTS][max_batch] pinned
-    int32_t *t_dev;
-    hipStream_t stream;
-    hipEvent_t in_ready, done;
-    bool busy;
-    int last_batch, last_tmax;
-    hipEvent_t t_copied[QV_STAGE_SLOTS];
-    bool t_pending[QV_STAGE_SLOTS];
-    int t_slot;
+    QvWork work = {};
+    float *logprobs_ws = nullptr;        // [max_batch][t_cap][1025] log-prob workspace (engines with a model)
+    int32_t *t_host_scratch = nullptr;   // [QV_STAGE_SLOTS][max_batch] pinned
+    int32_t *t_dev = nullptr;            // [max_batch]
+    hipStream_t stream = nullptr;        // n_ctx > 1: the context's own stream, with the events that fence a batch on it
+    hipEvent_t in_ready = nullptr, done = nullptr;
+    bool busy = false;
+    int last_batch = 0, last_tmax = 0;   // shape of the last post-logits run on this context
+    hipEvent_t t_copied[QV_STAGE_SLOTS] = {};
+    bool t_pending[QV_STAGE_SLOTS] = {};
+    int t_slot = 0;
     // stage timers (qv_profile_stages): start, forward done, decode done, build done, rerank done
-    hipEvent_t stage_ev[5];
-    bool stage_valid;
+    hipEvent_t stage_ev[5] = {};
+    bool stage_valid = false;
     // the post-logits chain (k_decode .. k_result, 13 kernels) as ONE hipGraph launch, keyed by what the kernel
     // arguments depend on; captured the first time a key is seen on this context
-    struct PostGraph { const float *lp; int batch, t_max, variants; hipGraphExec_t exec; } post_graph[4];   // variants: the kernel variants in force (spans, CTC) and the engine's window
+    struct PostGraph { const float *lp; int batch, t_max, variants; hipGraphExec_t exec; } post_graph[4] = {};   // variants: the kernel variants in force (spans, CTC) and the engine's window
     bool post_graph_off = false;   // a capture / instantiate failed on this context: plain launches from then on
-    int n_post_graph;
+    int n_post_graph = 0;
     // forced alignment (qv_align_results_ctx): what the context's last batch was decoded from -- log-prob tensor (the
     // context's workspace or the caller's), its row pitch in frames, batch size, the stream the chain ran on -- and the
     // lazily allocated workspace.  al_lp == nullptr: nothing to align (no batch yet, or the workspace was reused).
@@ -291,10 +293,10 @@ struct QvCtx {
 struct qv_engine {
     // every entry point that touches the engine takes this lock for the duration of the HOST call (entry points call
     // one another, hence recursive): calls from several host threads are serialised instead of corrupting the shared
-    // host-side state (current context, staging slots); the device work they enqueue stays asynchronous
+    // host-side state (context rotation, staging slots); the device work they enqueue stays asynchronous
     std::recursive_mutex mu;
     // ... and consecutive calls that enqueue on DIFFERENT caller streams are ordered on the device as well (they share
-    // the current context's workspace): each such call waits for the event the previous one left behind (QvStreamOrder)
+    // a context's workspace): each such call waits for the event the previous one left behind (QvStreamOrder)
     hipEvent_t tail_ev = nullptr;
     hipStream_t tail_stream = nullptr;
     bool tail_valid = false;
@@ -306,14 +308,10 @@ struct qv_engine {
     QvTables tab;                 // device pointers
     std::vector<void *> allocs;   // everything hipMalloc'ed for tables/work
     QvCtx ctx[QV_MAX_CTX];
+    // cur_ctx: index of the context of the most recent asynchronous call (qv_last_context), written by
+    // qv_predict_batch_async alone.  The entry points without a context argument act on ctx[cur_ctx].
     int n_ctx, cur_ctx, next_ctx;
-    // the CURRENT context's buffers (copied from ctx[cur_ctx] by qv_select_ctx; launches capture
-    // pointer values, and all enqueueing is host-serial)
-    QvWork work;
     QvModel *model;
-    float *logprobs_ws;           // [max_batch][t_cap][1025] engine-owned log-prob workspace
-    int32_t *t_host_scratch;      // pinned [max_batch]
-    int32_t *t_dev;               // [max_batch]
     // resampler filters already arranged per phase and resident in HBM (qv_upfirdn)
     struct Fir { int up; std::vector<float> taps; float *hflip_dev; int P; };
     std::vector<Fir> firs;
@@ -329,5 +327,4 @@ struct qv_engine {
     // host copies of small table parts used by debug/entry code
     std::vector<uint8_t> h_surah;
     std::vector<uint16_t> h_ayah;
-    int last_batch, last_tmax;
 };

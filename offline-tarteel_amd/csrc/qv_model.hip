@@ -237,30 +237,45 @@ extern "C" int qv_weight_random(uint64_t seed, int32_t index, float *out, int64_
 }
 
 #define QV_FWD_GRAPHS 4
-// per-context state: the activations of one batch in flight
+// the forward's launches (log-mel .. log-softmax) as ONE hipGraph launch, keyed by everything a grid size or kernel
+// argument is computed from on the host; per-utterance lengths are read from lens_dev by the kernels
+struct FwdKey {
+    const float *audio; float *logprobs; const half_t *pos; int64_t n_max; int v[13];
+    bool operator==(const FwdKey &o) const {
+        return audio == o.audio && logprobs == o.logprobs && pos == o.pos && n_max == o.n_max && !memcmp(v, o.v, sizeof(v));
+    }
+};
+struct FwdGraph { FwdKey key; hipGraphExec_t exec; int64_t last_use; };
+
+// per-context state: the activations of one batch in flight, their staging buffer, the context's forward graphs
 struct QvActs {
     float *feats, *x, *logits;
     double *mel_stats;   // [batch][80][2] per-feature sum / sum of squares, then the per-chunk partial sums (qv_melstats_doubles)
     half_t *c0, *c1, *c1p, *c2, *c2p, *c2k, *ln, *hbuf, *qk, *vt, *att, *glu, *dw, *xh;
     int32_t *lens_dev;   // [5][max_batch]: n_samples, tm, l1, l2, l3; then [max_batch + 1] packed row offsets
     int32_t *row_map;    // [M] utterance << 16 | frame of every packed row (written by k_pack_rows)
-    int32_t *lens_host;  // pinned, QV_STAGE_SLOTS slots of [6 * max_batch + 1] (see QvCtx)
-    hipEvent_t lens_copied[QV_STAGE_SLOTS];
-    bool lens_pending[QV_STAGE_SLOTS];
-    int lens_slot, lens_last;   // next slot to fill; slot of the last forward (qv_model_tap reads its offsets)
+    int32_t *lens_host = nullptr;   // pinned, QV_STAGE_SLOTS slots of [6 * max_batch + 1] (see QvCtx)
+    hipEvent_t lens_copied[QV_STAGE_SLOTS] = {};
+    bool lens_pending[QV_STAGE_SLOTS] = {};
+    int lens_slot = 0, lens_last = 0;   // next slot to fill; slot of the last forward (qv_model_tap reads its offsets)
     float *tap_x;        // [N_LAYERS+1][M][512] when save_taps
-    int last_batch, last_tmax, last_tm_max, last_rows, last_t2m;
+    int last_batch = 0, last_tmax = 0, last_tm_max = 0, last_rows = 0, last_t2m = 0;
     // QV_PREC_ORT_MIXED: the float32 tensors in front of the quantisers, the s8 operand buffer, the range keys
     float *c1f, *c1pf, *c2f, *gluf, *dwf;
     int8_t *q8;
     uint32_t *mm;        // [MM_SITES][max_batch][QV_MM_STRIDE]: {min, max} keys at the front of each utterance's slot
     float *tap_lnc, *tap_glu, *tap_dw;   // [N_LAYERS][M][512] each when save_taps
+    FwdGraph fwd_graph[QV_FWD_GRAPHS];
+    int n_fwd_graph = 0;
+    int64_t fwd_tick = 0, fwd_last_capture = 0;   // forwards seen by the context / the one that captured last
+    bool fwd_disabled = false;                    // a capture or instantiate failed on this context: plain launches from then on
+    FwdKey fwd_seen[QV_FWD_GRAPHS] = {};          // keys of the context's last few uncaptured forwards: a shape is captured when it comes back
+    int fwd_seen_at = 0;
 };
 
-// the flat QvActs base is the CURRENT context (qv_model_select_ctx copies it in and out)
-struct QvModel : QvActs {
-    QvActs ctx_acts[QV_MAX_CTX];
-    int n_ctx, cur_ctx;
+struct QvModel {
+    QvActs ctx_acts[QV_MAX_CTX] = {};   // context k's state: the functions that run on a context are handed k
+    int n_ctx;
     std::vector<void *> allocs;
     FrontendTab ft;
     const float *c0_w, *c0_b, *dw2_w, *dw2_b, *dw5_w, *dw5_b, *pw3_b, *pw6_b, *sub_out_b, *head_b;
@@ -279,29 +294,10 @@ struct QvModel : QvActs {
     int max_batch, tm_cap, t1_cap, t2_cap, t3_cap;
     std::map<int, half_t *> pos_cache;  // t_max -> projected positions f16 [2*t_max-1][17*512]
     bool save_taps;
-    // the forward's launches (log-mel .. log-softmax) as ONE hipGraph launch per context, keyed by everything a grid
-    // size or kernel argument is computed from on the host; per-utterance lengths are read from lens_dev by the kernels
-    struct FwdKey {
-        const float *audio; float *logprobs; const half_t *pos; int64_t n_max; int v[13];
-        bool operator==(const FwdKey &o) const {
-            return audio == o.audio && logprobs == o.logprobs && pos == o.pos && n_max == o.n_max && !memcmp(v, o.v, sizeof(v));
-        }
-    };
-    struct FwdGraph { FwdKey key; hipGraphExec_t exec; int64_t last_use; } fwd_graph[QV_MAX_CTX][QV_FWD_GRAPHS];
-    int n_fwd_graph[QV_MAX_CTX] = {};
-    int64_t fwd_tick[QV_MAX_CTX] = {}, fwd_last_capture[QV_MAX_CTX] = {};   // forwards seen by the context / the one that captured last
-    bool fwd_disabled[QV_MAX_CTX] = {};        // a capture or instantiate failed on this context: plain launches from then on
-    int64_t fwd_capture_failures = 0;
-    FwdKey fwd_seen[QV_MAX_CTX][QV_FWD_GRAPHS] = {};   // keys of the context's last few uncaptured forwards: a shape is captured when it comes back
-    int fwd_seen_at[QV_MAX_CTX] = {};
-    int64_t fwd_replays = 0, fwd_captures = 0;   // graph launches / captures since creation (qv_debug_forward_graph_stats)
+    // forward graphs of all contexts together (qv_debug_forward_graph_stats / _failures): graph launches, captures, and
+    // captures or instantiations that failed
+    int64_t fwd_replays = 0, fwd_captures = 0, fwd_capture_failures = 0;
 };
-
-void qv_model_select_ctx(QvModel *m, int k) {
-    m->ctx_acts[m->cur_ctx] = *static_cast<QvActs *>(m);
-    *static_cast<QvActs *>(m) = m->ctx_acts[k];
-    m->cur_ctx = k;
-}
 
 namespace {
 
@@ -690,64 +686,49 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const hal
     return QV_OK;
 }
 
-// activations of execution context k (into the flat fields, then filed under ctx_acts[k])
+// activations, staging buffer and events of execution context k
 int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused) {
+    QvActs &a = m->ctx_acts[k];
     const size_t Bz = (size_t)m->max_batch, M = Bz * m->t3_cap;
     const int t_pad_cap = (m->t3_cap + 31) / 32 * 32;
-    m->lens_host = nullptr;
-    TRY(dal(eng, m, Bz * m->tm_cap * QV_NMEL, &m->feats));
-    TRY(dal(eng, m, qv_melstats_doubles(Bz), &m->mel_stats));
+    TRY(dal(eng, m, Bz * m->tm_cap * QV_NMEL, &a.feats));
+    TRY(dal(eng, m, qv_melstats_doubles(Bz), &a.mel_stats));
     // the conv0 activation only exists on the two-kernel cross-check path (QVERSE_SUB_UNFUSED=1)
-    m->c0 = nullptr;
-    if (sub_unfused) TRY(dal(eng, m, Bz * m->t1_cap * 40 * QV_SUBC, &m->c0));
-    TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &m->c1));
-    TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &m->c1p));
-    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &m->c2));
-    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &m->c2p));
-    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &m->c2k));
-    TRY(dal(eng, m, M * QV_D, &m->x));
-    TRY(dal(eng, m, M * QV_D, &m->ln));
-    TRY(dal(eng, m, M * QV_FF, &m->hbuf));
-    TRY(dal(eng, m, M * 2 * QV_D, &m->qk));
-    TRY(dal(eng, m, Bz * QV_D * t_pad_cap, &m->vt));
-    TRY(dal(eng, m, M * QV_D, &m->att));
-    TRY(dal(eng, m, M * QV_D, &m->glu));
-    TRY(dal(eng, m, M * QV_D, &m->dw));
-    TRY(dal(eng, m, M * QV_D, &m->xh));
-    TRY(dal(eng, m, M * HEAD_N, &m->logits));
-    TRY(dal(eng, m, Bz * 6 + 1, &m->lens_dev));
-    TRY(dal(eng, m, M, &m->row_map));
-    QV_HIP(hipHostMalloc((void **)&m->lens_host, sizeof(int32_t) * (Bz * 6 + 1) * QV_STAGE_SLOTS, hipHostMallocDefault));
-    m->ctx_acts[k].lens_host = m->lens_host;  // owned by the context from here on
-    for (int i = 0; i < QV_STAGE_SLOTS; ++i) {
-        m->lens_copied[i] = nullptr;
-        QV_HIP(hipEventCreateWithFlags(&m->lens_copied[i], hipEventDisableTiming));
-        m->ctx_acts[k].lens_copied[i] = m->lens_copied[i];
-        m->lens_pending[i] = false;
-    }
-    m->lens_slot = m->lens_last = 0;
-    m->tap_x = nullptr;
-    if (m->save_taps) TRY(dal(eng, m, (size_t)(N_LAYERS + 1) * M * QV_D, &m->tap_x));
-    m->c1f = m->c1pf = m->c2f = m->gluf = m->dwf = nullptr;
-    m->q8 = nullptr;
-    m->mm = nullptr;
-    m->tap_lnc = m->tap_glu = m->tap_dw = nullptr;
+    if (sub_unfused) TRY(dal(eng, m, Bz * m->t1_cap * 40 * QV_SUBC, &a.c0));
+    TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1));
+    TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1p));
+    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2));
+    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2p));
+    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2k));
+    TRY(dal(eng, m, M * QV_D, &a.x));
+    TRY(dal(eng, m, M * QV_D, &a.ln));
+    TRY(dal(eng, m, M * QV_FF, &a.hbuf));
+    TRY(dal(eng, m, M * 2 * QV_D, &a.qk));
+    TRY(dal(eng, m, Bz * QV_D * t_pad_cap, &a.vt));
+    TRY(dal(eng, m, M * QV_D, &a.att));
+    TRY(dal(eng, m, M * QV_D, &a.glu));
+    TRY(dal(eng, m, M * QV_D, &a.dw));
+    TRY(dal(eng, m, M * QV_D, &a.xh));
+    TRY(dal(eng, m, M * HEAD_N, &a.logits));
+    TRY(dal(eng, m, Bz * 6 + 1, &a.lens_dev));
+    TRY(dal(eng, m, M, &a.row_map));
+    QV_HIP(hipHostMalloc((void **)&a.lens_host, sizeof(int32_t) * (Bz * 6 + 1) * QV_STAGE_SLOTS, hipHostMallocDefault));
+    for (int i = 0; i < QV_STAGE_SLOTS; ++i) QV_HIP(hipEventCreateWithFlags(&a.lens_copied[i], hipEventDisableTiming));
+    if (m->save_taps) TRY(dal(eng, m, (size_t)(N_LAYERS + 1) * M * QV_D, &a.tap_x));
     if (m->ort) {
-        TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &m->c1f));
-        TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &m->c1pf));
-        TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &m->c2f));
-        TRY(dal(eng, m, M * QV_D, &m->gluf));
-        TRY(dal(eng, m, M * QV_D, &m->dwf));
-        TRY(dal(eng, m, std::max(Bz * m->t2_cap * 20 * QV_SUBC, M * QV_D), &m->q8));
-        TRY(dal(eng, m, (size_t)MM_SITES * Bz * QV_MM_STRIDE, &m->mm));
+        TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1f));
+        TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1pf));
+        TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2f));
+        TRY(dal(eng, m, M * QV_D, &a.gluf));
+        TRY(dal(eng, m, M * QV_D, &a.dwf));
+        TRY(dal(eng, m, std::max(Bz * m->t2_cap * 20 * QV_SUBC, M * QV_D), &a.q8));
+        TRY(dal(eng, m, (size_t)MM_SITES * Bz * QV_MM_STRIDE, &a.mm));
         if (m->save_taps) {
-            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &m->tap_lnc));
-            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &m->tap_glu));
-            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &m->tap_dw));
+            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &a.tap_lnc));
+            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &a.tap_glu));
+            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &a.tap_dw));
         }
     }
-    m->last_batch = m->last_tmax = m->last_tm_max = m->last_rows = m->last_t2m = 0;
-    m->ctx_acts[k] = *static_cast<QvActs *>(m);
     return QV_OK;
 }
 
@@ -792,39 +773,32 @@ int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out) {
     const char *tp = getenv("QVERSE_DEBUG_TAPS");
     m->save_taps = tp && tp[0] == '1';
     m->n_ctx = eng->n_ctx;
-    m->cur_ctx = 0;
     const char *su = getenv("QVERSE_SUB_UNFUSED");
     const bool sub_unfused = su && su[0] == '1';
-    for (QvActs &a : m->ctx_acts) {
-        a = QvActs();
-        a.lens_host = nullptr;
-        for (hipEvent_t &e : a.lens_copied) e = nullptr;
-    }
-    // contexts are allocated last to first so that the flat fields end up being context 0
-    for (int k = m->n_ctx - 1; k >= 0; --k) TRY(alloc_context(eng, m, k, sub_unfused));
+    for (int k = 0; k < m->n_ctx; ++k) TRY(alloc_context(eng, m, k, sub_unfused));
     return QV_OK;
 }
 
 void qv_model_destroy(QvModel *m) {
     if (!m) return;
-    for (int k = 0; k < QV_MAX_CTX; ++k)
-        for (int i = 0; i < m->n_fwd_graph[k]; ++i) (void)hipGraphExecDestroy(m->fwd_graph[k][i].exec);
     for (void *p : m->allocs) (void)hipFree(p);
     for (QvActs &a : m->ctx_acts) {
+        for (int i = 0; i < a.n_fwd_graph; ++i) (void)hipGraphExecDestroy(a.fwd_graph[i].exec);
         if (a.lens_host) (void)hipHostFree(a.lens_host);
         for (hipEvent_t e : a.lens_copied) if (e) (void)hipEventDestroy(e);
     }
     delete m;
 }
 
-int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64_t *len_host, int batch, int64_t n_max,
+int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, const int64_t *len_host, int batch, int64_t n_max,
                      float *logprobs, int t_max_out, int32_t *t_out_host, hipStream_t s, bool zero_pad_rows, bool may_graph) {
     if (batch < 1 || batch > m->max_batch) { qv_set_error(eng, "batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    QvActs &a = m->ctx_acts[k];
     int B = batch, MB = m->max_batch;
     int tm_max = 0, t1m = 0, t2m = 0, t3m = 0, t3min = INT32_MAX, rows = 0;
-    const int slot = m->lens_slot;
-    if (m->lens_pending[slot]) { QV_HIP(hipEventSynchronize(m->lens_copied[slot])); m->lens_pending[slot] = false; }
-    int32_t *lh = m->lens_host + (size_t)slot * (MB * 6 + 1);
+    const int slot = a.lens_slot;
+    if (a.lens_pending[slot]) { QV_HIP(hipEventSynchronize(a.lens_copied[slot])); a.lens_pending[slot] = false; }
+    int32_t *lh = a.lens_host + (size_t)slot * (MB * 6 + 1);
     for (int b = 0; b < B; ++b) {
         int64_t n = len_host[b];
         if (n < 400 || n > n_max || n / 160 + 1 > m->tm_cap) {
@@ -848,12 +822,12 @@ int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64
     const int T = t3m;
     const int M = rows;
     const int t_pad = (T + 31) / 32 * 32;
-    QV_HIP(hipMemcpyAsync(m->lens_dev, lh, sizeof(int32_t) * (MB * 6 + 1), hipMemcpyHostToDevice, s));
-    QV_HIP(hipEventRecord(m->lens_copied[slot], s));
-    m->lens_pending[slot] = true;
-    m->lens_last = slot;
-    m->lens_slot = (slot + 1) % QV_STAGE_SLOTS;
-    const int32_t *d_n = m->lens_dev, *d_tm = d_n + MB, *d_l1 = d_n + 2 * MB, *d_l2 = d_n + 3 * MB, *d_l3 = d_n + 4 * MB,
+    QV_HIP(hipMemcpyAsync(a.lens_dev, lh, sizeof(int32_t) * (MB * 6 + 1), hipMemcpyHostToDevice, s));
+    QV_HIP(hipEventRecord(a.lens_copied[slot], s));
+    a.lens_pending[slot] = true;
+    a.lens_last = slot;
+    a.lens_slot = (slot + 1) % QV_STAGE_SLOTS;
+    const int32_t *d_n = a.lens_dev, *d_tm = d_n + MB, *d_l1 = d_n + 2 * MB, *d_l2 = d_n + 3 * MB, *d_l3 = d_n + 4 * MB,
                   *d_off = d_n + 5 * MB;
     const half_t *posp = nullptr;
     TRY(get_pos(eng, m, T, s, &posp));
@@ -875,152 +849,152 @@ int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64
         for (int b = 0; b < B; ++b) t_min_pad = std::min(t_min_pad, (int)t_out_host[b]);
     }
     auto launch_all = [&]() -> int {
-    uint32_t *mm_base = m->mm;
+    uint32_t *mm_base = a.mm;
     auto mm_site = [&](int site) { return mm_base + (size_t)site * MB * QV_MM_STRIDE; };
     if (m->ort) {
         // QV_PREC_ORT_MIXED front-end: every Conv is DynamicQuantizeLinear -> ConvInteger (qv_ort.h); the strided /
         // depthwise ones as exact integer stencils, the two pointwise ones on the i8 MFMA
-        launch_mm_init(m->mm, (size_t)MM_SITES * MB * QV_MM_STRIDE, s);
-        launch_logmel(audio, n_max, d_n, m->ft, m->feats, tm_max, m->mel_stats, B, s);
-        launch_mel_minmax(m->feats, d_n, tm_max, m->mel_stats, mm_site(MM_MEL), B, s);
+        launch_mm_init(a.mm, (size_t)MM_SITES * MB * QV_MM_STRIDE, s);
+        launch_logmel(audio, n_max, d_n, m->ft, a.feats, tm_max, a.mel_stats, B, s);
+        launch_mel_minmax(a.feats, d_n, tm_max, a.mel_stats, mm_site(MM_MEL), B, s);
         for (int pass = 0; pass < 2; ++pass)
-            launch_sub01_ort(pass, m->feats, tm_max, d_tm, m->mel_stats, m->o_c0.wq, m->o_c0.scale, m->c0_b, d_l1, m->o_dw2.wq,
-                             m->o_dw2.scale, m->dw2_b, d_l2, mm_site(MM_MEL), mm_site(MM_C0), mm_site(MM_C1), m->c1f, t2m, B, s);
+            launch_sub01_ort(pass, a.feats, tm_max, d_tm, a.mel_stats, m->o_c0.wq, m->o_c0.scale, m->c0_b, d_l1, m->o_dw2.wq,
+                             m->o_dw2.scale, m->dw2_b, d_l2, mm_site(MM_MEL), mm_site(MM_C0), mm_site(MM_C1), a.c1f, t2m, B, s);
         GemmArgs g = {};
         g.alpha = 1.f;
         g.len = d_l2; g.rows_per_utt = t2m * 20; g.f_per_t = 20;
-        launch_quant_rows(m->c1f, B * t2m * 20, QV_SUBC, RowOwner{nullptr, g.len, g.rows_per_utt, g.f_per_t}, mm_site(MM_C1), m->q8, s);
-        g.A = (const half_t *)m->q8; g.Wi8 = m->o_pw3.wq; g.wsum = m->o_pw3.wsum; g.w_scale = m->o_pw3.scale; g.bias = m->pw3_b;
-        g.out = m->c1pf; g.mm_in = mm_site(MM_C1); g.mm_out = mm_site(MM_C1P);
+        launch_quant_rows(a.c1f, B * t2m * 20, QV_SUBC, RowOwner{nullptr, g.len, g.rows_per_utt, g.f_per_t}, mm_site(MM_C1), a.q8, s);
+        g.A = (const half_t *)a.q8; g.Wi8 = m->o_pw3.wq; g.wsum = m->o_pw3.wsum; g.w_scale = m->o_pw3.scale; g.bias = m->pw3_b;
+        g.out = a.c1pf; g.mm_in = mm_site(MM_C1); g.mm_out = mm_site(MM_C1P);
         g.M = B * t2m * 20; g.N = QV_SUBC; g.K = QV_SUBC / 2; g.lda = QV_SUBC / 2; g.ldw = QV_SUBC / 2; g.ldo = QV_SUBC;
         launch_gemm(EPI_F32_RELU, g, s);
-        launch_dwconv2d_ort(m->c1pf, t2m, 20, d_l2, m->o_dw5.wq, m->o_dw5.scale, m->dw5_b, d_l3, mm_site(MM_C1P), mm_site(MM_C2),
-                            m->c2f, t3m, 10, B, s);
+        launch_dwconv2d_ort(a.c1pf, t2m, 20, d_l2, m->o_dw5.wq, m->o_dw5.scale, m->dw5_b, d_l3, mm_site(MM_C1P), mm_site(MM_C2),
+                            a.c2f, t3m, 10, B, s);
         g.len = d_l3; g.rows_per_utt = t3m * 10; g.f_per_t = 10;
-        launch_quant_rows(m->c2f, B * t3m * 10, QV_SUBC, RowOwner{nullptr, g.len, g.rows_per_utt, g.f_per_t}, mm_site(MM_C2), m->q8, s);
+        launch_quant_rows(a.c2f, B * t3m * 10, QV_SUBC, RowOwner{nullptr, g.len, g.rows_per_utt, g.f_per_t}, mm_site(MM_C2), a.q8, s);
         g.Wi8 = m->o_pw6.wq; g.wsum = m->o_pw6.wsum; g.w_scale = m->o_pw6.scale; g.bias = m->pw6_b;
-        g.out = m->c2p; g.mm_in = mm_site(MM_C2); g.mm_out = nullptr; g.M = B * t3m * 10;
+        g.out = a.c2p; g.mm_in = mm_site(MM_C2); g.mm_out = nullptr; g.M = B * t3m * 10;
         launch_gemm(EPI_F16_RELU, g, s);
-        launch_pack_rows(m->c2p, t3m, 10 * QV_SUBC, d_l3, d_off, m->c2k, m->row_map, B, s);
+        launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
         GemmArgs o = {};
-        o.A = m->c2k; o.W = m->sub_out_w; o.bias = m->sub_out_b; o.out = m->x;
+        o.A = a.c2k; o.W = m->sub_out_w; o.bias = m->sub_out_b; o.out = a.x;
         o.M = M; o.N = QV_D; o.K = 2560; o.lda = 2560; o.ldw = 2560; o.ldo = QV_D; o.alpha = sqrtf((float)QV_D);
         o.in_flight = m->n_ctx;
         launch_gemm(EPI_F32, o, s);
     } else
     if (!(skip & 32)) {
-    launch_logmel(audio, n_max, d_n, m->ft, m->feats, tm_max, m->mel_stats, B, s);
-    if (m->c0) {
+    launch_logmel(audio, n_max, d_n, m->ft, a.feats, tm_max, a.mel_stats, B, s);
+    if (a.c0) {
         // cross-check path: conv0 and the depthwise conv as two kernels through HBM
-        launch_conv0(m->feats, tm_max, d_tm, m->mel_stats, m->c0_w, m->c0_b, m->c0, t1m, B, s);
-        launch_dwconv2d(m->c0, t1m, 40, d_l1, m->dw2_w, m->dw2_b, m->c1, t2m, 20, B, s);
+        launch_conv0(a.feats, tm_max, d_tm, a.mel_stats, m->c0_w, m->c0_b, a.c0, t1m, B, s);
+        launch_dwconv2d(a.c0, t1m, 40, d_l1, m->dw2_w, m->dw2_b, a.c1, t2m, 20, B, s);
     } else {
-        launch_sub01(m->feats, tm_max, d_tm, m->mel_stats, m->c0_w, m->c0_b, d_l1, m->dw2_w, m->dw2_b, m->c1, t2m, B, s);
+        launch_sub01(a.feats, tm_max, d_tm, a.mel_stats, m->c0_w, m->c0_b, d_l1, m->dw2_w, m->dw2_b, a.c1, t2m, B, s);
     }
     GemmArgs g = {};
     g.alpha = 1.f;
-    g.A = m->c1; g.W = m->pw3_w; g.bias = m->pw3_b; g.out = m->c1p;
+    g.A = a.c1; g.W = m->pw3_w; g.bias = m->pw3_b; g.out = a.c1p;
     g.M = B * t2m * 20; g.N = QV_SUBC; g.K = QV_SUBC; g.lda = QV_SUBC; g.ldw = QV_SUBC; g.ldo = QV_SUBC;
     launch_gemm(EPI_F16_RELU, g, s);
-    launch_dwconv2d(m->c1p, t2m, 20, d_l2, m->dw5_w, m->dw5_b, m->c2, t3m, 10, B, s);
-    g.A = m->c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = m->c2p; g.M = B * t3m * 10;
+    launch_dwconv2d(a.c1p, t2m, 20, d_l2, m->dw5_w, m->dw5_b, a.c2, t3m, 10, B, s);
+    g.A = a.c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = a.c2p; g.M = B * t3m * 10;
     launch_gemm(EPI_F16_RELU, g, s);
-    launch_pack_rows(m->c2p, t3m, 10 * QV_SUBC, d_l3, d_off, m->c2k, m->row_map, B, s);
+    launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
     // Linear(2560 -> 512) and xscaling (x * sqrt(d_model)) in one epilogue
-    g.A = m->c2k; g.W = m->sub_out_w; g.bias = m->sub_out_b; g.out = m->x;
+    g.A = a.c2k; g.W = m->sub_out_w; g.bias = m->sub_out_b; g.out = a.x;
     g.M = M; g.N = QV_D; g.K = 2560; g.lda = 2560; g.ldw = 2560; g.ldo = QV_D; g.alpha = sqrtf((float)QV_D);
     g.in_flight = m->n_ctx;
     launch_gemm(EPI_F32, g, s);
     } else {
-        launch_pack_rows(m->c2p, t3m, 10 * QV_SUBC, d_l3, d_off, m->c2k, m->row_map, B, s);
+        launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
     }
-    if (m->save_taps) QV_HIP(hipMemcpyAsync(m->tap_x, m->x, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
+    if (m->save_taps) QV_HIP(hipMemcpyAsync(a.tap_x, a.x, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
 
-    if (!(skip & 1)) launch_layernorm(m->x, m->L[0].ln_g[0], m->L[0].ln_b[0], m->ln, M, s);
+    if (!(skip & 1)) launch_layernorm(a.x, m->L[0].ln_g[0], m->L[0].ln_b[0], a.ln, M, s);
     for (int l = 0; l < N_LAYERS; ++l) {
         const LayerW &L = m->L[l];
         auto gemm = [&](int epi, const half_t *A, int K, const WMat &W, const float *bias, void *out, int N, int ldo,
                         float alpha) {
-            GemmArgs a = {};
-            a.A = A; a.W = W.w; a.Wq = W.q; a.wscale = W.sc; a.W8 = W.q8; a.w8scale = W.sc8; a.bias = bias; a.out = out; a.out2 = m->vt;
-            a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = ldo; a.alpha = alpha; a.t_max = T; a.t_pad = t_pad;
-            a.row_map = m->row_map; a.in_flight = m->n_ctx;
-            if (!(skip & 64)) launch_gemm(epi, a, s);
-            if ((dup & 64) && epi != EPI_RESID) launch_gemm(epi, a, s);
+            GemmArgs g = {};
+            g.A = A; g.W = W.w; g.Wq = W.q; g.wscale = W.sc; g.W8 = W.q8; g.w8scale = W.sc8; g.bias = bias; g.out = out; g.out2 = a.vt;
+            g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = ldo; g.alpha = alpha; g.t_max = T; g.t_pad = t_pad;
+            g.row_map = a.row_map; g.in_flight = m->n_ctx;
+            if (!(skip & 64)) launch_gemm(epi, g, s);
+            if ((dup & 64) && epi != EPI_RESID) launch_gemm(epi, g, s);
         };
         // 1/2 FFN
-        gemm(EPI_F16_SWISH, m->ln, QV_D, L.ff1_w1, L.ff1_b1, m->hbuf, QV_FF, QV_FF, 1.f);
-        gemm(EPI_RESID, m->hbuf, QV_FF, L.ff1_w2, L.ff1_b2, m->x, QV_D, QV_D, 0.5f);
+        gemm(EPI_F16_SWISH, a.ln, QV_D, L.ff1_w1, L.ff1_b1, a.hbuf, QV_FF, QV_FF, 1.f);
+        gemm(EPI_RESID, a.hbuf, QV_FF, L.ff1_w2, L.ff1_b2, a.x, QV_D, QV_D, 0.5f);
         // rel-pos MHSA
-        if (!(skip & 1)) launch_layernorm(m->x, L.ln_g[1], L.ln_b[1], m->ln, M, s);
-        if (dup & 1) launch_layernorm(m->x, L.ln_g[1], L.ln_b[1], m->ln, M, s);
-        gemm(EPI_QKV, m->ln, QV_D, L.qkv_w, L.qkv_b, m->qk, 3 * QV_D, 2 * QV_D, 1.f);
-        if (!(skip & 4)) launch_attention(m->qk, m->vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d_l3, d_off, m->att, T, t3min, t_pad, B, s, att_variant);
-        if (dup & 4) launch_attention(m->qk, m->vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d_l3, d_off, m->att, T, t3min, t_pad, B, s, att_variant);
-        gemm(EPI_RESID, m->att, QV_D, L.out_w, L.out_b, m->x, QV_D, QV_D, 1.f);
+        if (!(skip & 1)) launch_layernorm(a.x, L.ln_g[1], L.ln_b[1], a.ln, M, s);
+        if (dup & 1) launch_layernorm(a.x, L.ln_g[1], L.ln_b[1], a.ln, M, s);
+        gemm(EPI_QKV, a.ln, QV_D, L.qkv_w, L.qkv_b, a.qk, 3 * QV_D, 2 * QV_D, 1.f);
+        if (!(skip & 4)) launch_attention(a.qk, a.vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d_l3, d_off, a.att, T, t3min, t_pad, B, s, att_variant);
+        if (dup & 4) launch_attention(a.qk, a.vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d_l3, d_off, a.att, T, t3min, t_pad, B, s, att_variant);
+        gemm(EPI_RESID, a.att, QV_D, L.out_w, L.out_b, a.x, QV_D, QV_D, 1.f);
         // conv module
         if (m->ort) {
             // norm_conv -> [DQL] pointwise_conv1 + GLU -> [DQL] depthwise_conv -> BatchNorm -> Swish -> [DQL] pointwise_conv2
             uint32_t *mm_ln = mm_site(MM_LAYER(l)), *mm_glu = mm_ln + (size_t)MB * QV_MM_STRIDE, *mm_dw = mm_glu + (size_t)MB * QV_MM_STRIDE;
             const size_t tap_off = (size_t)l * M * QV_D;
-            launch_ln_minmax(m->x, L.ln_g[2], L.ln_b[2], M, m->row_map, mm_ln, m->save_taps ? m->tap_lnc + tap_off : nullptr, s);
-            launch_ln_quant(m->x, L.ln_g[2], L.ln_b[2], M, m->row_map, mm_ln, m->q8, s);
-            GemmArgs a = {};
-            a.A = (const half_t *)m->q8; a.Wi8 = L.o_pw1.wq; a.wsum = L.o_pw1.wsum; a.w_scale = L.o_pw1.scale; a.bias = L.pw1_b;
-            a.out = m->gluf; a.M = M; a.N = 2 * QV_D; a.K = QV_D / 2; a.lda = QV_D / 2; a.ldw = QV_D / 2; a.ldo = QV_D; a.alpha = 1.f;
-            a.row_map = m->row_map; a.mm_in = mm_ln; a.mm_out = mm_glu;
-            launch_gemm(EPI_GLU, a, s);
-            launch_dwconv1d_ort(m->gluf, L.o_dw.wq, L.o_dw.scale, L.o_dw_b, L.bn_alpha, L.bn_beta, d_l3, d_off, mm_glu, mm_dw, m->dwf,
+            launch_ln_minmax(a.x, L.ln_g[2], L.ln_b[2], M, a.row_map, mm_ln, m->save_taps ? a.tap_lnc + tap_off : nullptr, s);
+            launch_ln_quant(a.x, L.ln_g[2], L.ln_b[2], M, a.row_map, mm_ln, a.q8, s);
+            GemmArgs g = {};
+            g.A = (const half_t *)a.q8; g.Wi8 = L.o_pw1.wq; g.wsum = L.o_pw1.wsum; g.w_scale = L.o_pw1.scale; g.bias = L.pw1_b;
+            g.out = a.gluf; g.M = M; g.N = 2 * QV_D; g.K = QV_D / 2; g.lda = QV_D / 2; g.ldw = QV_D / 2; g.ldo = QV_D; g.alpha = 1.f;
+            g.row_map = a.row_map; g.mm_in = mm_ln; g.mm_out = mm_glu;
+            launch_gemm(EPI_GLU, g, s);
+            launch_dwconv1d_ort(a.gluf, L.o_dw.wq, L.o_dw.scale, L.o_dw_b, L.bn_alpha, L.bn_beta, d_l3, d_off, mm_glu, mm_dw, a.dwf,
                                 T, B, s);
-            launch_quant_rows(m->dwf, M, QV_D, RowOwner{m->row_map, nullptr, 0, 0}, mm_dw, m->q8, s);
-            a.Wi8 = L.o_pw2.wq; a.wsum = L.o_pw2.wsum; a.w_scale = L.o_pw2.scale; a.bias = L.pw2_b;
-            a.out = m->x; a.N = QV_D; a.mm_in = mm_dw; a.mm_out = nullptr;
-            launch_gemm(EPI_RESID, a, s);
+            launch_quant_rows(a.dwf, M, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_dw, a.q8, s);
+            g.Wi8 = L.o_pw2.wq; g.wsum = L.o_pw2.wsum; g.w_scale = L.o_pw2.scale; g.bias = L.pw2_b;
+            g.out = a.x; g.N = QV_D; g.mm_in = mm_dw; g.mm_out = nullptr;
+            launch_gemm(EPI_RESID, g, s);
             if (m->save_taps) {
-                QV_HIP(hipMemcpyAsync(m->tap_glu + tap_off, m->gluf, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
-                QV_HIP(hipMemcpyAsync(m->tap_dw + tap_off, m->dwf, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
+                QV_HIP(hipMemcpyAsync(a.tap_glu + tap_off, a.gluf, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
+                QV_HIP(hipMemcpyAsync(a.tap_dw + tap_off, a.dwf, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
             }
         } else {
-        if (!(skip & 1)) launch_layernorm(m->x, L.ln_g[2], L.ln_b[2], m->ln, M, s);
-        if (dup & 1) launch_layernorm(m->x, L.ln_g[2], L.ln_b[2], m->ln, M, s);
-        gemm(EPI_GLU, m->ln, QV_D, L.pw1_w, L.pw1_b, m->glu, 2 * QV_D, QV_D, 1.f);
-        if (!(skip & 8)) launch_dwconv1d(m->glu, L.dw_w, L.dw_b, d_l3, d_off, m->dw, T, B, s);
-        if (dup & 8) launch_dwconv1d(m->glu, L.dw_w, L.dw_b, d_l3, d_off, m->dw, T, B, s);
-        gemm(EPI_RESID, m->dw, QV_D, L.pw2_w, L.pw2_b, m->x, QV_D, QV_D, 1.f);
+        if (!(skip & 1)) launch_layernorm(a.x, L.ln_g[2], L.ln_b[2], a.ln, M, s);
+        if (dup & 1) launch_layernorm(a.x, L.ln_g[2], L.ln_b[2], a.ln, M, s);
+        gemm(EPI_GLU, a.ln, QV_D, L.pw1_w, L.pw1_b, a.glu, 2 * QV_D, QV_D, 1.f);
+        if (!(skip & 8)) launch_dwconv1d(a.glu, L.dw_w, L.dw_b, d_l3, d_off, a.dw, T, B, s);
+        if (dup & 8) launch_dwconv1d(a.glu, L.dw_w, L.dw_b, d_l3, d_off, a.dw, T, B, s);
+        gemm(EPI_RESID, a.dw, QV_D, L.pw2_w, L.pw2_b, a.x, QV_D, QV_D, 1.f);
         }
         // 1/2 FFN
-        if (!(skip & 1)) launch_layernorm(m->x, L.ln_g[3], L.ln_b[3], m->ln, M, s);
-        if (dup & 1) launch_layernorm(m->x, L.ln_g[3], L.ln_b[3], m->ln, M, s);
-        gemm(EPI_F16_SWISH, m->ln, QV_D, L.ff2_w1, L.ff2_b1, m->hbuf, QV_FF, QV_FF, 1.f);
-        gemm(EPI_RESID, m->hbuf, QV_FF, L.ff2_w2, L.ff2_b2, m->x, QV_D, QV_D, 0.5f);
+        if (!(skip & 1)) launch_layernorm(a.x, L.ln_g[3], L.ln_b[3], a.ln, M, s);
+        if (dup & 1) launch_layernorm(a.x, L.ln_g[3], L.ln_b[3], a.ln, M, s);
+        gemm(EPI_F16_SWISH, a.ln, QV_D, L.ff2_w1, L.ff2_b1, a.hbuf, QV_FF, QV_FF, 1.f);
+        gemm(EPI_RESID, a.hbuf, QV_FF, L.ff2_w2, L.ff2_b2, a.x, QV_D, QV_D, 0.5f);
         // norm_out (+ next layer's first LayerNorm)
         if (skip & 2) { }
         else if (l + 1 < N_LAYERS)
-            launch_layernorm2(m->x, L.ln_g[4], L.ln_b[4], m->L[l + 1].ln_g[0], m->L[l + 1].ln_b[0], m->ln, M, s);
+            launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], m->L[l + 1].ln_g[0], m->L[l + 1].ln_b[0], a.ln, M, s);
         else   // last layer: the f16 copy of the encoder output (CTC head operand) comes out of the same pass
-            launch_layernorm2(m->x, L.ln_g[4], L.ln_b[4], nullptr, nullptr, m->xh, M, s);
+            launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], nullptr, nullptr, a.xh, M, s);
         if (m->save_taps)
-            QV_HIP(hipMemcpyAsync(m->tap_x + (size_t)(l + 1) * M * QV_D, m->x, sizeof(float) * (size_t)M * QV_D,
+            QV_HIP(hipMemcpyAsync(a.tap_x + (size_t)(l + 1) * M * QV_D, a.x, sizeof(float) * (size_t)M * QV_D,
                                   hipMemcpyDeviceToDevice, s));
     }
-    if (skip & 2) launch_to_half(m->x, m->xh, (size_t)M * QV_D, s);   // (timing experiments only: the pass that writes xh was skipped)
+    if (skip & 2) launch_to_half(a.x, a.xh, (size_t)M * QV_D, s);   // (timing experiments only: the pass that writes xh was skipped)
     if (m->ort) {
         // ConvASRDecoder is a 1x1 Conv1d in the exported graph: DynamicQuantizeLinear on the encoder output, ConvInteger
-        launch_rows_minmax(m->x, M, m->row_map, mm_site(MM_HEAD), s);
-        launch_quant_rows(m->x, M, QV_D, RowOwner{m->row_map, nullptr, 0, 0}, mm_site(MM_HEAD), m->q8, s);
-        GemmArgs a = {};
-        a.A = (const half_t *)m->q8; a.Wi8 = m->o_head.wq; a.wsum = m->o_head.wsum; a.w_scale = m->o_head.scale; a.bias = m->head_b;
-        a.out = m->logits; a.M = M; a.N = HEAD_N; a.K = QV_D / 2; a.lda = QV_D / 2; a.ldw = QV_D / 2; a.ldo = HEAD_N; a.alpha = 1.f;
-        a.row_map = m->row_map; a.mm_in = mm_site(MM_HEAD);
-        launch_gemm(EPI_F32, a, s);
+        launch_rows_minmax(a.x, M, a.row_map, mm_site(MM_HEAD), s);
+        launch_quant_rows(a.x, M, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_site(MM_HEAD), a.q8, s);
+        GemmArgs g = {};
+        g.A = (const half_t *)a.q8; g.Wi8 = m->o_head.wq; g.wsum = m->o_head.wsum; g.w_scale = m->o_head.scale; g.bias = m->head_b;
+        g.out = a.logits; g.M = M; g.N = HEAD_N; g.K = QV_D / 2; g.lda = QV_D / 2; g.ldw = QV_D / 2; g.ldo = HEAD_N; g.alpha = 1.f;
+        g.row_map = a.row_map; g.mm_in = mm_site(MM_HEAD);
+        launch_gemm(EPI_F32, g, s);
     } else {
-        GemmArgs a = {};
-        a.A = m->xh; a.W = m->head_w; a.bias = m->head_b; a.out = m->logits;
-        a.M = M; a.N = HEAD_N; a.K = QV_D; a.lda = QV_D; a.ldw = QV_D; a.ldo = HEAD_N; a.alpha = 1.f;
-        launch_gemm(EPI_F32, a, s);
+        GemmArgs g = {};
+        g.A = a.xh; g.W = m->head_w; g.bias = m->head_b; g.out = a.logits;
+        g.M = M; g.N = HEAD_N; g.K = QV_D; g.lda = QV_D; g.ldw = QV_D; g.ldo = HEAD_N; g.alpha = 1.f;
+        launch_gemm(EPI_F32, g, s);
     }
     // packed logits -> the caller's dense [B][t_max_out][1025] log-prob tensor (valid frames only)
-    launch_logsoftmax(m->logits, HEAD_N, logprobs, M, m->row_map, t_max_out, s);
+    launch_logsoftmax(a.logits, HEAD_N, logprobs, M, a.row_map, t_max_out, s);
     if (zero_pad_rows) launch_zero_pad_rows(logprobs, d_l3, t_max_out, t_min_pad, B, s);
     return QV_OK;
     };
@@ -1037,25 +1011,24 @@ int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64
     if (qv_kernel_variant(QV_KV_FWD_GRAPH) == 1 && may_graph && !m->save_taps && !eng->profile_stages && !qv_gemm_prof_on()) {
         // (the GEMM tile policy is host state that picks kernels: its epoch is part of the key, so a graph captured under
         // another policy is never replayed after qv_debug_gemm_tiles / QVERSE_GEMM_* changed it)
-        QvModel::FwdKey key = {audio, logprobs, posp, n_max,
-                               {B, M, T, t3min, tm_max, t1m, t2m, t_max_out, t_min_pad, att_variant,
-                                qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB), qv_gemm_policy_epoch()}};
-        const int k = m->cur_ctx;
-        const int64_t tick = ++m->fwd_tick[k];
-        QvModel::FwdGraph *hit = nullptr;
-        for (int i = 0; i < m->n_fwd_graph[k]; ++i)
-            if (m->fwd_graph[k][i].key == key) hit = &m->fwd_graph[k][i];
+        FwdKey key = {audio, logprobs, posp, n_max,
+                      {B, M, T, t3min, tm_max, t1m, t2m, t_max_out, t_min_pad, att_variant,
+                       qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB), qv_gemm_policy_epoch()}};
+        const int64_t tick = ++a.fwd_tick;
+        FwdGraph *hit = nullptr;
+        for (int i = 0; i < a.n_fwd_graph; ++i)
+            if (a.fwd_graph[i].key == key) hit = &a.fwd_graph[i];
         bool seen = false;
-        for (const QvModel::FwdKey &o : m->fwd_seen[k]) seen = seen || o == key;
+        for (const FwdKey &o : a.fwd_seen) seen = seen || o == key;
         if (!hit && !seen) {
-            m->fwd_seen[k][m->fwd_seen_at[k]] = key;
-            m->fwd_seen_at[k] = (m->fwd_seen_at[k] + 1) % QV_FWD_GRAPHS;
+            a.fwd_seen[a.fwd_seen_at] = key;
+            a.fwd_seen_at = (a.fwd_seen_at + 1) % QV_FWD_GRAPHS;
         }
         // a full context replaces its LEAST RECENTLY USED graph, and at most once per 2 * QV_FWD_GRAPHS forwards: a loop
         // over more recurring shapes than slots must not pay a capture + instantiate + stream synchronise per cycle
         // (it keeps replaying the shapes it holds and runs the others as plain launches)
-        const bool full = m->n_fwd_graph[k] >= QV_FWD_GRAPHS;
-        const bool may_capture = !m->fwd_disabled[k] && (full ? (seen && tick - m->fwd_last_capture[k] >= 2 * QV_FWD_GRAPHS) : true);
+        const bool full = a.n_fwd_graph >= QV_FWD_GRAPHS;
+        const bool may_capture = !a.fwd_disabled && (full ? (seen && tick - a.fwd_last_capture >= 2 * QV_FWD_GRAPHS) : true);
         bool ran_plain = false;
         if (!hit && may_capture) {
             hipGraph_t graph = nullptr;
@@ -1075,24 +1048,24 @@ int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64
             }
             if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || !exec) {
                 (void)hipGetLastError();
-                m->fwd_disabled[k] = true;
+                a.fwd_disabled = true;
                 m->fwd_capture_failures++;
                 TRY(launch_all());
                 ran_plain = true;
             } else {
-                int slot = m->n_fwd_graph[k];
-                if (!full) m->n_fwd_graph[k]++;
+                int slot = a.n_fwd_graph;
+                if (!full) a.n_fwd_graph++;
                 else {
                     slot = 0;
                     for (int i = 1; i < QV_FWD_GRAPHS; ++i)
-                        if (m->fwd_graph[k][i].last_use < m->fwd_graph[k][slot].last_use) slot = i;
+                        if (a.fwd_graph[i].last_use < a.fwd_graph[slot].last_use) slot = i;
                     QV_HIP(hipStreamSynchronize(s));   // its last replay may still be queued on this stream (rate-limited above)
-                    (void)hipGraphExecDestroy(m->fwd_graph[k][slot].exec);
+                    (void)hipGraphExecDestroy(a.fwd_graph[slot].exec);
                 }
-                m->fwd_graph[k][slot] = {key, exec, tick};
-                m->fwd_last_capture[k] = tick;
+                a.fwd_graph[slot] = {key, exec, tick};
+                a.fwd_last_capture = tick;
                 m->fwd_captures++;
-                hit = &m->fwd_graph[k][slot];
+                hit = &a.fwd_graph[slot];
             }
         }
         if (hit) { QV_HIP(hipGraphLaunch(hit->exec, s)); hit->last_use = tick; m->fwd_replays++; }
@@ -1101,7 +1074,7 @@ int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64
         TRY(launch_all());
     }
     QV_HIP(hipGetLastError());
-    m->last_batch = B; m->last_tmax = T; m->last_tm_max = tm_max; m->last_rows = M; m->last_t2m = t2m;
+    a.last_batch = B; a.last_tmax = T; a.last_tm_max = tm_max; a.last_rows = M; a.last_t2m = t2m;
     return QV_OK;
 }
 
@@ -1110,30 +1083,31 @@ int qv_model_forward(qv_engine *eng, QvModel *m, const float *audio, const int64
 // which: 0 FFN-up (N 2048, K 512, Swish), 1 FFN-down (N 512, K 2048, residual), 2 QKV, 3 attention
 // out-projection, 4 pointwise-conv + GLU.  The residual variants run with alpha = 0 so replaying
 // them does not disturb the stream.
-static int replay_args(qv_engine *eng, QvModel *m, int which, GemmArgs &a, int &epi) {
-    int M = m->last_rows;
+static int replay_args(qv_engine *eng, QvModel *m, int k, int which, GemmArgs &g, int &epi) {
+    QvActs &a = m->ctx_acts[k];
+    int M = a.last_rows;
     if (M <= 0) { qv_set_error(eng, "replay needs a previous forward"); return QV_ERR_ARG; }
     const LayerW &L = m->L[0];
-    a = GemmArgs{};
-    a.M = M; a.out2 = m->vt; a.t_max = m->last_tmax; a.t_pad = (m->last_tmax + 31) / 32 * 32; a.alpha = 1.f;
-    a.row_map = m->row_map; a.in_flight = m->n_ctx;
+    g = GemmArgs{};
+    g.M = M; g.out2 = a.vt; g.t_max = a.last_tmax; g.t_pad = (a.last_tmax + 31) / 32 * 32; g.alpha = 1.f;
+    g.row_map = a.row_map; g.in_flight = m->n_ctx;
     const WMat *W;
     switch (which) {
-        case 0: epi = EPI_F16_SWISH; a.A = m->ln; W = &L.ff1_w1; a.bias = L.ff1_b1; a.out = m->hbuf; a.N = QV_FF; a.K = QV_D; a.ldo = QV_FF; break;
-        case 1: epi = EPI_RESID; a.A = m->hbuf; W = &L.ff1_w2; a.bias = L.ff1_b2; a.out = m->x; a.N = QV_D; a.K = QV_FF; a.ldo = QV_D; a.alpha = 0.f; break;
-        case 2: epi = EPI_QKV; a.A = m->ln; W = &L.qkv_w; a.bias = L.qkv_b; a.out = m->qk; a.N = 3 * QV_D; a.K = QV_D; a.ldo = 2 * QV_D; break;
-        case 3: epi = EPI_RESID; a.A = m->att; W = &L.out_w; a.bias = L.out_b; a.out = m->x; a.N = QV_D; a.K = QV_D; a.ldo = QV_D; a.alpha = 0.f; break;
-        case 4: epi = EPI_GLU; a.A = m->ln; W = &L.pw1_w; a.bias = L.pw1_b; a.out = m->glu; a.N = 2 * QV_D; a.K = QV_D; a.ldo = QV_D; break;
+        case 0: epi = EPI_F16_SWISH; g.A = a.ln; W = &L.ff1_w1; g.bias = L.ff1_b1; g.out = a.hbuf; g.N = QV_FF; g.K = QV_D; g.ldo = QV_FF; break;
+        case 1: epi = EPI_RESID; g.A = a.hbuf; W = &L.ff1_w2; g.bias = L.ff1_b2; g.out = a.x; g.N = QV_D; g.K = QV_FF; g.ldo = QV_D; g.alpha = 0.f; break;
+        case 2: epi = EPI_QKV; g.A = a.ln; W = &L.qkv_w; g.bias = L.qkv_b; g.out = a.qk; g.N = 3 * QV_D; g.K = QV_D; g.ldo = 2 * QV_D; break;
+        case 3: epi = EPI_RESID; g.A = a.att; W = &L.out_w; g.bias = L.out_b; g.out = a.x; g.N = QV_D; g.K = QV_D; g.ldo = QV_D; g.alpha = 0.f; break;
+        case 4: epi = EPI_GLU; g.A = a.ln; W = &L.pw1_w; g.bias = L.pw1_b; g.out = a.glu; g.N = 2 * QV_D; g.K = QV_D; g.ldo = QV_D; break;
         default: return QV_ERR_ARG;
     }
-    a.W = W->w; a.Wq = W->q; a.wscale = W->sc; a.W8 = W->q8; a.w8scale = W->sc8;
-    a.lda = a.K; a.ldw = a.K;
+    g.W = W->w; g.Wq = W->q; g.wscale = W->sc; g.W8 = W->q8; g.w8scale = W->sc8;
+    g.lda = g.K; g.ldw = g.K;
     if (which == 4 && m->ort) {
         // QV_PREC_ORT_MIXED: this GEMM is the A8W8 one (s8 operands left in q8 by the last forward; K counts byte pairs);
         // the range it folds into the GLU site is the one the last forward already left there
-        a.A = (const half_t *)m->q8; a.W = nullptr; a.Wi8 = L.o_pw1.wq; a.wsum = L.o_pw1.wsum; a.w_scale = L.o_pw1.scale;
-        a.out = m->gluf; a.K = QV_D / 2; a.lda = a.ldw = QV_D / 2;
-        a.mm_in = m->mm + (size_t)MM_LAYER(0) * m->max_batch * QV_MM_STRIDE; a.mm_out = (uint32_t *)a.mm_in + (size_t)m->max_batch * QV_MM_STRIDE;
+        g.A = (const half_t *)a.q8; g.W = nullptr; g.Wi8 = L.o_pw1.wq; g.wsum = L.o_pw1.wsum; g.w_scale = L.o_pw1.scale;
+        g.out = a.gluf; g.K = QV_D / 2; g.lda = g.ldw = QV_D / 2;
+        g.mm_in = a.mm + (size_t)MM_LAYER(0) * m->max_batch * QV_MM_STRIDE; g.mm_out = (uint32_t *)g.mm_in + (size_t)m->max_batch * QV_MM_STRIDE;
     }
     return QV_OK;
 }
@@ -1154,27 +1128,27 @@ void qv_model_weights_info(const QvModel *m, char *out, int cap) {
                  m->ort ? "; Conv weights on the file's int8 integers" : m->w4 ? "; pointwise-conv weights as dequantised f16 values" : "");
 }
 
-int qv_model_replay_kernel(qv_engine *eng, QvModel *m, int which, char *name_out, int cap) {
-    GemmArgs a;
+int qv_model_replay_kernel(qv_engine *eng, QvModel *m, int k, int which, char *name_out, int cap) {
+    GemmArgs g;
     int epi = 0;
-    int rc = replay_args(eng, m, which, a, epi);
+    int rc = replay_args(eng, m, k, which, g, epi);
     if (rc != QV_OK) return rc;
-    snprintf(name_out, (size_t)cap, "%s", qv_gemm_kernel_name(epi, a));
+    snprintf(name_out, (size_t)cap, "%s", qv_gemm_kernel_name(epi, g));
     return QV_OK;
 }
 
-int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int which, int iters, double *avg_us, double *flops, hipStream_t s) {
+int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int k, int which, int iters, double *avg_us, double *flops, hipStream_t s) {
     if (iters < 1) return QV_ERR_ARG;
-    GemmArgs a;
+    GemmArgs g;
     int epi = 0;
-    int rc = replay_args(eng, m, which, a, epi);
+    int rc = replay_args(eng, m, k, which, g, epi);
     if (rc != QV_OK) return rc;
     hipEvent_t e0, e1;
     QV_HIP(hipEventCreate(&e0));
     QV_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) launch_gemm(epi, a, s);
+    for (int i = 0; i < 3; ++i) launch_gemm(epi, g, s);
     QV_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) launch_gemm(epi, a, s);
+    for (int i = 0; i < iters; ++i) launch_gemm(epi, g, s);
     QV_HIP(hipEventRecord(e1, s));
     QV_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -1182,41 +1156,42 @@ int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int which, int iters, doubl
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     *avg_us = (double)ms * 1e3 / iters;
-    *flops = 2.0 * (double)a.M * (double)a.N * (double)a.K * (a.Wi8 ? 2.0 : 1.0);   // (A8W8: K counts byte pairs)
+    *flops = 2.0 * (double)g.M * (double)g.N * (double)g.K * (g.Wi8 ? 2.0 : 1.0);   // (A8W8: K counts byte pairs)
     return QV_OK;
 }
 
-int qv_model_tap(qv_engine *eng, QvModel *m, int what, int layer, float *out, hipStream_t s) {
-    size_t M = (size_t)m->last_rows;
+int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *out, hipStream_t s) {
+    QvActs &a = m->ctx_acts[k];
+    size_t M = (size_t)a.last_rows;
     if (what == 0) {
         // normalised features are never materialised on the fast path (conv0 normalises on load)
-        launch_melapply(m->feats, m->lens_dev, m->last_tm_max, m->mel_stats, out, m->last_batch, s);
+        launch_melapply(a.feats, a.lens_dev, a.last_tm_max, a.mel_stats, out, a.last_batch, s);
     } else if (what == 10) {   // the log-mel features as k_logmel left them, [B][tm_max][80]
-        QV_HIP(hipMemcpyAsync(out, m->feats, sizeof(float) * (size_t)m->last_batch * m->last_tm_max * QV_NMEL, hipMemcpyDeviceToDevice, s));
+        QV_HIP(hipMemcpyAsync(out, a.feats, sizeof(float) * (size_t)a.last_batch * a.last_tm_max * QV_NMEL, hipMemcpyDeviceToDevice, s));
     } else if (what >= 6 && what <= 9) {
         // QV_PREC_ORT_MIXED: the dense subsampling tensors in front of / behind the quantisers, as they sit in HBM
         if (!m->ort) { qv_set_error(eng, "taps 6..9 exist under QV_PREC_ORT_MIXED only"); return QV_ERR_ARG; }
-        const size_t B = (size_t)m->last_batch;
-        if (what == 6) QV_HIP(hipMemcpyAsync(out, m->c1f, sizeof(float) * B * m->last_t2m * 20 * QV_SUBC, hipMemcpyDeviceToDevice, s));
-        if (what == 7) QV_HIP(hipMemcpyAsync(out, m->c1pf, sizeof(float) * B * m->last_t2m * 20 * QV_SUBC, hipMemcpyDeviceToDevice, s));
-        if (what == 8) QV_HIP(hipMemcpyAsync(out, m->c2f, sizeof(float) * B * m->last_tmax * 10 * QV_SUBC, hipMemcpyDeviceToDevice, s));
-        if (what == 9) launch_to_float(m->c2p, out, B * m->last_tmax * 10 * QV_SUBC, s);
+        const size_t B = (size_t)a.last_batch;
+        if (what == 6) QV_HIP(hipMemcpyAsync(out, a.c1f, sizeof(float) * B * a.last_t2m * 20 * QV_SUBC, hipMemcpyDeviceToDevice, s));
+        if (what == 7) QV_HIP(hipMemcpyAsync(out, a.c1pf, sizeof(float) * B * a.last_t2m * 20 * QV_SUBC, hipMemcpyDeviceToDevice, s));
+        if (what == 8) QV_HIP(hipMemcpyAsync(out, a.c2f, sizeof(float) * B * a.last_tmax * 10 * QV_SUBC, hipMemcpyDeviceToDevice, s));
+        if (what == 9) launch_to_float(a.c2p, out, B * a.last_tmax * 10 * QV_SUBC, s);
     } else {
         if (!m->save_taps) { qv_set_error(eng, "set QVERSE_DEBUG_TAPS=1 before creating the engine"); return QV_ERR_ARG; }
         const float *src = nullptr;
         if (what == 1 || what == 2) {
             int idx = what == 1 ? 0 : layer + 1;
             if (idx < 0 || idx > N_LAYERS) return QV_ERR_ARG;
-            src = m->tap_x + (size_t)idx * M * QV_D;
+            src = a.tap_x + (size_t)idx * M * QV_D;
         } else if (what >= 3 && what <= 5) {
             if (!m->ort || layer < 0 || layer >= N_LAYERS) { qv_set_error(eng, "taps 3..5 exist under QV_PREC_ORT_MIXED only"); return QV_ERR_ARG; }
-            src = (what == 3 ? m->tap_lnc : what == 4 ? m->tap_glu : m->tap_dw) + (size_t)layer * M * QV_D;
+            src = (what == 3 ? a.tap_lnc : what == 4 ? a.tap_glu : a.tap_dw) + (size_t)layer * M * QV_D;
         } else return QV_ERR_ARG;
         // unpack to the dense [B][t_max][512] view the tests read (padding frames zero)
-        const int T = m->last_tmax;
-        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)m->last_batch * T * QV_D, s));
-        for (int b = 0; b < m->last_batch; ++b) {
-            const int32_t *off = m->lens_host + (size_t)m->lens_last * (m->max_batch * 6 + 1) + 5 * m->max_batch;   // this context's last forward
+        const int T = a.last_tmax;
+        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)a.last_batch * T * QV_D, s));
+        for (int b = 0; b < a.last_batch; ++b) {
+            const int32_t *off = a.lens_host + (size_t)a.lens_last * (m->max_batch * 6 + 1) + 5 * m->max_batch;   // this context's last forward
             int r0 = off[b], n = off[b + 1] - r0;
             QV_HIP(hipMemcpyAsync(out + (size_t)b * T * QV_D, src + (size_t)r0 * QV_D,
                                   sizeof(float) * (size_t)n * QV_D, hipMemcpyDeviceToDevice, s));

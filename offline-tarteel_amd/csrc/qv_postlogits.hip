@@ -2129,9 +2129,9 @@ __global__ void k_track_final(QvTables tab, QvTrack tw, int batch, int nblk) {
 
 // ====================================================================== host side =======
 
-static int launch_retrieval(qv_engine *eng, int batch, int force_ctc, hipStream_t stream) {
+static int launch_retrieval(qv_engine *eng, QvCtx &c, int batch, int force_ctc, hipStream_t stream) {
     QvTables &tab = eng->tab;
-    QvWork &wk = eng->work;
+    QvWork &wk = c.work;
     QvKnobs kn = eng->knobs;
     int N = tab.n_verses;
     size_t sm_tri = (size_t)N * 8 + 8 * 8 + 8 * 8 + 64 * 4 + 512 * 4 + 272 * 4 + 128 * 8 + 64 * 4 + TRI_WORDS * 4 +
@@ -2152,9 +2152,9 @@ static int launch_retrieval(qv_engine *eng, int batch, int force_ctc, hipStream_
     return QV_OK;
 }
 
-int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_host, int batch, hipStream_t stream) {
+int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int32_t *t_host, int batch, hipStream_t stream) {
     QvTables &tab = eng->tab;
-    QvWork &wk = eng->work;
+    QvWork &wk = c.work;
     if (batch > wk.max_batch || t_max > wk.t_cap) {
         qv_set_error(eng, "batch or frame count exceeds engine capacity");
         return QV_ERR_CAPACITY;
@@ -2163,13 +2163,12 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
         if (t_host[b] < 0 || t_host[b] > t_max) { qv_set_error(eng, "t_host[b] out of range"); return QV_ERR_ARG; }
     {
         // pinned staging slot: wait for the copy that last read it (two calls ago), never for the stream
-        QvCtx &c = eng->ctx[eng->cur_ctx];
         const int slot = c.t_slot;
         c.t_slot = (slot + 1) % QV_STAGE_SLOTS;
         if (c.t_pending[slot]) { QV_HIP(hipEventSynchronize(c.t_copied[slot])); c.t_pending[slot] = false; }
-        int32_t *th = eng->t_host_scratch + (size_t)slot * wk.max_batch;
+        int32_t *th = c.t_host_scratch + (size_t)slot * wk.max_batch;
         for (int b = 0; b < batch; ++b) th[b] = t_host[b];
-        QV_HIP(hipMemcpyAsync(eng->t_dev, th, sizeof(int32_t) * batch, hipMemcpyHostToDevice, stream));
+        QV_HIP(hipMemcpyAsync(c.t_dev, th, sizeof(int32_t) * batch, hipMemcpyHostToDevice, stream));
         QV_HIP(hipEventRecord(c.t_copied[slot], stream));
         c.t_pending[slot] = true;
     }
@@ -2180,11 +2179,11 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
 #endif
     auto launch_chain = [&]() -> int {
         if (skip & 128) return QV_OK;   // (timing experiments only: no post-logits chain at all)
-        hipLaunchKernelGGL(k_decode, dim3(batch), dim3(64 * DEC_WAVES), 0, stream, tab, wk, lp, t_max, eng->t_dev);
-        qv_stage_mark(eng, 2, stream);
-        int rc = launch_retrieval(eng, batch, 0, stream);
+        hipLaunchKernelGGL(k_decode, dim3(batch), dim3(64 * DEC_WAVES), 0, stream, tab, wk, lp, t_max, c.t_dev);
+        qv_stage_mark(eng, c, 2, stream);
+        int rc = launch_retrieval(eng, c, batch, 0, stream);
         if (rc) return rc;
-        qv_stage_mark(eng, 3, stream);
+        qv_stage_mark(eng, c, 3, stream);
         if (skip & 16) { }
         // the long-target variant (up to 768 states per candidate: 12 state registers per lane, 3 KB of LDS per wave) only when
         // THIS batch has a clip of more than 384 frames -- not whenever the engine COULD hold one: an engine created for
@@ -2197,7 +2196,7 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
         else if (t_max > 384) hipLaunchKernelGGL((k_ctc<true, 1>), dim3(batch, 64), dim3(256), 0, stream, tab, wk, eng->knobs, lp, t_max);
         else hipLaunchKernelGGL((k_ctc<false, 1>), dim3(batch, 64), dim3(256), 0, stream, tab, wk, eng->knobs, lp, t_max);
         hipLaunchKernelGGL(k_result, dim3(batch), dim3(256), 0, stream, tab, wk, batch);
-        qv_stage_mark(eng, 4, stream);
+        qv_stage_mark(eng, c, 4, stream);
         return QV_OK;
     };
     // One graph launch for the whole chain when its arguments are the ones a graph was captured with: the
@@ -2210,17 +2209,16 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
     // (4.26 vs 4.13 ms per step, within box noise) -- kernel boundaries cost the same inside a graph, and the
     // host's ~3.5 us per launch is not what limits the step.
     static const bool use_graph = [] { const char *e = getenv("QVERSE_POST_GRAPH"); return e && atoi(e) != 0; }();
-    QvCtx &gc = eng->ctx[eng->cur_ctx];
-    if (use_graph && !gc.post_graph_off && eng->n_ctx > 1 && stream == gc.stream && lp == eng->logprobs_ws && !eng->profile_stages) {
+    if (use_graph && !c.post_graph_off && eng->n_ctx > 1 && stream == c.stream && lp == c.logprobs_ws && !eng->profile_stages) {
         // (the kernel variants that pick launches inside the chain are part of the key: a graph captured under another span pass
         // or CTC wave program must not be replayed after qv_debug_kernel_variant changed it)
         const int variants = qv_kernel_variant(QV_KV_SPANS) | (qv_kernel_variant(QV_KV_CTC) << 4) | ((QV_MAXW > 16) << 8);
         QvCtx::PostGraph *hit = nullptr;
-        for (int i = 0; i < gc.n_post_graph; ++i)
-            if (gc.post_graph[i].lp == lp && gc.post_graph[i].batch == batch && gc.post_graph[i].t_max == t_max && gc.post_graph[i].variants == variants)
-                hit = &gc.post_graph[i];
+        for (int i = 0; i < c.n_post_graph; ++i)
+            if (c.post_graph[i].lp == lp && c.post_graph[i].batch == batch && c.post_graph[i].t_max == t_max && c.post_graph[i].variants == variants)
+                hit = &c.post_graph[i];
         bool ran_plain = false;
-        if (!hit && gc.n_post_graph < 4) {
+        if (!hit && c.n_post_graph < 4) {
             hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
             // as for the forward graph: a failure of the capture machinery is not a failure of the batch
@@ -2234,13 +2232,13 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
             }
             if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || !exec) {
                 (void)hipGetLastError();
-                gc.post_graph_off = true;
+                c.post_graph_off = true;
                 int rc = launch_chain();
                 if (rc) return rc;
                 ran_plain = true;
             } else {
-                gc.post_graph[gc.n_post_graph] = {lp, batch, t_max, variants, exec};
-                hit = &gc.post_graph[gc.n_post_graph++];
+                c.post_graph[c.n_post_graph] = {lp, batch, t_max, variants, exec};
+                hit = &c.post_graph[c.n_post_graph++];
             }
         }
         if (hit) {
@@ -2254,20 +2252,20 @@ int qv_post_run(qv_engine *eng, const float *lp, int t_max, const int32_t *t_hos
         if (rc) return rc;
     }
     QV_HIP(hipGetLastError());
-    eng->last_batch = batch;
-    eng->last_tmax = t_max;
+    c.last_batch = batch;
+    c.last_tmax = t_max;
     return QV_OK;
 }
 
-int qv_post_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int n, hipStream_t stream) {
-    QvWork &wk = eng->work;
+int qv_post_debug_retrieve(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, hipStream_t stream) {
+    QvWork &wk = c.work;
     if (n > QV_MAXQ) { qv_set_error(eng, "transcript longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     int32_t zero = 0;
-    QV_HIP(hipMemcpyAsync(eng->t_dev, &zero, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_init_utts, dim3(1), dim3(64), 0, stream, wk, eng->t_dev, 1);
+    QV_HIP(hipMemcpyAsync(c.t_dev, &zero, sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_init_utts, dim3(1), dim3(64), 0, stream, wk, c.t_dev, 1);
     if (n > 0) QV_HIP(hipMemcpyAsync(wk.q, codes_host, n, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_prepare_codes, dim3(1), dim3(64), 0, stream, wk, n);
-    int rc = launch_retrieval(eng, 1, 1, stream);
+    int rc = launch_retrieval(eng, c, 1, 1, stream);
     if (rc) return rc;
     QV_HIP(hipGetLastError());
     QV_HIP(hipStreamSynchronize(stream));
@@ -2329,16 +2327,16 @@ int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32
 
 // match_verse(text, max_span, hint, use_trigram_index=False) (quran_db.py:244-371): full scan,
 // continuation bonuses, span pass; result in utt[0].base_* (SYNCHRONOUS).
-int qv_post_match_verse(qv_engine *eng, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
+int qv_post_match_verse(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
                         const double *bonus_value, int max_span, hipStream_t stream) {
     QvTables &tab = eng->tab;
-    QvWork &wk = eng->work;
+    QvWork &wk = c.work;
     QvKnobs kn = eng->knobs;
     kn.max_span = max_span;
     const int N = tab.n_verses;
     int32_t zero = 0;
-    QV_HIP(hipMemcpyAsync(eng->t_dev, &zero, sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_init_utts, dim3(1), dim3(64), 0, stream, wk, eng->t_dev, 1);
+    QV_HIP(hipMemcpyAsync(c.t_dev, &zero, sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_init_utts, dim3(1), dim3(64), 0, stream, wk, c.t_dev, 1);
     if (n > 0) QV_HIP(hipMemcpyAsync(wk.q, codes_host, n, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_prepare_codes, dim3(1), dim3(64), 0, stream, wk, n);
     int hv[3] = {-1, -1, -1};

@@ -277,7 +277,18 @@ def test_batches_in_flight_equal_one_at_a_time(setup):
         for rep in range(2):
             tickets = [eng.predict_batch_async(a, l) for a, l in batches[:3]]
             assert tickets == [(3 * rep + i) % 3 for i in range(3)] or len(set(tickets)) == 3
-            got = [eng.fetch_results(t, a.shape[0], eng.frames_for(max(l))) for t, (a, l) in zip(tickets, batches[:3])]
+            # the second repetition fetches the three tickets in reverse order: a fetch reads its own context, whichever
+            # context ran last and whatever was fetched before
+            order = [0, 1, 2] if rep == 0 else [2, 1, 0]
+            got = [None] * 3
+            for i in order:
+                got[i] = eng.fetch_results(tickets[i], batches[i][0].shape[0], eng.frames_for(max(batches[i][1])))
+            # fetching moves nothing: the last context is still the last ticket handed out, and the calls without a
+            # context argument act on it
+            assert eng.lib.qv_last_context(eng.h) == tickets[2]
+            pk = eng.packed_results(1).cpu()
+            assert pk[:, :2].tolist() == [[want[2][0]["surah"], want[2][0]["ayah"]]]
+            assert torch.equal(pk, eng.packed_results(1, tickets[2]).cpu())
             # a 4th and 5th call reuse contexts 0 and 1 (the host waits for them if still busy)
             t3 = eng.predict_batch_async(*batches[3])
             t4 = eng.predict_batch_async(*batches[4])
