@@ -291,7 +291,7 @@ struct QvModel {
     const float *o_dw2_b, *o_dw5_b;
     LayerW L[N_LAYERS];
     // capacities
-    int max_batch, tm_cap, t1_cap, t2_cap, t3_cap;
+    int max_batch, max_samples, tm_cap, t1_cap, t2_cap, t3_cap;
     std::map<int, half_t *> pos_cache;  // t_max -> projected positions f16 [2*t_max-1][17*512]
     bool save_taps;
     // forward graphs of all contexts together (qv_debug_forward_graph_stats / _failures): graph launches, captures, and
@@ -753,6 +753,7 @@ int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out) {
     TRY(prepare_weights(eng, m, hw));
     int B = cfg->max_batch;
     m->max_batch = B;
+    m->max_samples = cfg->max_samples;
     m->tm_cap = cfg->max_samples / 160 + 1;
     m->t1_cap = stage_len(m->tm_cap);
     m->t2_cap = stage_len(m->t1_cap);
@@ -801,7 +802,7 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
     int32_t *lh = a.lens_host + (size_t)slot * (MB * 6 + 1);
     for (int b = 0; b < B; ++b) {
         int64_t n = len_host[b];
-        if (n < 400 || n > n_max || n / 160 + 1 > m->tm_cap) {
+        if (n < 400 || n > n_max || n > m->max_samples) {   // (samples, not mel frames: up to 159 samples more would still fit tm_cap)
             qv_set_error(eng, "utterance length out of range (need 400 <= n <= capacity)");
             return QV_ERR_CAPACITY;
         }

@@ -62,3 +62,16 @@ def oracle_floor(R, w, audio, lens, lp_ref, T, threads: int | None = None, seeds
         rows["f16_linear_inputs"] = delta(R.forward(w, audio, lens, ort=make_f16_input_ops(R, **ort_kw))[0], lp_ref, T)
     return {"max": max(r[0] for r in rows.values()), "rms": max(r[1] for r in rows.values()),
             "argmax": min(r[2] for r in rows.values()), "rows": rows}
+
+
+FLOOR_K = 1.5   # device-vs-oracle may be at most this many times the oracle's distance from itself on the same clip
+
+
+def _assert_on_the_floor(tag, got, floor):
+    mx, rms, same = got
+    print(f"[ort-e2e] {tag}: hip vs OrtMixed max {mx:.4f} rms {rms:.5f} argmax {same:.4f} | oracle vs itself: max {floor['max']:.4f} "
+          f"rms {floor['rms']:.5f} argmax {floor['argmax']:.4f}  ({', '.join(f'{k} {v[0]:.4f}/{v[1]:.5f}' for k, v in floor['rows'].items())})")
+    # within north_star's 1e-2 outright, or within FLOOR_K x what the reference's arithmetic reproduces of itself
+    assert mx <= max(FLOOR_K * floor["max"], 1e-2), (tag, mx, floor["max"])
+    assert rms <= max(FLOOR_K * floor["rms"], 2.5e-3), (tag, rms, floor["rms"])
+    assert same >= floor["argmax"] - 0.03, (tag, same, floor["argmax"])

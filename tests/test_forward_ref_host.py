@@ -1,0 +1,128 @@
+"""The premises of tests/test_gpu_forward_lengths.py, checked with the reference alone (CPU, oracle/fastconformer_ref.py):
+the f16-operand twin's distance `e` from the fp32 restatement is below 1e-2 on the "sharp attention" weights and within
+2x of what it is on the plain ones, the two planted errors stand out of the bound there (and the position error does
+NOT on the plain weights -- the gap those tests close), the structured set's argmax condition leaves (almost) no frame
+out, and the oracle is batch-invariant, so one padded call serves a ragged device batch."""
+
+import pytest
+import torch
+
+import forward_ref as FR
+from oracle import fastconformer_ref as R
+
+SEED = 7
+FRAMES = [1, 33, 129, 257]          # the ladder's shortest and longest clip and two in between, cut from the ladder's audio
+CHECKED = [1, 2, 3]                 # rows of T = 33, 129, 257
+
+
+@pytest.fixture(scope="module")
+def refs():
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    ladder = [FR.samples_for_frames(t) for t in FR.LADDER]
+    rows = [FR.LADDER.index(t) for t in FRAMES]
+    lens = [ladder[r] for r in rows]
+    audio = FR.clips(ladder, FR.LADDER_AUDIO_SEED)[rows][:, : max(lens)].contiguous()
+    plain = R.random_weights(SEED)
+    sharp = FR.sharp_weights(plain)
+    out = dict(audio=audio, lens=lens, plain_w=plain, sharp_w=sharp,
+               sharp=FR.reference(sharp, audio, lens), plain=FR.reference(plain, audio, lens))
+    assert out["sharp"]["t"] == FRAMES
+    return out
+
+
+def test_sharp_weights_touch_the_query_side_only(refs):
+    changed = [k for k in refs["plain_w"] if not torch.equal(refs["plain_w"][k], refs["sharp_w"][k])]
+    assert len(changed) == 4 * R.N_LAYERS and all(k.endswith(FR.SHARP_SUFFIXES) for k in changed)
+    for k in changed:
+        assert torch.equal(refs["sharp_w"][k], refs["plain_w"][k] * 4.0)
+
+
+def test_twin_distance_is_a_fair_floor_on_the_sharp_set(refs):
+    """the premise that 1e-2 is a meaningful bound on the sharp set: gain 4 does not move the f16-operand floor"""
+    for b in CHECKED:
+        e4, e1 = refs["sharp"]["e"][b], refs["plain"]["e"][b]
+        print(f"[fwd-ref] T={FRAMES[b]}: e sharp {e4:.3e}  plain {e1:.3e}")
+        assert 0.0 < e4 < 1e-2, (FRAMES[b], e4)
+        assert 0.0 < e1 < 1e-2, (FRAMES[b], e1)
+        assert max(e4, e1) < 2.0 * min(e4, e1), (FRAMES[b], e4, e1)
+
+
+def test_planted_errors_stand_out_on_the_sharp_set_and_hide_on_the_plain_one(refs):
+    audio, lens = refs["audio"], refs["lens"]
+    bad = FR.planted(refs["sharp_w"], audio, lens, CHECKED)
+    for b in CHECKED:
+        n, bound = FRAMES[b], refs["sharp"]["bound"][b]
+        d_pos = FR.maxdiff(bad["positions"][b], refs["sharp"]["lp"][b], n)
+        d_last = FR.maxdiff(bad["last_frame"][b], refs["sharp"]["lp"][b], n - 1)     # all frames but the last
+        print(f"[fwd-ref] sharp T={n}: positions off by one {d_pos:.3f}, last frame dropped {d_last:.3f}, bound (a) {bound:.3e}")
+        assert d_pos >= 4.0 * bound, (n, d_pos, bound)
+        assert d_last >= 4.0 * bound, (n, d_last, bound)
+    # The gap: on the plain random weights a position off-by-one moves the log-probs by LESS than the 1e-2 every oracle
+    # comparison grants.  If this ever fails the plain weights have become sensitive enough to the position term, and
+    # the sharp set is no longer the only place where such an error shows.
+    with FR.positions_off_by_one():
+        lp, _ = R.forward(refs["plain_w"], audio, lens)
+    for b in (2, 3):
+        d = FR.maxdiff(lp[b], refs["plain"]["lp"][b], FRAMES[b])
+        print(f"[fwd-ref] plain T={FRAMES[b]}: positions off by one {d:.4f}")
+        assert 0.0 < d < 1e-2, (FRAMES[b], d)
+
+
+def test_planted_errors_leave_the_module_as_it_was(refs):
+    f0, c0 = R.rel_pos_emb, R.conformer_layer
+    with FR.positions_off_by_one():
+        assert torch.equal(R.rel_pos_emb(5), torch.roll(f0(5), 1, 0))
+    with FR.last_frame_dropped():
+        assert R.conformer_layer is not c0
+    assert R.rel_pos_emb is f0 and R.conformer_layer is c0
+
+
+def test_attention_rounding_twin_restates_the_oracle_layer(refs, monkeypatch):
+    """forward_ref.attention_roundings swaps in a restated Conformer layer: with its float16 roundings switched off it must BE
+    the oracle's layer (softmax written as exp / sum: float32 noise only), and with them it stays on the twin's floor"""
+    for b in CHECKED:
+        d = FR.maxdiff(refs["sharp"]["twin_att"][b], refs["sharp"]["lp"][b], FRAMES[b])
+        print(f"[fwd-ref] T={FRAMES[b]}: twin with attention roundings vs fp32 {d:.3e} (e {refs['sharp']['e'][b]:.3e})")
+        assert 0.0 < d < 1e-2, (FRAMES[b], d)
+    monkeypatch.setattr(FR, "_h", lambda x: x)
+    layer = R.conformer_layer
+    with FR.attention_roundings():
+        lp, _ = R.forward(refs["sharp_w"], refs["audio"], refs["lens"])
+    assert R.conformer_layer is layer
+    for b, n in enumerate(FRAMES):
+        assert FR.maxdiff(lp[b], refs["sharp"]["lp"][b], n) <= 2e-5, n
+
+
+def test_structured_condition_leaves_few_frames_out():
+    """GPU test 5 asks for equal argmax wherever the fp32 top-1 / top-2 gap exceeds 4 e; at most 5 % of the frames may fall
+    outside that condition -- here with the reference alone, on that test's clips."""
+    w = R.structured_weights(SEED)
+    lens = [FR.samples_for_frames(t) for t in FR.STRUCTURED_FRAMES]
+    ref = FR.reference(w, FR.clips(lens, FR.STRUCTURED_AUDIO_SEED), lens)
+    assert ref["t"] == FR.STRUCTURED_FRAMES
+    for b, n in enumerate(ref["t"]):
+        keep = FR.decided_frames(ref["lp"][b, :n], ref["e"][b])
+        left_out = 1.0 - float(keep.float().mean())
+        print(f"[fwd-ref] structured T={n}: e {ref['e'][b]:.3e}, bound (a) {ref['bound'][b]:.3e}, frames left out {left_out:.3f}")
+        assert left_out <= 0.05, (n, left_out)
+        # the twin itself decides those frames as fp32 does
+        assert bool((ref["twin"][b, :n].argmax(-1) == ref["lp"][b, :n].argmax(-1))[keep].all())
+
+
+def test_oracle_is_batch_invariant(refs):
+    """why one padded oracle call can serve a ragged device batch"""
+    for b in (0, 3):
+        n = refs["lens"][b]
+        one, t = R.forward(refs["sharp_w"], refs["audio"][b: b + 1, :n].contiguous(), [n])
+        assert int(t[0]) == FRAMES[b]
+        d = FR.maxdiff(one[0], refs["sharp"]["lp"][b], FRAMES[b])
+        print(f"[fwd-ref] T={FRAMES[b]} alone vs in the padded batch: {d:.2e}")
+        assert d <= 1e-5, (FRAMES[b], d)
+
+
+def test_samples_for_frames_is_the_smallest_count():
+    for t in (1, 2, 33, 376, 766):
+        n = FR.samples_for_frames(t)
+        assert R.sub_len(R.mel_frames(n)) == t
+        assert n == 400 or R.sub_len(R.mel_frames(n - 160)) == t - 1
+    assert R.sub_len(R.mel_frames(FR.MAX_SAMPLES)) == 766

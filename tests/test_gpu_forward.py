@@ -11,6 +11,7 @@ import os
 import pytest
 import torch
 
+from forward_ref import samples_for_frames as _samples_for_frames
 from synth import synth_audio
 
 pytestmark = pytest.mark.gpu
@@ -498,16 +499,6 @@ def test_digital_silence_is_finite_and_batch_invariant(setup):
     assert t1[0] == t[1] and torch.equal(one[0, : t1[0]], lp[1, : t[1]])
     res = eng.predict_batch(a.cuda().contiguous(), lens)
     assert len(res) == 2 and res[1]["t_frames"] == t[1]
-
-
-def _samples_for_frames(T):
-    """smallest sample count whose three stride-2 stages leave exactly T encoder frames"""
-    sl = lambda x: (x + 2 - 3) // 2 + 1  # noqa: E731
-    n = 400
-    while sl(sl(sl(n // 160 + 1))) < T:
-        n += 160
-    assert sl(sl(sl(n // 160 + 1))) == T
-    return n
 
 
 @pytest.mark.parametrize("precision", [0, 1, 2])

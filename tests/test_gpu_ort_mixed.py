@@ -21,6 +21,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from ort_floor import FLOOR_K, _assert_on_the_floor  # noqa: F401
 from synth import synth_audio
 
 pytestmark = pytest.mark.gpu
@@ -155,19 +156,6 @@ def test_whole_layer_and_head_on_device_inputs(setup):
         want = torch.log_softmax(lg, -1)[0]
         got = setup["lp"][b, :t].cpu()
         _report(f"head[{b}]", got, want, 2e-6)
-
-
-FLOOR_K = 1.5   # device-vs-oracle may be at most this many times the oracle's distance from itself on the same clip
-
-
-def _assert_on_the_floor(tag, got, floor):
-    mx, rms, same = got
-    print(f"[ort-e2e] {tag}: hip vs OrtMixed max {mx:.4f} rms {rms:.5f} argmax {same:.4f} | oracle vs itself: max {floor['max']:.4f} "
-          f"rms {floor['rms']:.5f} argmax {floor['argmax']:.4f}  ({', '.join(f'{k} {v[0]:.4f}/{v[1]:.5f}' for k, v in floor['rows'].items())})")
-    # within north_star's 1e-2 outright, or within FLOOR_K x what the reference's arithmetic reproduces of itself
-    assert mx <= max(FLOOR_K * floor["max"], 1e-2), (tag, mx, floor["max"])
-    assert rms <= max(FLOOR_K * floor["rms"], 2.5e-3), (tag, rms, floor["rms"])
-    assert same >= floor["argmax"] - 0.03, (tag, same, floor["argmax"])
 
 
 def test_logprobs_against_the_oracle_and_its_noise_floor(setup):
