@@ -2004,8 +2004,10 @@ __global__ __launch_bounds__(256) void k_result(QvTables tab, QvWork wk, int bat
     r.ctc_norm_loss = 0.f;
     r.n_tokens = u.n_tok;
     r.n_chars = u.q_len;
-    r.n_candidates = u.n_cand;
-    r.flags = u.flags;
+    // literal mode (skip_unused == 0) builds a candidate list for gate-pass utterances too; nothing scores it, so the
+    // result reports what include/qverse.h promises: no candidates and no clipped list when the rerank did not run
+    r.n_candidates = u.use_ctc ? u.n_cand : 0;
+    r.flags = u.use_ctc ? u.flags : (u.flags & ~QV_FLAG_CAND_OVERFLOW);
     r.t_frames = u.t_frames;
     if (u.q_len > 0) {
         if (u.use_ctc && key != ~0ull) {
