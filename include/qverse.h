@@ -302,6 +302,49 @@ int qv_align(qv_engine *e, const float *logprobs_dev, const int32_t *t_host, int
 int qv_align_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, qv_align_info *info_host, uint16_t *ids_host,
                          int16_t *first_host, int16_t *last_host, float *logp_host, int32_t pitch);
 
+/* ---- ranked alternatives (n-best) -------------------------------------------------------------
+ * The reference's predict() also returns "candidates": the head of the rerank's ranked list, or [best] when the gate
+ * passed (experiments/c2c-direct/run.py:424-435).  The list is selected on the device from what the batch left in HBM;
+ * one fixed-size record per row comes back in one copy.
+ *   QV_SOURCE_CTC rows   the stable top k of the row's reranked candidates with a finite loss, by final_score descending,
+ *                        ties to the smaller candidate index (run.py:378-379; IEEE > and == on doubles, so -0.0 and +0.0
+ *                        tie).  Entry 0 is the winner qv_result reports: same candidate, ctc_norm_loss with the same bits.
+ *   QV_SOURCE_TEXT rows  (the gate passed, or the rerank ran and no candidate was feasible) entry 0 is the text match with
+ *                        score = text_score = qv_result.base_score.  With QV_NBEST_TEXT_RUNNERS match_verse's runners-up
+ *                        follow in its order: single verses, scores unrounded; the runner that IS a single-verse base is
+ *                        not repeated.  Without the flag the list is [best], as in the reference.
+ *   rows without a prediction (empty or withheld transcript, surah 0): n_entries = 0.
+ * Entries past n_entries are zeroed. */
+#define QV_NBEST_MAX 32
+enum { QV_NBEST_TEXT_RUNNERS = 1 };
+typedef struct {
+    int32_t surah, ayah, ayah_end, start_verse, span;
+    int32_t cand_index;   /* index in the reranked candidate list; -1 for text entries */
+    int32_t source;       /* QV_SOURCE_CTC | QV_SOURCE_TEXT */
+    int32_t n_tokens;     /* CTC target length; 0 for text entries */
+    double  score;        /* CTC: final_score (run.py:376); TEXT: the text score */
+    double  text_score;
+    float   ctc_loss, ctc_norm_loss;
+} qv_nbest_entry;
+typedef struct { int32_t n_entries, n_ranked /* finite-loss candidates */, source, flags /* the row's QV_FLAG_* */; } qv_nbest_info;
+
+/* The n-best lists of context ctx's last batch: info_host[batch], entries_host[batch][k], 1 <= k <= QV_NBEST_MAX; flags:
+ * QV_NBEST_*.  SYNCHRONOUS.  Like qv_align_results_ctx it must be called before the context is reused (the next batch on
+ * it, or qv_match_verse / qv_debug_retrieve, which run on the current context's workspace), and it waits for the batch
+ * itself: on the context's own stream when the batch ran there, after a device-wide join when it ran on a caller stream.
+ * Works after qv_predict_batch[_async[_ctx]] and after qv_decode_retrieve_rerank[_async], with either matching window.
+ * The workspace (max_batch records of 1,808 bytes in device memory plus a pinned mirror) is allocated by the first call
+ * that uses the context; one device-to-host copy per call.  Bad context, null pointer, batch < 1, a batch the context
+ * does not hold, k outside 1..QV_NBEST_MAX or unknown flags: QV_ERR_ARG; batch above max_batch: QV_ERR_CAPACITY. */
+int qv_nbest_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, int32_t k, int32_t flags,
+                         qv_nbest_info *info_host, qv_nbest_entry *entries_host);
+/* The same selection on caller-supplied vectors: row r ranks the entries c < n_host[r] of final_host[r * pitch + c] whose
+ * loss_host[r * pitch + c] is finite.  index_host[rows][k] receives the indices in rank order, -1 padded; count_host[rows]
+ * how many.  rows <= max_batch (else QV_ERR_CAPACITY), 0 <= n_host[r] <= pitch <= 2048, 1 <= k <= QV_NBEST_MAX (else
+ * QV_ERR_ARG).  NaN scores are never selected.  SYNCHRONOUS on `stream`; uses the current context's n-best workspace. */
+int qv_nbest_select(qv_engine *e, const double *final_host, const float *loss_host, const int32_t *n_host,
+                    int32_t rows, int32_t pitch, int32_t k, int32_t *index_host, int32_t *count_host, void *stream);
+
 /* Device pointer of the packed (surah, ayah, ayah_end, float-bits(score)) i32[B,4] rows of the
  * last async call -- the payload of the per-batch RCCL all-gather. */
 const int32_t *qv_packed_results_dev(qv_engine *e);

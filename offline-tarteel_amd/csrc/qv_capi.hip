@@ -595,6 +595,7 @@ extern "C" void qv_destroy(qv_engine *e) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
         if (c.align.out_host) (void)hipHostFree(c.align.out_host);
         if (c.align.in_host) (void)hipHostFree(c.align.in_host);
+        if (c.nbest.out_host) (void)hipHostFree(c.nbest.out_host);
         if (c.stream) (void)hipStreamDestroy(c.stream);
         if (c.in_ready) (void)hipEventDestroy(c.in_ready);
         if (c.done) (void)hipEventDestroy(c.done);
@@ -1023,6 +1024,37 @@ extern "C" int qv_align_results_ctx(qv_engine *eng, int32_t k, int32_t batch, qv
     }
     if (batch > eng->ctx[k].work.max_batch) { qv_set_error(eng, "qv_align_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
     return qv_align_results(eng, k, batch, info_host, ids_host, first_host, last_host, logp_host, pitch);
+}
+
+// ---- ranked alternatives (qv_nbest.hip) ------------------------------------------------------------------------------
+extern "C" int qv_nbest_results_ctx(qv_engine *eng, int32_t k_ctx, int32_t batch, int32_t k, int32_t flags, qv_nbest_info *info_host,
+                                    qv_nbest_entry *entries_host) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (k_ctx < 0 || k_ctx >= eng->n_ctx || batch < 1 || k < 1 || k > QV_NBEST_MAX || (flags & ~QV_NBEST_TEXT_RUNNERS) || !info_host ||
+        !entries_host) {
+        qv_set_error(eng, "qv_nbest_results_ctx: bad context, null argument, empty batch, k outside 1..QV_NBEST_MAX or unknown flags");
+        return QV_ERR_ARG;
+    }
+    if (batch > eng->ctx[k_ctx].work.max_batch) { qv_set_error(eng, "qv_nbest_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    return qv_nbest_results(eng, k_ctx, batch, k, flags, info_host, entries_host);
+}
+
+extern "C" int qv_nbest_select(qv_engine *eng, const double *final_host, const float *loss_host, const int32_t *n_host, int32_t rows,
+                               int32_t pitch, int32_t k, int32_t *index_host, int32_t *count_host, void *stream) {
+    QV_SERIALISE(eng);
+    QV_ORDERED(eng, stream);
+    if (!eng) return QV_ERR_ARG;
+    if (!final_host || !loss_host || !n_host || !index_host || !count_host || rows < 1 || pitch < 1 || pitch > QV_CAND_CAP || k < 1 ||
+        k > QV_NBEST_MAX) {
+        qv_set_error(eng, "qv_nbest_select: null argument, no rows, pitch outside 1..2048 or k outside 1..QV_NBEST_MAX");
+        return QV_ERR_ARG;
+    }
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    if (rows > c.work.max_batch) { qv_set_error(eng, "qv_nbest_select: rows exceed engine capacity"); return QV_ERR_CAPACITY; }
+    for (int r = 0; r < rows; ++r)
+        if (n_host[r] < 0 || n_host[r] > pitch) { qv_set_error(eng, "qv_nbest_select: n_host[r] outside 0..pitch"); return QV_ERR_ARG; }
+    return qv_nbest_select_rows(eng, c, final_host, loss_host, n_host, rows, pitch, k, index_host, count_host, (hipStream_t)stream);
 }
 
 extern "C" int qv_debug_forward_tap(qv_engine *eng, int32_t what, int32_t layer, float *out_dev, void *stream) {

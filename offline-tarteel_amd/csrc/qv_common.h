@@ -210,6 +210,24 @@ int qv_align_explicit(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *
 int qv_align_results(qv_engine *eng, int k, int batch, qv_align_info *info_host, uint16_t *ids_host, int16_t *first_host,
                      int16_t *last_host, float *logp_host, int pitch);
 
+// ranked alternatives (qv_nbest.hip).  One record per row -- qv_nbest_info, then QV_NBEST_MAX entries -- so a batch comes
+// back in ONE copy into a pinned buffer, from where the host hands the first k entries of every row to the caller.
+#define QV_NBEST_ROW_BYTES (sizeof(qv_nbest_info) + QV_NBEST_MAX * sizeof(qv_nbest_entry))
+#define QV_NBEST_SEL_PITCH (QV_NBEST_MAX + 1)   // qv_nbest_select's device output per row: the count, then the indices
+// per-context n-best workspace, allocated by the first n-best call on that context (out == nullptr: not yet); the staging
+// arrays of the explicit form by the first qv_nbest_select (sel_final == nullptr: not yet)
+struct QvNbestWs {
+    unsigned char *out;       // [B][QV_NBEST_ROW_BYTES]
+    unsigned char *out_host;  // pinned mirror of out (qv_nbest_select's indices come back through it as well)
+    double *sel_final;        // [B][QV_CAND_CAP], followed in the same allocation by
+    float *sel_loss;          // [B][QV_CAND_CAP]
+    int32_t *sel_n;           // [B]
+    int32_t *sel_idx;         // [B][QV_NBEST_SEL_PITCH]
+};
+int qv_nbest_results(qv_engine *eng, int k_ctx, int batch, int k, int flags, qv_nbest_info *info_host, qv_nbest_entry *entries_host);
+int qv_nbest_select_rows(qv_engine *eng, QvCtx &c, const double *final_host, const float *loss_host, const int32_t *n_host, int rows,
+                         int pitch, int k, int32_t *index_host, int32_t *count_host, hipStream_t stream);
+
 // post-logits launchers (qv_postlogits.hip); `c` is the execution context whose workspace and staging slots the call uses
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,
@@ -288,6 +306,8 @@ struct QvCtx {
     int al_tmax = 0, al_batch = 0;
     hipStream_t al_stream = nullptr;
     QvAlignWs align = {};
+    // ranked alternatives (qv_nbest_results_ctx): the same batch, read from the candidate arrays of `work`
+    QvNbestWs nbest = {};
 };
 
 struct qv_engine {

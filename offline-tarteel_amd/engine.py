@@ -79,6 +79,28 @@ ALIGN_INFO_DTYPE = np.dtype([("n_tokens", "<i4"), ("flags", "<i4"), ("t_frames",
                              ("span", "<i4"), ("reserved", "<i4"), ("score", "<f4"), ("reserved_f", "<f4")])
 assert ALIGN_INFO_DTYPE.itemsize == C.sizeof(QvAlignInfo)
 
+NBEST_MAX = 32           # include/qverse.h: QV_NBEST_MAX
+NBEST_TEXT_RUNNERS = 1   # QV_NBEST_TEXT_RUNNERS
+
+
+class QvNbestEntry(C.Structure):
+    """include/qverse.h: qv_nbest_entry"""
+    _fields_ = [("surah", C.c_int32), ("ayah", C.c_int32), ("ayah_end", C.c_int32), ("start_verse", C.c_int32),
+                ("span", C.c_int32), ("cand_index", C.c_int32), ("source", C.c_int32), ("n_tokens", C.c_int32),
+                ("score", C.c_double), ("text_score", C.c_double), ("ctc_loss", C.c_float), ("ctc_norm_loss", C.c_float)]
+
+
+class QvNbestInfo(C.Structure):
+    """include/qverse.h: qv_nbest_info"""
+    _fields_ = [("n_entries", C.c_int32), ("n_ranked", C.c_int32), ("source", C.c_int32), ("flags", C.c_int32)]
+
+
+NBEST_ENTRY_DTYPE = np.dtype([("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("start_verse", "<i4"), ("span", "<i4"),
+                              ("cand_index", "<i4"), ("source", "<i4"), ("n_tokens", "<i4"), ("score", "<f8"),
+                              ("text_score", "<f8"), ("ctc_loss", "<f4"), ("ctc_norm_loss", "<f4")], align=True)
+NBEST_INFO_DTYPE = np.dtype([("n_entries", "<i4"), ("n_ranked", "<i4"), ("source", "<i4"), ("flags", "<i4")])
+assert NBEST_ENTRY_DTYPE.itemsize == C.sizeof(QvNbestEntry) == 56 and NBEST_INFO_DTYPE.itemsize == C.sizeof(QvNbestInfo) == 16
+
 RESULT_DTYPE = np.dtype([
     ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("source", "<i4"),
     ("score", "<f8"), ("base_score", "<f8"), ("ctc_norm_loss", "<f4"),
@@ -134,6 +156,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_fetch_results_ctx.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.qv_align.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_align_results_ctx.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32]
+    lib.qv_nbest_results_ctx.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.qv_nbest_select.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.qv_tracker_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -296,9 +320,11 @@ class Engine:
         self._check(rc, "qv_forward")
         return lp, t_out.tolist()
 
-    def decode_retrieve_rerank(self, log_probs, t_frames, want_text: bool = True, align: bool = False) -> list[dict]:
+    def decode_retrieve_rerank(self, log_probs, t_frames, want_text: bool = True, align: bool = False,
+                               nbest: int | None = None) -> list[dict]:
         """align=True: every result dict gains an "alignment" entry (align_results) -- the winner's token ids and the
-        frames each of them occupies in `log_probs`."""
+        frames each of them occupies in `log_probs`.  nbest=K: every dict gains "nbest", the row's list of up to K ranked
+        alternatives (nbest_results)."""
         torch = self.torch
         assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous()
         B, t_max, V = log_probs.shape
@@ -311,9 +337,9 @@ class Engine:
             res.ctypes.data_as(C.c_void_p),
             greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
         self._check(rc, "qv_decode_retrieve_rerank")
-        return self._with_alignment(self._results(res, greedy), align)
+        return self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest)
 
-    def predict_batch(self, audio, lengths, want_text: bool = True, align: bool = False) -> list[dict]:
+    def predict_batch(self, audio, lengths, want_text: bool = True, align: bool = False, nbest: int | None = None) -> list[dict]:
         torch = self.torch
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
         B, N = audio.shape
@@ -326,7 +352,71 @@ class Engine:
             res.ctypes.data_as(C.c_void_p),
             greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
         self._check(rc, "qv_predict_batch")
-        return self._with_alignment(self._results(res, greedy), align)
+        return self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest)
+
+    # ---------------------------------------------------------------- ranked alternatives
+    def _with_nbest(self, results: list[dict], nbest: int | None) -> list[dict]:
+        if nbest is not None:
+            for d, lst in zip(results, self.nbest_results(batch=len(results), k=int(nbest))):
+                d["nbest"] = lst
+        return results
+
+    def nbest_raw(self, ctx: int | None = None, batch: int = 1, k: int = 5, runners: bool = False):
+        """qv_nbest_results_ctx as structured arrays: (info [batch] of NBEST_INFO_DTYPE, entries [batch, k] of
+        NBEST_ENTRY_DTYPE)."""
+        if ctx is None:
+            ctx = int(self.lib.qv_last_context(self.h))
+        info = np.zeros(batch, dtype=NBEST_INFO_DTYPE)
+        ent = np.zeros((batch, max(int(k), 1)), dtype=NBEST_ENTRY_DTYPE)
+        rc = self.lib.qv_nbest_results_ctx(self.h, int(ctx), int(batch), int(k), NBEST_TEXT_RUNNERS if runners else 0,
+                                           info.ctypes.data_as(C.c_void_p), ent.ctypes.data_as(C.c_void_p))
+        self._check(rc, "qv_nbest_results_ctx")
+        return info, ent
+
+    def nbest_results(self, ctx: int | None = None, batch: int = 1, k: int = 5, runners: bool = False) -> list[list[dict]]:
+        """Ranked alternatives of every row of context `ctx`'s last batch (default: the most recent call's), selected on
+        the device (qv_nbest_results_ctx).  Per row a list of at most k dicts, best first: "surah", "ayah", "ayah_end",
+        "start" / "span" (first verse as a global index, number of ayat), "cand_index" (position in the reranked
+        candidate list, -1 for text entries), "source", "n_tokens", "score" (the rerank's final_score for a CTC row, the
+        text score for a text row), "text_score", "ctc_loss", "ctc_norm_loss".  A reranked row lists the head of the
+        rerank's ranking (entry 0 is the prediction); a row decided by the text match lists that match -- with
+        runners=True followed by match_verse's runners-up; a row without a prediction is [].  Call it before the context
+        is reused."""
+        info, ent = self.nbest_raw(ctx, batch, k, runners)
+        out = []
+        for b in range(batch):
+            rows = []
+            for e in ent[b, : int(info[b]["n_entries"])]:
+                rows.append({"surah": int(e["surah"]), "ayah": int(e["ayah"]), "ayah_end": int(e["ayah_end"]),
+                             "start": int(e["start_verse"]), "span": int(e["span"]), "cand_index": int(e["cand_index"]),
+                             "source": QV_SOURCE[int(e["source"])], "n_tokens": int(e["n_tokens"]), "score": float(e["score"]),
+                             "text_score": float(e["text_score"]), "ctc_loss": float(e["ctc_loss"]),
+                             "ctc_norm_loss": float(e["ctc_norm_loss"])})
+            out.append(rows)
+        return out
+
+    def nbest_select(self, finals, losses, k: int = 5) -> list[list[int]]:
+        """The device's selection on explicit vectors (qv_nbest_select): finals[r] (float64) and losses[r] (float32) are
+        row r's scores and losses, rows may differ in length (at most 2,048 entries, at most max_batch rows).  Per row
+        the indices of the stable top k by score among the entries with a finite loss: score descending, ties to the
+        smaller index."""
+        rows = len(finals)
+        assert rows == len(losses) and rows >= 1
+        n = np.ascontiguousarray(np.array([len(x) for x in finals], np.int32))
+        assert all(len(a) == len(b) for a, b in zip(finals, losses))
+        pitch = max(int(n.max()), 1)
+        fin = np.zeros((rows, pitch), np.float64)
+        los = np.full((rows, pitch), np.inf, np.float32)
+        for r in range(rows):
+            fin[r, : n[r]] = np.asarray(finals[r], np.float64)
+            los[r, : n[r]] = np.asarray(losses[r], np.float32)
+        idx = np.zeros((rows, max(int(k), 1)), np.int32)
+        cnt = np.zeros(rows, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_nbest_select(self.h, p(fin), p(los), p(n), rows, pitch, int(k), p(idx), p(cnt), self._stream())
+        self._check(rc, "qv_nbest_select")
+        assert all((idx[r, cnt[r]:] == -1).all() for r in range(rows))
+        return [idx[r, : cnt[r]].tolist() for r in range(rows)]
 
     # ---------------------------------------------------------------- word timings
     def _with_alignment(self, results: list[dict], align: bool) -> list[dict]:

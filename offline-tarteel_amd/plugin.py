@@ -38,6 +38,9 @@ _PRECISIONS = {"fp16": 0, "mixed": 1, "ort": 2}
 # QVERSE_WORDS=1: predict() adds "words" -- per-word timings of the recognised verse from the device's forced alignment
 # (Engine.align_results + words.words_from_alignment); [] when there is no prediction or the alignment carries a flag
 _WORDS = os.getenv("QVERSE_WORDS", "") not in ("", "0", "false", "False")
+# QVERSE_CANDIDATES=K: predict() adds the reference's "candidates" list (c2c-direct/run.py:424-435) with up to K entries
+# (1..32; the reference keeps 5) -- see predict_candidates
+_CANDIDATES = int(os.getenv("QVERSE_CANDIDATES", "0") or 0) or None
 _engine = None
 _last_raw: list[dict] = []   # engine-level dicts of the most recent predict_arrays() call (profile line)
 
@@ -99,17 +102,27 @@ def _words_of(eng, r: dict) -> list[dict]:
     return words_from_alignment(eng.tables, a["start"], a["span"], a)
 
 
-def _finish(eng, raw: list[dict], round_score: bool, words: bool) -> list[dict]:
+def shape_candidates(nbest: list[dict]) -> list[dict]:
+    """An engine n-best list as the reference's "candidates" (c2c-direct/run.py:424-435): ranked[:K] when the rerank ranked
+    anything, [best] with the text score otherwise, [] for an empty prediction; scores rounded to 4 places."""
+    return [{"surah": e["surah"], "ayah": e["ayah"], "ayah_end": e["ayah_end"] or e["ayah"], "score": round(float(e["score"]), 4)}
+            for e in nbest]
+
+
+def _finish(eng, raw: list[dict], round_score: bool, words: bool, candidates: int | None = None) -> list[dict]:
     out = [_to_dict(r, round_score) for r in raw]
     if words:
         for d, r in zip(out, raw):
             d["words"] = _words_of(eng, r)
+    if candidates is not None:
+        for d, r in zip(out, raw):
+            d["candidates"] = shape_candidates(r["nbest"]) if r["surah"] else []
     return out
 
 
-def predict_arrays(arrays, round_score: bool = True, words: bool = False) -> list[dict]:
+def predict_arrays(arrays, round_score: bool = True, words: bool = False, candidates: int | None = None) -> list[dict]:
     """audio arrays (float32, 16 kHz) -> predict()-shaped dicts, one engine call per <= MAX_BATCH.
-    words=True: every dict gains "words" (see predict_words)."""
+    words=True: every dict gains "words" (see predict_words); candidates=K: "candidates" (see predict_candidates)."""
     import torch
 
     eng = _ensure_engine()
@@ -121,34 +134,43 @@ def predict_arrays(arrays, round_score: bool = True, words: bool = False) -> lis
         for i, a in enumerate(chunk):
             buf[i, : len(a)] = a
         dev = torch.from_numpy(buf).cuda(eng.device)
-        raw = eng.predict_batch(dev, lens, align=words)
+        raw = eng.predict_batch(dev, lens, align=words, nbest=candidates)
         _last_raw[:] = raw
-        out.extend(_finish(eng, raw, round_score, words))
+        out.extend(_finish(eng, raw, round_score, words, candidates))
     return out
 
 
-def predict_device(dev, lens, round_score: bool = True, words: bool = False) -> list[dict]:
+def predict_device(dev, lens, round_score: bool = True, words: bool = False, candidates: int | None = None) -> list[dict]:
     """a zero-padded float32 cuda matrix of 16 kHz clips -> predict()-shaped dicts, one engine call per <= MAX_BATCH rows"""
     eng = _ensure_engine()
     out = []
     for s in range(0, len(lens), eng.max_batch):
         chunk = lens[s: s + eng.max_batch]
-        raw = eng.predict_batch(dev[s: s + len(chunk), : max(chunk)].contiguous(), chunk, align=words)
+        raw = eng.predict_batch(dev[s: s + len(chunk), : max(chunk)].contiguous(), chunk, align=words, nbest=candidates)
         _last_raw[:] = raw
-        out.extend(_finish(eng, raw, round_score, words))
+        out.extend(_finish(eng, raw, round_score, words, candidates))
     return out
 
 
-def predict_batch(audio_paths, words: bool = False) -> list[dict]:
+def predict_batch(audio_paths, words: bool = False, candidates: int | None = None) -> list[dict]:
     """files -> dicts.  The ingest (mix-down, resampling to 16 kHz) runs on the GPU (audio.load_audio_device: the same float32
     arithmetic as the host load_audio, bit for bit); QVERSE_INGEST=host keeps it on the host.
-    words=True: every dict gains "words" (see predict_words); without it the dicts are unchanged."""
+    words=True: every dict gains "words" (see predict_words); candidates=K: every dict carries "candidates" (see
+    predict_candidates); without them the dicts are unchanged."""
     if os.getenv("QVERSE_INGEST", "device") == "host":
-        return predict_arrays([load_audio(p) for p in audio_paths], words=words)
+        return predict_arrays([load_audio(p) for p in audio_paths], words=words, candidates=candidates)
     from .audio import load_audio_device
 
     dev, lens = load_audio_device(list(audio_paths), _ensure_engine())
-    return predict_device(dev, lens, words=words)
+    return predict_device(dev, lens, words=words, candidates=candidates)
+
+
+def predict_candidates(audio_path: str, k: int = 5) -> dict:
+    """predict() plus the reference's "candidates" (c2c-direct/run.py:424-435): up to k {"surah", "ayah", "ayah_end",
+    "score"} dicts, best first -- the head of the CTC rerank's ranking with its final scores when the rerank decided, the
+    text match with its score when the gate passed, [] when nothing was recognised.  Selected on the device
+    (Engine.nbest_results)."""
+    return predict_arrays([load_audio(audio_path)], candidates=k)[0]
 
 
 def predict_words(audio_path: str) -> dict:
@@ -163,7 +185,7 @@ def predict(audio_path: str) -> dict:
     t0 = time.perf_counter()
     audio = load_audio(audio_path)
     t1 = time.perf_counter()
-    res = predict_arrays([audio], words=_WORDS)[0]
+    res = predict_arrays([audio], words=_WORDS, candidates=_CANDIDATES)[0]
     if _PROFILE:
         # the reference's line (mixed/run.py:76-81,117-124): forward= decode= build= rerank= total=
         # candidates= use_ctc= source= -- stage times from HIP events around the device stages of this
