@@ -147,7 +147,9 @@ int qv_forward(qv_engine *e, const float *audio_dev, const int64_t *lengths_host
 /* Post-logits stages on log-probs already in HBM.  t_host[b] = valid frames of row b.
  * results_host: qv_result[B]; greedy_ids_host (optional, may be NULL): i32[B, t_max] collapsed
  * token ids (-1 padded) for host-side transcript text.  SYNCHRONOUS: returns after the results
- * have been copied back (one stream sync at the end, none in between). */
+ * have been copied back (one stream sync at the end, none in between).
+ * Rows t >= t_host[b] of logprobs_dev are NEVER READ, here, by qv_align and by the calls that go back to the tensor
+ * (qv_align_results_ctx): they may hold anything, NaN included.  Valid frames hold no NaN. */
 int qv_decode_retrieve_rerank(qv_engine *e, const float *logprobs_dev, const int32_t *t_host,
                               int32_t batch, int32_t t_max, qv_result *results_host,
                               int32_t *greedy_ids_host, void *stream);
@@ -365,6 +367,17 @@ int qv_debug_retrieve(qv_engine *e, const uint8_t *codes_host, int32_t n_codes,
 int qv_debug_ctc_loss(qv_engine *e, const float *logprobs_dev, int32_t t_frames,
                       const uint16_t *targets_host, const int32_t *lens_host, int32_t n,
                       float *loss_host, void *stream);
+
+/* The normalised transcript the decode kernel left in context ctx's workspace -- what the matching kernels read, not a
+ * host restatement from the greedy ids.  Row b of codes_host (rows `pitch` bytes apart, pitch >= qv_max_transcript(e),
+ * else QV_ERR_ARG) receives the row's len_host[b] alphabet codes (0 = ' ', 63 = a character outside the verse alphabet;
+ * bytes past the length are left alone); len_host[b] / words_host[b] = its length in codes and its number of
+ * whitespace-separated words.  A row flagged QV_FLAG_EMPTY_TRANSCRIPT or QV_FLAG_TRANSCRIPT_TRUNCATED has length 0.
+ * Same lifetime rule as qv_fetch_results_ctx: ask before the context is reused; it waits for the batch itself.  Works
+ * with either matching window.  Bad context, null pointer, batch < 1 or a batch the context does not hold: QV_ERR_ARG;
+ * batch above max_batch: QV_ERR_CAPACITY. */
+int qv_debug_transcript_codes(qv_engine *e, int32_t ctx, int32_t batch, uint8_t *codes_host, int32_t pitch,
+                              int32_t *len_host, int32_t *words_host);
 
 /* Intermediate activations of the acoustic model for the layer-wise parity tests.
  * what: 0 = normalised mel features f32[B, t_mel_max, 80]; 1 = subsampling output

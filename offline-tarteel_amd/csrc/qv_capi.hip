@@ -900,6 +900,39 @@ extern "C" int qv_fetch_results_ctx(qv_engine *eng, int32_t k, int32_t batch, in
     return fetch_results(eng, eng->ctx[k], batch, t_max, res, greedy_host, stream);
 }
 
+// the transcript k_decode left in the workspace (rows of eng->max_q codes: the pitch of the kernel set the engine runs)
+extern "C" int qv_debug_transcript_codes(qv_engine *eng, int32_t k, int32_t batch, uint8_t *codes_host, int32_t pitch,
+                                         int32_t *len_host, int32_t *words_host) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (k < 0 || k >= eng->n_ctx || batch < 1 || !codes_host || !len_host || !words_host || pitch < eng->max_q) {
+        qv_set_error(eng, "qv_debug_transcript_codes: bad context, null argument, empty batch or pitch < qv_max_transcript");
+        return QV_ERR_ARG;
+    }
+    QvCtx &c = eng->ctx[k];
+    if (batch > c.work.max_batch) { qv_set_error(eng, "qv_debug_transcript_codes: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    if (!c.al_lp || batch > c.al_batch) {
+        qv_set_error(eng, "qv_debug_transcript_codes: the context holds no batch of that size (ask before the context is reused)");
+        return QV_ERR_ARG;
+    }
+    if (eng->n_ctx == 1) QV_HIP(hipDeviceSynchronize());  // the batch ran on a caller stream we were not given
+    hipStream_t stream = eng->n_ctx > 1 ? c.stream : nullptr;
+    QV_ORDERED(eng, stream);
+    std::vector<QvUtt> utt(batch);
+    std::vector<uint8_t> q((size_t)batch * eng->max_q);
+    QV_HIP(hipMemcpyAsync(utt.data(), c.work.utt, sizeof(QvUtt) * batch, hipMemcpyDeviceToHost, stream));
+    QV_HIP(hipMemcpyAsync(q.data(), c.work.q, q.size(), hipMemcpyDeviceToHost, stream));
+    QV_HIP(hipStreamSynchronize(stream));
+    for (int b = 0; b < batch; ++b) {
+        const int n = utt[b].q_len;
+        if (n < 0 || n > eng->max_q) { qv_set_error(eng, "qv_debug_transcript_codes: q_len outside the window"); return QV_ERR_HIP; }
+        memcpy(codes_host + (size_t)b * pitch, q.data() + (size_t)b * eng->max_q, (size_t)n);
+        len_host[b] = n;
+        words_host[b] = utt[b].q_words;
+    }
+    return QV_OK;
+}
+
 extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int32_t n_codes, int32_t *base_start,
                                  int32_t *base_span, double *base_score, int32_t *cand_start, int32_t *cand_span,
                                  double *cand_score, int32_t cand_cap, int32_t *n_cand, int32_t *runner_idx,

@@ -162,6 +162,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.qv_debug_ctc_loss.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp]
+    lib.qv_debug_transcript_codes.argtypes = [vp, i32, i32, vp, i32, vp, vp]
     lib.qv_debug_forward_tap.argtypes = [vp, i32, i32, vp, vp]
     lib.qv_profile_gemm.argtypes = [vp, i32]
     lib.qv_profile_gemm_read.argtypes = [vp, vp, vp, vp]
@@ -294,6 +295,9 @@ class Engine:
                 ids = greedy[b, : int(r["n_tokens"])].tolist()
                 d["greedy_ids"] = ids
                 d["transcript"] = self.transcript_of(ids)
+                # the device's own counts of that transcript (greedy tokens, normalised characters): with the text fields,
+                # so that a row fetched without them (want_text=False) keeps the numeric fields it always had
+                d["n_tokens"], d["n_chars"] = int(r["n_tokens"]), int(r["n_chars"])
             out.append(d)
         return out
 
@@ -813,6 +817,21 @@ class Engine:
         return {"base_start": bs.value, "base_span": bp.value, "base_score": bsc.value,
                 "cand_start": cs[:n].copy(), "cand_span": cp[:n].copy(), "cand_score": csc[:n].copy(),
                 "runner_idx": ri[: nr.value].copy(), "runner_score": rs[: nr.value].copy()}
+
+    def transcript_codes(self, ctx: int | None = None, batch: int = 1) -> list[dict]:
+        """The normalised transcript the decode kernel left on the device for every row of context `ctx`'s last batch
+        (default: the most recent call's) -- the codes the matching kernels read (qv_debug_transcript_codes).  Per row
+        {"codes": uint8 array (tables.encode of the transcript), "n_chars", "n_words"}; a row flagged EMPTY or TRUNCATED
+        has no codes.  Call it before the context is reused."""
+        if ctx is None:
+            ctx = int(self.lib.qv_last_context(self.h))
+        pitch = self.max_transcript
+        codes = np.zeros((batch, pitch), np.uint8)
+        n, words = np.zeros(batch, np.int32), np.zeros(batch, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_debug_transcript_codes(self.h, int(ctx), int(batch), p(codes), pitch, p(n), p(words))
+        self._check(rc, "qv_debug_transcript_codes")
+        return [{"codes": codes[b, : n[b]].copy(), "n_chars": int(n[b]), "n_words": int(words[b])} for b in range(batch)]
 
     def debug_ctc_loss(self, log_probs_2d, id_lists) -> np.ndarray:
         assert log_probs_2d.is_cuda and log_probs_2d.dim() == 2 and log_probs_2d.is_contiguous()

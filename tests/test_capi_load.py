@@ -19,7 +19,7 @@ def test_library_builds_loads_and_exports_header_symbols():
     from offline_tarteel_amd.engine import exported_symbols
 
     syms = exported_symbols()
-    assert len(syms) >= 14
+    assert len(syms) >= 14 and "qv_debug_transcript_codes" in syms
     for s in syms:
         assert hasattr(lib, s), f"libqverse.so lacks {s}"
     lib.qv_build_info.restype = ctypes.c_char_p

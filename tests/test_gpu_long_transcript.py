@@ -288,6 +288,43 @@ def test_hot_path_matches_long_transcripts_the_default_window_withholds(wide, de
         check_hot(g, w, name)
 
 
+@pytest.fixture(scope="module")
+def readout_case(oracle):
+    """2:282 alone (298 tokens, 597 states) with 35 % of its ids replaced: fails the gate, fits the default window, and every
+    candidate near it is a target of more than 384 states"""
+    ids = oracle.token_ids(oracle.verse_index(2, 282), 1).tolist()
+    assert 384 < 2 * len(ids) + 1 <= T_LONG
+    return ("2:282 35% replaced", dense_logprobs(corrupted(ids, 0.35, 7), T_LONG, 21), T_LONG)
+
+
+def test_member_readouts_of_long_targets_against_torch(either, oracle, hot_cases, readout_case):
+    """k_ctc<true, .> on the hot path: one alpha recursion per leader, and the losses of its members read off the same
+    alpha row at their own lengths.  Every entry of the reranked rows' n-best lists (k = 32): the token count is the
+    table's, the loss is F.ctc_loss of that token list within 1e-3 max(1, |want| / 100) -- targets of more than 384 and of
+    more than 512 states among them, which the per-target entry point reaches only through k_ctc_debug."""
+    cases = hot_cases[0] + [readout_case]
+    lp, frames = batch_of(cases)
+    res = either.decode_retrieve_rerank(lp, frames, want_text=False)
+    info, ent = either.nbest_raw(batch=len(cases), k=32)
+    n = n384 = n512 = 0
+    worst = 0.0
+    for b, ((name, x, T), r) in enumerate(zip(cases, res)):
+        if r["source"] != "ctc":
+            continue
+        rows = ent[b, : int(info[b]["n_entries"])]
+        id_lists = [either.tables.token_ids(int(e["start_verse"]), int(e["span"])).tolist() for e in rows]
+        want = oracle.ctc_loss_torch(x[:T].numpy(), id_lists)
+        for e, ids, w in zip(rows, id_lists, want):
+            assert int(e["n_tokens"]) == len(ids) and 2 * len(ids) + 1 <= T, (name, int(e["cand_index"]))
+            d = abs(float(e["ctc_loss"]) - float(w))
+            assert d <= 1e-3 * max(1.0, abs(float(w)) / 100), (name, int(e["cand_index"]), len(ids), float(e["ctc_loss"]), float(w))
+            worst = max(worst, d / max(1.0, abs(float(w)) / 100))
+            n, n384, n512 = n + 1, n384 + (2 * len(ids) + 1 > 384), n512 + (2 * len(ids) + 1 > 512)
+    print(f"window {either.max_transcript}: {n} entries compared, {n384} of more than 384 states, {n512} of more than 512; "
+          f"largest scaled distance {worst:.3g}")
+    assert n384 >= 10 and n512 >= 1
+
+
 def retrieve_vs_oracle(eng, oracle, t, want):
     r = eng.debug_retrieve(t)
     (cs, cp, sc, m), mv = want

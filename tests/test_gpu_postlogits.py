@@ -128,6 +128,95 @@ def test_parity_specialised_ctc_recursion_equals_the_generic_one_bit_for_bit(eng
         assert a == b, (a, b)
 
 
+def ctc_torch_strict(lp, id_lists):
+    """Oracle.ctc_loss_torch's call (batches of 16 on expanded float32 log-probs, reduction='none') with
+    zero_infinity=False: a target with no alignment comes back as inf"""
+    import torch.nn.functional as F
+
+    t, vocab = lp.shape
+    log_probs = torch.from_numpy(np.ascontiguousarray(lp, dtype=np.float32)).unsqueeze(1)
+    out = []
+    for s in range(0, len(id_lists), 16):
+        chunk = id_lists[s: s + 16]
+        n = len(chunk)
+        targets = torch.tensor([int(x) for seq in chunk for x in seq], dtype=torch.long)
+        tl = torch.tensor([len(seq) for seq in chunk], dtype=torch.long)
+        il = torch.full((n,), t, dtype=torch.long)
+        out.extend(F.ctc_loss(log_probs.expand(t, n, vocab).contiguous(), targets, il, tl, blank=1024, reduction="none",
+                              zero_infinity=False).tolist())
+    return np.asarray(out, dtype=np.float32)
+
+
+@pytest.fixture(scope="module")
+def long_ids(oracle):
+    return oracle.token_ids(oracle.verse_index(2, 282), 5).tolist()          # 2:282-286, 618 tokens
+
+
+@pytest.mark.parametrize("noise,boost", [(1.0, 5.0), (2.0, 5.0), (1.0, 30.0), (3.0, 12.0)])
+@pytest.mark.parametrize("T", [385, 513, 766, 768])
+def test_ctc_loss_beyond_384_states_vs_torch_and_the_float64_twin(engine, oracle, long_ids, T, noise, boost):
+    """ctc_wave<8> / <12> and ctc_wave2<8> / <12> (385 ... 768 states) against references of their own -- F.ctc_loss and
+    the float64 twin -- instead of against each other: target lengths around every instantiation boundary, T = 2L + 1
+    exactly, equal neighbours at 1|2 and at the end, one id repeated (a blank between every pair: 2L - 1 frames), on peaked and on
+    flat log-probs, both wave programs.  Bounds of DESIGN.md section 2: |loss - F.ctc_loss| <= 1e-3 max(1, |want| / 100) and
+    |loss / L - twin| <= 1e-5 max(1, |twin|); above 384 states a target may sit up to twice as far from the twin as torch's
+    own float32 recursion does on that target (both are float32 recursions that differ in summation order and in the
+    rounding of exp / log).  Device, torch and twin must agree on which targets have no alignment (with 2L + 1 <= T every
+    target has one: the three must all say so)."""
+    rng = np.random.default_rng(T + int(100 * noise + boost))
+    worst = {"dev": 0.0, "torch": 0.0, "dev_abs": 0.0, "torch_abs": 0.0, "dev_vs_torch": 0.0}
+    n_long = n_inf = 0
+    lp = torch.log_softmax(torch.from_numpy(synth_logits(long_ids, T, seed=T + int(boost), noise=noise, boost=boost, rep=2)), -1)
+    targets = []
+    for L in sorted({L for L in (1, 191, 192, 193, 255, 256, 257, 300, 383) if 2 * L + 1 <= T} | {(T - 1) // 2}):
+        t = rng.integers(0, 1024, size=L)
+        targets.append(t.astype(np.uint16))
+        t = rng.integers(0, 1024, size=L)
+        if L > 3:
+            t[2] = t[1]
+            t[L - 1] = t[L - 2]
+        targets.append(t.astype(np.uint16))
+        targets.append(np.full(L, int(rng.integers(0, 1024)), np.uint16))
+        targets.append(np.asarray(long_ids[:L], np.uint16))
+    assert 2 * len(targets[-1]) + 1 == T - (T % 2 == 0)
+    want = ctc_torch_strict(lp.numpy(), targets)
+    twin = np.array([oracle.ctc_score_f64(lp.numpy(), tg.tolist()) for tg in targets])
+    dev = lp.cuda().contiguous()
+    got = {}
+    try:
+        for var in (0, 1):
+            engine.kernel_variant(4, var)
+            got[var] = engine.debug_ctc_loss(dev, targets)
+    finally:
+        engine.kernel_variant(4, -1)
+    assert got[0].view(np.uint32).tolist() == got[1].view(np.uint32).tolist(), (T, noise, boost)
+    for tg, g, w, tw in zip(targets, got[1], want, twin):
+        L = len(tg)
+        tag = (T, noise, boost, L, float(g), float(w), float(tw))
+        assert np.isinf(g) == np.isinf(w) == (tw == 1e9), tag
+        assert not np.isnan(g), tag
+        if np.isinf(g):
+            n_inf += 1
+            continue
+        b_torch, b_twin = 1e-3 * max(1.0, abs(w) / 100), 1e-5 * max(1.0, abs(tw))
+        d_dev, d_torch = abs(g / L - tw), abs(w / L - tw)
+        if 2 * L + 1 > 384:
+            n_long += 1
+            b_twin = max(b_twin, 2 * d_torch)
+            b_torch = max(b_torch, 2 * d_torch * L)
+        assert abs(g - w) <= b_torch, tag
+        assert d_dev <= b_twin, tag
+        scale = max(1.0, abs(tw))
+        worst["dev"], worst["torch"] = max(worst["dev"], d_dev / scale), max(worst["torch"], d_torch / scale)
+        worst["dev_abs"] = max(worst["dev_abs"], d_dev * L / max(1.0, abs(w) / 100))
+        worst["torch_abs"] = max(worst["torch_abs"], d_torch * L / max(1.0, abs(w) / 100))
+        worst["dev_vs_torch"] = max(worst["dev_vs_torch"], abs(g - w) / max(1.0, abs(w) / 100))
+    print(f"T={T} noise={noise} boost={boost}: device to twin {worst['dev']:.3g} relative / {worst['dev_abs']:.3g} scaled absolute, torch float32 to twin "
+          f"{worst['torch']:.3g} / {worst['torch_abs']:.3g}, device to torch {worst['dev_vs_torch']:.3g} scaled absolute; "
+          f"{n_long} targets above 384 states, {n_inf} without an alignment")
+    assert n_long >= 3 and n_inf == 0
+
+
 def test_retrieval_matches_reference_fixtures(engine, oracle, ret_cases):
     from oracle.oracle import normalize_arabic
 
