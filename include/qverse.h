@@ -347,6 +347,55 @@ int qv_nbest_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, int32_t k, in
 int qv_nbest_select(qv_engine *e, const double *final_host, const float *loss_host, const int32_t *n_host,
                     int32_t rows, int32_t pitch, int32_t k, int32_t *index_host, int32_t *count_host, void *stream);
 
+/* ---- transcription with confidence --------------------------------------------------------------
+ * The greedy transcript of every row together with how sure the model was of it: what a streaming front end gates its
+ * chunks by (the reference's transcribers return {"text", "avg_logprob"}, shared/streaming.py:158-181).  One kernel on
+ * log-probs f32[batch, t_max, 1025] in HBM with t_host[b] valid frames (rows t >= t_host[b] are never read), one
+ * fixed-size record per row back in one copy.
+ *   per frame   fid[t] = the argmax of frame t with numpy's first-maximum rule (the decode stage's own rule: -0.0 and
+ *               +0.0 tie, the smaller index wins); m[t] = lp[t][fid[t]], float32.
+ *   tokens      frame t starts a run if t == 0 or fid[t] != fid[t-1]; blank runs are runs.  Every non-blank run is a token:
+ *               id[i], first[i] / last[i] = the run's first and last frame (inclusive; a frame is 0.08 s), logp[i] = the
+ *               maximum of m[t] over the run (the value at the first frame that attains it: float32, exact, independent
+ *               of the order of evaluation).  The ids are those qv_decode_retrieve_rerank reports as greedy ids.
+ *   per row     n_tokens, t_frames, n_blank_frames (frames whose argmax is the blank); min_token_logprob = the smallest
+ *               logp[i] (0 without tokens); avg_logprob = sum of logp[i] / n_tokens (0.0 without tokens);
+ *               frame_avg_logprob = sum of m[t] / t_frames (0.0 without frames); flags = QV_FLAG_EMPTY_TRANSCRIPT when there
+ *               is no token, else 0.
+ *   the sums    are float64 and formed in ONE order, so the two averages are reproducible bit for bit: the elements are
+ *               converted to double; lane l of 64 adds the elements l, l + 64, l + 128, ... in ascending order starting
+ *               from +0.0; the 64 partial sums are combined by p[l] = p[l] + p[l ^ o] for o = 32, 16, 8, 4, 2, 1 (addition
+ *               commutes: all lanes end with the same value); one IEEE double division by the count follows.
+ *   -inf        maxima propagate as IEEE says (a frame of -inf everywhere yields token 0 with logp = -inf).  Valid frames
+ *               hold no NaN.
+ * Output rows are `pitch` entries apart, pitch >= t_max.  Entries past n_tokens hold -1 in ids / first / last and 0 in logp.
+ * logp_host, first_host and last_host may each be NULL.  NULL info_host / ids_host / input pointer, batch < 1, t_max < 1,
+ * pitch < t_max, a t_host[b] outside 0..t_max: QV_ERR_ARG; batch above max_batch or t_max above the engine's frame capacity:
+ * QV_ERR_CAPACITY.  The workspace (per row of max_batch a record of 40 + 12 * frame capacity bytes in device memory plus a
+ * pinned mirror) belongs to the current execution context and is allocated by the first call that uses it; one
+ * device-to-host copy per call.  Independent of the retrieval state: results of an earlier batch stay fetchable. */
+typedef struct {
+    int32_t n_tokens, t_frames, n_blank_frames, flags;
+    float   min_token_logprob, reserved_f;
+    double  avg_logprob, frame_avg_logprob;
+} qv_transcript_info;
+
+/* on the caller's log-probs; works on an engine without a model.  SYNCHRONOUS on `stream`. */
+int qv_transcribe(qv_engine *e, const float *logprobs_dev, const int32_t *t_host, int32_t batch, int32_t t_max,
+                  qv_transcript_info *info_host, int32_t *ids_host,
+                  float *logp_host, int16_t *first_host, int16_t *last_host,
+                  int32_t pitch, void *stream);
+/* the forward (as qv_predict_batch runs it: audio_dev f32[batch, n_max], zero padded) into the current context's own log-prob
+ * workspace, then the same kernel; t_max = qv_frames_for_samples(longest row).  Waits for batches in flight first (their
+ * results stay fetchable, but a batch whose log-probs lived in that workspace is forgotten by qv_align_results_ctx /
+ * qv_nbest_results_ctx / qv_debug_transcript_codes: ask them before transcribing).  SYNCHRONOUS like
+ * qv_predict_batch.  An engine without a model: QV_ERR_NO_MODEL. */
+int qv_transcribe_batch(qv_engine *e, const float *audio_dev, const int64_t *lengths_host,
+                        int32_t batch, int64_t n_max,
+                        qv_transcript_info *info_host, int32_t *ids_host,
+                        float *logp_host, int16_t *first_host, int16_t *last_host,
+                        int32_t pitch, void *stream);
+
 /* Device pointer of the packed (surah, ayah, ayah_end, float-bits(score)) i32[B,4] rows of the
  * last async call -- the payload of the per-batch RCCL all-gather. */
 const int32_t *qv_packed_results_dev(qv_engine *e);

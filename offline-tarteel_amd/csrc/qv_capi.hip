@@ -596,6 +596,7 @@ extern "C" void qv_destroy(qv_engine *e) {
         if (c.align.out_host) (void)hipHostFree(c.align.out_host);
         if (c.align.in_host) (void)hipHostFree(c.align.in_host);
         if (c.nbest.out_host) (void)hipHostFree(c.nbest.out_host);
+        if (c.transcribe.host) (void)hipHostFree(c.transcribe.host);
         if (c.stream) (void)hipStreamDestroy(c.stream);
         if (c.in_ready) (void)hipEventDestroy(c.in_ready);
         if (c.done) (void)hipEventDestroy(c.done);
@@ -1088,6 +1089,50 @@ extern "C" int qv_nbest_select(qv_engine *eng, const double *final_host, const f
     for (int r = 0; r < rows; ++r)
         if (n_host[r] < 0 || n_host[r] > pitch) { qv_set_error(eng, "qv_nbest_select: n_host[r] outside 0..pitch"); return QV_ERR_ARG; }
     return qv_nbest_select_rows(eng, c, final_host, loss_host, n_host, rows, pitch, k, index_host, count_host, (hipStream_t)stream);
+}
+
+// ---- transcription with confidence (qv_transcribe.hip) ---------------------------------------------------------------
+extern "C" int qv_transcribe(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch, int32_t t_max,
+                             qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host,
+                             int16_t *last_host, int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!lp || !t_host || !info_host || !ids_host || batch < 1 || t_max < 1 || pitch < t_max) {
+        qv_set_error(eng, "qv_transcribe: null argument, empty batch, t_max < 1 or pitch < t_max");
+        return QV_ERR_ARG;
+    }
+    QV_ORDERED(eng, stream);
+    return qv_transcribe_rows(eng, eng->ctx[eng->cur_ctx], lp, t_host, batch, t_max, info_host, ids_host, logp_host, first_host,
+                              last_host, pitch, (hipStream_t)stream);
+}
+
+extern "C" int qv_transcribe_batch(qv_engine *eng, const float *audio_dev, const int64_t *lengths_host, int32_t batch, int64_t n_max,
+                                   qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host,
+                                   int16_t *last_host, int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    if (!audio_dev || !lengths_host || !info_host || !ids_host || batch < 1) {
+        qv_set_error(eng, "qv_transcribe_batch: null argument or empty batch");
+        return QV_ERR_ARG;
+    }
+    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "qv_transcribe_batch: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    int64_t lmax = 0;
+    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
+    const int t_max = qv_frames_for_samples(lmax);
+    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "qv_transcribe_batch: audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    if (t_max < 1 || pitch < t_max) { qv_set_error(eng, "qv_transcribe_batch: pitch < qv_frames_for_samples(longest row)"); return QV_ERR_ARG; }
+    QV_ORDERED(eng, stream);
+    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
+    QV_TRY(quiesce_contexts(eng));
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
+    std::vector<int32_t> t_out(batch);
+    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max, t_out.data(),
+                              (hipStream_t)stream, /*zero_pad_rows=*/false);
+    if (rc) return rc;
+    return qv_transcribe_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, info_host, ids_host, logp_host, first_host, last_host,
+                              pitch, (hipStream_t)stream);
 }
 
 extern "C" int qv_debug_forward_tap(qv_engine *eng, int32_t what, int32_t layer, float *out_dev, void *stream) {

@@ -228,6 +228,19 @@ int qv_nbest_results(qv_engine *eng, int k_ctx, int batch, int k, int flags, qv_
 int qv_nbest_select_rows(qv_engine *eng, QvCtx &c, const double *final_host, const float *loss_host, const int32_t *n_host, int rows,
                          int pitch, int k, int32_t *index_host, int32_t *count_host, hipStream_t stream);
 
+// transcription with confidence (qv_transcribe.hip).  One record per row -- qv_transcript_info, then ids / logp / first /
+// last with P = t_max rounded up to even entries each -- so a batch comes back in ONE copy into the pinned mirror.
+// Per-context workspace, allocated by the first transcription call on that context (dev == nullptr: not yet): the rows'
+// frame counts in the first t_bytes, the records behind them; `host` mirrors it.
+struct QvTranscribeWs {
+    unsigned char *dev;
+    unsigned char *host;
+    size_t t_bytes;
+};
+int qv_transcribe_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max,
+                       qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host, int16_t *last_host,
+                       int pitch, hipStream_t stream);
+
 // post-logits launchers (qv_postlogits.hip); `c` is the execution context whose workspace and staging slots the call uses
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,
@@ -308,6 +321,8 @@ struct QvCtx {
     QvAlignWs align = {};
     // ranked alternatives (qv_nbest_results_ctx): the same batch, read from the candidate arrays of `work`
     QvNbestWs nbest = {};
+    // transcription with confidence (qv_transcribe, qv_transcribe_batch): independent of the batch state above
+    QvTranscribeWs transcribe = {};
 };
 
 struct qv_engine {

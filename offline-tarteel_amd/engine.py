@@ -101,6 +101,18 @@ NBEST_ENTRY_DTYPE = np.dtype([("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<
 NBEST_INFO_DTYPE = np.dtype([("n_entries", "<i4"), ("n_ranked", "<i4"), ("source", "<i4"), ("flags", "<i4")])
 assert NBEST_ENTRY_DTYPE.itemsize == C.sizeof(QvNbestEntry) == 56 and NBEST_INFO_DTYPE.itemsize == C.sizeof(QvNbestInfo) == 16
 
+class QvTranscriptInfo(C.Structure):
+    """include/qverse.h: qv_transcript_info"""
+    _fields_ = [("n_tokens", C.c_int32), ("t_frames", C.c_int32), ("n_blank_frames", C.c_int32), ("flags", C.c_int32),
+                ("min_token_logprob", C.c_float), ("reserved_f", C.c_float),
+                ("avg_logprob", C.c_double), ("frame_avg_logprob", C.c_double)]
+
+
+TRANSCRIPT_INFO_DTYPE = np.dtype([("n_tokens", "<i4"), ("t_frames", "<i4"), ("n_blank_frames", "<i4"), ("flags", "<i4"),
+                                  ("min_token_logprob", "<f4"), ("reserved_f", "<f4"),
+                                  ("avg_logprob", "<f8"), ("frame_avg_logprob", "<f8")])
+assert TRANSCRIPT_INFO_DTYPE.itemsize == C.sizeof(QvTranscriptInfo) == 40
+
 RESULT_DTYPE = np.dtype([
     ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("source", "<i4"),
     ("score", "<f8"), ("base_score", "<f8"), ("ctc_norm_loss", "<f4"),
@@ -158,6 +170,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_align_results_ctx.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32]
     lib.qv_nbest_results_ctx.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.qv_nbest_select.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.qv_transcribe.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_transcribe_batch.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_tracker_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -201,7 +215,14 @@ def env_knobs() -> dict:
         threshold=float(os.getenv("CTC_DIRECT_THRESHOLD", "0.80")),
         text_weight=float(os.getenv("CTC_DIRECT_TEXT_WEIGHT", "0.0")),
         span_penalty=float(os.getenv("CTC_DIRECT_SPAN_PENALTY", "0.5")),
+        stream_gate=stream_gate_default(),   # QVERSE_STREAM_GATE: not a qv_config field (Engine.__init__ takes it out)
     )
+
+
+def stream_gate_default() -> bool:
+    """QVERSE_STREAM_GATE=1: the engine-backed streaming row gates its chunks by the engine's own confidence
+    (StreamingPipeline.run_on_audio_chunked[_batch], confidence_gate=None).  Off by default."""
+    return os.getenv("QVERSE_STREAM_GATE", "0") == "1"
 
 
 class Engine:
@@ -239,6 +260,7 @@ class Engine:
         self.contexts = int(contexts)
         kn = env_knobs()
         kn.update(knobs)
+        kn.pop("stream_gate", None)   # read by the streaming row when it runs, not by the engine
         for k, v in kn.items():
             setattr(cfg, k, v)
         self.cfg = cfg
@@ -784,9 +806,68 @@ class Engine:
         return {"surah": s, "ayah": a, "ayah_end": a + span - 1 if span > 1 else None, "score": sc.value,
                 "n_words": n_words, "verse": v, "span": span}
 
-    def transcribe_batch(self, audio, lengths) -> list[str]:
+    def _transcripts(self, info, ids, logp, first, last) -> list[dict]:
+        out = []
+        # (whole arrays to Python objects at once: per-element numpy scalar access would cost more than the device call)
+        for b, (n, t, n_blank, flags, mn, _, avg, favg) in enumerate(info.tolist()):
+            row = ids[b, :n].tolist()
+            out.append({
+                "text": self.transcript_of(row),
+                "avg_logprob": avg, "frame_avg_logprob": favg, "min_token_logprob": mn, "n_tokens": n, "t_frames": t,
+                "n_blank_frames": n_blank, "flags": flags,
+                "tokens": [{"id": i, "first": f, "last": l, "logp": p}
+                           for i, f, l, p in zip(row, first[b, :n].tolist(), last[b, :n].tolist(), logp[b, :n].tolist())],
+            })
+        return out
+
+    def transcribe_raw(self, log_probs, t_frames, pitch: int | None = None):
+        """qv_transcribe as arrays: (info [B] of TRANSCRIPT_INFO_DTYPE, ids int32 [B, pitch], logp float32, first / last
+        int16 [B, pitch]); entries past a row's n_tokens hold -1 (ids, first, last) and 0 (logp)."""
+        torch = self.torch
+        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        B, t_max, V = log_probs.shape
+        assert V == 1025 and len(t_frames) == B
+        pitch = t_max if pitch is None else int(pitch)
+        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        info = np.zeros(B, dtype=TRANSCRIPT_INFO_DTYPE)
+        ids = np.zeros((B, max(pitch, 1)), np.int32)
+        logp = np.zeros((B, max(pitch, 1)), np.float32)
+        first, last = np.zeros((B, max(pitch, 1)), np.int16), np.zeros((B, max(pitch, 1)), np.int16)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_transcribe(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, p(info), p(ids), p(logp), p(first),
+                                    p(last), pitch, self._stream())
+        self._check(rc, "qv_transcribe")
+        return info, ids, logp, first, last
+
+    def transcribe_logprobs(self, log_probs, t_frames) -> list[dict]:
+        """Greedy transcription with confidence (qv_transcribe) of float32 cuda log-probs [B, t_max, 1025] with t_frames[b]
+        valid frames.  Per row a dict: "text" (transcript_of the ids), "avg_logprob" (mean over the tokens of each token's
+        best frame), "frame_avg_logprob" (mean over the frames of the frame's maximum), "min_token_logprob", "n_tokens",
+        "t_frames", "n_blank_frames", "flags", and "tokens": [{"id", "first", "last" (encoder frames, inclusive; a frame is
+        0.08 s), "logp"}].  One kernel, one copy back; definitions in include/qverse.h."""
+        return self._transcripts(*self.transcribe_raw(log_probs, t_frames))
+
+    def transcribe_batch(self, audio, lengths, confidence: bool = False):
         """Forward + greedy CTC decode of a zero-padded batch (float32 cuda [B, N]); the
-        transcript of each row as c2c-direct/run.py:187-204 returns it."""
+        transcript of each row as c2c-direct/run.py:187-204 returns it.  confidence=True: one dict per row as
+        transcribe_logprobs returns it (qv_transcribe_batch: the forward into the engine's own workspace, argmax, collapse
+        and confidence on the device) -- a reference-style {"text", "avg_logprob"} transcriber result."""
+        if confidence:
+            torch = self.torch
+            assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
+            B, N = audio.shape
+            ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+            assert len(ln) == B and ln.max() <= N
+            pitch = self.frames_for(int(ln.max()))
+            info = np.zeros(B, dtype=TRANSCRIPT_INFO_DTYPE)
+            ids = np.zeros((B, pitch), np.int32)
+            logp = np.zeros((B, pitch), np.float32)
+            first, last = np.zeros((B, pitch), np.int16), np.zeros((B, pitch), np.int16)
+            p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+            rc = self.lib.qv_transcribe_batch(self.h, C.c_void_p(audio.data_ptr()), p(ln), B, N, p(info), p(ids), p(logp), p(first),
+                                              p(last), pitch, self._stream())
+            self._check(rc, "qv_transcribe_batch")
+            return self._transcripts(info, ids, logp, first, last)
         lp, T = self.forward(audio, lengths)
         ids = lp.argmax(-1).cpu().numpy()
         out = []

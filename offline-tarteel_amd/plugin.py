@@ -224,6 +224,19 @@ def transcribe(audio_path: str) -> str:
     return eng.transcript_of(dedup)
 
 
+def transcribe_detailed(audio_path: str) -> dict:
+    """transcribe() with confidence: {"text", "avg_logprob", "frame_avg_logprob", "min_token_logprob", "n_tokens",
+    "t_frames", "tokens": [{"id", "first", "last", "logp"}], ...} from Engine.transcribe_batch(confidence=True) -- argmax,
+    collapse and the confidence figures in one kernel on the device.  Usable as a reference-style ``transcribe_fn`` that
+    returns a dict (shared/streaming.py:158-166 reads "text" and "avg_logprob")."""
+    import torch
+
+    eng = _ensure_engine()
+    audio = load_audio(audio_path)
+    dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
+    return eng.transcribe_batch(dev, [len(audio)], confidence=True)[0]
+
+
 def model_size() -> int:
     wp = weights_path()
     return wp.stat().st_size if wp is not None and wp.exists() else 0

@@ -179,13 +179,14 @@ class StreamingPipeline:
         return out
 
     # ------------------------------------------------------------------ audio -----
-    def transcribe_chunks(self, chunk_lists: list[list[np.ndarray]]) -> list[list[str]]:
-        """Every chunk of every recording through the engine, in packed ragged batches."""
+    def transcribe_chunks(self, chunk_lists: list[list[np.ndarray]], confidence: bool = False) -> list[list]:
+        """Every chunk of every recording through the engine, in packed ragged batches.  confidence=True: a dict per chunk
+        ({"text", "avg_logprob", ...}, Engine.transcribe_batch(confidence=True)) in place of the bare text."""
         import torch
 
         eng = self._eng()
         flat = [c for chunks in chunk_lists for c in chunks]
-        texts: list[str] = []
+        texts: list = []
         cap = int(eng.max_batch)
         for i in range(0, len(flat), cap):
             part = flat[i:i + cap]
@@ -194,7 +195,10 @@ class StreamingPipeline:
             for j, c in enumerate(part):
                 host[j, :len(c)] = c
             dev = torch.from_numpy(host).cuda(eng.device)
-            texts.extend(eng.transcribe_batch(dev, [len(c) for c in part]))
+            if confidence:
+                texts.extend(eng.transcribe_batch(dev, [len(c) for c in part], confidence=True))
+            else:
+                texts.extend(eng.transcribe_batch(dev, [len(c) for c in part]))
         out, k = [], 0
         for chunks in chunk_lists:
             out.append(texts[k:k + len(chunks)])
@@ -220,11 +224,21 @@ class StreamingPipeline:
         return np.asarray(audio, dtype=np.float32)
 
     def run_on_audio_chunked_batch(self, audio_paths, transcribe_fn=None, chunk_seconds: float = 3.0,
-                                   overlap_seconds: float = 0.0) -> list[list[dict]]:
-        """run_on_audio_chunked for several recordings (paths or float32 arrays) at once."""
+                                   overlap_seconds: float = 0.0, confidence_gate: bool | None = None) -> list[list[dict]]:
+        """run_on_audio_chunked for several recordings (paths or float32 arrays) at once.
+
+        confidence_gate (engine-backed walk only, transcribe_fn=None): True = every chunk comes back from the engine as a
+        {"text", "avg_logprob", ...} dict, so the reference's gate (:156-178: avg_logprob < -1.0 or fewer than 2 words
+        skips the chunk and ages a held tentative emission) applies as it does to a caller's dict-returning transcribe_fn;
+        None = QVERSE_STREAM_GATE=1 in the environment; default off (bare texts, nothing gated).  A caller's transcribe_fn
+        is never affected."""
         chunk_lists = [split_chunks(self._load(a), chunk_seconds, overlap_seconds) for a in audio_paths]
         if transcribe_fn is None:
-            raws = self.transcribe_chunks(chunk_lists)
+            if confidence_gate is None:
+                from .engine import stream_gate_default
+
+                confidence_gate = stream_gate_default()
+            raws = self.transcribe_chunks(chunk_lists, confidence=True) if confidence_gate else self.transcribe_chunks(chunk_lists)
         states = [_ChunkState(self._tracker(streaming_mode=True)) for _ in chunk_lists]
         for k in range(max((len(c) for c in chunk_lists), default=0)):
             live, gens = [], []
@@ -241,5 +255,5 @@ class StreamingPipeline:
         return [s.finish() for s in states]
 
     def run_on_audio_chunked(self, audio_path, transcribe_fn=None, chunk_seconds: float = 3.0,
-                             overlap_seconds: float = 0.0) -> list[dict]:
-        return self.run_on_audio_chunked_batch([audio_path], transcribe_fn, chunk_seconds, overlap_seconds)[0]
+                             overlap_seconds: float = 0.0, confidence_gate: bool | None = None) -> list[dict]:
+        return self.run_on_audio_chunked_batch([audio_path], transcribe_fn, chunk_seconds, overlap_seconds, confidence_gate)[0]
