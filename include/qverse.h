@@ -435,7 +435,9 @@ int qv_debug_transcript_codes(qv_engine *e, int32_t ctx, int32_t batch, uint8_t 
  * 3 = norm_conv output, 4 = GLU output, 5 = depthwise conv + BatchNorm + Swish output of layer `layer`,
  * each f32[B, t_max, 512]; 6 = conv.2 output f32[B, t2_max, 20, 256], 7 = ReLU(conv.3) (same shape),
  * 8 = conv.5 output f32[B, t_max, 10, 256], 9 = ReLU(conv.6) f32[B, t_max, 10, 256] (rows past an
- * utterance's length are unspecified for 6..9). */
+ * utterance's length are unspecified for 6..9).  f16 front end only: 11 = conv.2 output (the first depthwise
+ * convolution, what k_sub01 or the two-kernel path wrote) converted to f32[B, t2_max, 20, 256], t2_max = the longest
+ * clip's count (rows past an utterance's length are that stage's values on zero padding). */
 int qv_debug_forward_tap(qv_engine *e, int32_t what, int32_t layer, float *out_dev, void *stream);
 
 /* Measurement hooks for bench.py's roofline line: while enabled, every GEMM launch of the
@@ -482,8 +484,16 @@ int qv_debug_attention_variant(int32_t mode);
  * off at every ayah end; which 3 (QVERSE_FWD_GRAPH): the forward of an engine with more than one context -- 0 = plain
  * launches, 1 = a shape that repeats on a context is captured once and replayed as one hipGraph launch; which 4
  * (QVERSE_CTC): the alpha recursion of the CTC rerank -- 0 = the wave program of rounds 1-5, 1 = the parity-specialised
- * one (two-term log-sum-exp for blank states).  The variants of a kernel produce identical bits. */
+ * one (two-term log-sum-exp for blank states); which 5 (QVERSE_SUB_RUN): how many tiles of four conv.2 frames one block
+ * of the fused subsampling kernel walks -- 0 = chosen from the launch shape, 1 / 2 = one / two tiles, 3 = the most a block
+ * ever walks (16).  The variants of a kernel produce identical bits. */
 int qv_debug_kernel_variant(int32_t which, int32_t mode);
+
+/* The forward's own frame arithmetic, for the tests: frames_out[0..3] = log-mel frames of a clip of n_samples and its
+ * frame counts after conv.0, conv.2 and conv.5 (the last one is the encoder's); run_tiles_out (optional) = tiles of four
+ * conv.2 frames a block of the fused subsampling kernel walks when `batch` clips, the longest of n_samples, are launched
+ * under the current which-5 variant. */
+int qv_debug_sub01_plan(int64_t n_samples, int32_t batch, int32_t *frames_out, int32_t *run_tiles_out);
 
 /* How many forwards of this engine were replayed as a hipGraph launch, and how many graphs were captured, since creation
  * (tests / bench.py: shows that the replay path -- and not the plain launches -- is what ran). */

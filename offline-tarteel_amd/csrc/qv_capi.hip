@@ -1185,6 +1185,13 @@ extern "C" int qv_debug_kernel_variant(int32_t which, int32_t mode) {
     return QV_OK;
 }
 
+extern "C" int qv_debug_sub01_plan(int64_t n_samples, int32_t batch, int32_t *frames_out, int32_t *run_tiles_out) {
+    if (n_samples < 400 || batch < 1 || !frames_out) return QV_ERR_ARG;
+    qv_model_frame_counts(n_samples, frames_out);
+    if (run_tiles_out) *run_tiles_out = qv_sub01_run_tiles(batch, frames_out[2]);
+    return QV_OK;
+}
+
 extern "C" int qv_debug_forward_graph_stats(qv_engine *eng, int64_t *replays, int64_t *captures) {
     QV_SERIALISE(eng);
     if (!eng || !eng->model || !replays || !captures) return QV_ERR_ARG;

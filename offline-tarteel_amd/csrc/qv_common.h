@@ -273,6 +273,8 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio_dev, 
                      bool zero_pad_rows = false,    // true: rows t >= T[b] of logprobs_dev are zeroed (the public qv_forward)
                      bool may_graph = false);       // true: `stream` is one of the engine's own (capturable) context streams
 int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *out_dev, hipStream_t stream);
+// frames of a clip of n_samples after the log-mel front end and after each of the three stride-2 stages (the forward's own arithmetic)
+void qv_model_frame_counts(int64_t n_samples, int32_t out[4]);
 int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int k, int which, int iters, double *avg_us, double *flops, hipStream_t s);
 int qv_model_replay_kernel(qv_engine *eng, QvModel *m, int k, int which, char *name_out, int cap);
 

@@ -21,6 +21,8 @@ void launch_conv0(const float *feats, int tm_max, const int32_t *len_in, const d
 void launch_sub01(const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0,
                   const float *b0, const int32_t *len1, const float *w1, const float *b1, half_t *out, int t2_max, int batch,
                   hipStream_t s);
+// tiles of four c1 frames per block of k_sub01 at this launch shape (and the current QV_KV_SUB_RUN)
+int qv_sub01_run_tiles(int batch, int t2_max);
 void launch_dwconv2d(const half_t *in, int tin_max, int fin, const int32_t *len_in, const float *w, const float *bias,
                      half_t *out, int tout_max, int fout, int batch, hipStream_t s);
 void launch_pack_rows(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, half_t *y,

@@ -277,122 +277,192 @@ __global__ __launch_bounds__(256) void k_dwconv2d(const half_t *__restrict__ in,
 // zero rows t >= len[b] of a channels-last f16 activation (so the next strided stage and the
 // out-projection see exactly what the unpadded single-utterance run sees)
 // conv0 + ReLU + first depthwise conv in one kernel: the [B][T1][40][256] activation (657 MB at
-// B = 64 x 10 s) never goes to HBM.  Block = (64-channel group, 4 output frames, utterance): the
-// 19 normalised mel rows it needs sit in LDS, the 9 x 40 x 64 conv0 tile is computed once into LDS
-// as f16 (same rounding as the two-kernel path), then the depthwise 3x3/s2 reads it from there.
-// Both convolutions are per-channel, so the only redundancy is the one-row halo (9 rows per 8).
-#define SUB_TT 4                    // c1 frames per block
-#define SUB_R1 (2 * SUB_TT + 1)     // c0 rows per block
-#define SUB_RM (2 * SUB_R1 + 1)     // mel rows per block
-#define SUB_CG 64                   // channels per block
+// B = 64 x 10 s) never goes to HBM.  A block walks a RUN of consecutive tiles of one utterance (a tile = 4 output frames
+// = 8 new conv0 rows + the row before them), 64 channels at a time: conv0 of the 8 new rows goes through the f32 matrix
+// pipe into an LDS tile as f16 (same rounding as the two-kernel path), the depthwise 3x3/s2 reads it from there.
+//   * loop order "channel group outer, tiles inner": a group's weights of both convolutions are fetched once and stay in
+//     registers for the whole run (21 conv0 values per lane: a wave owns ONE 32-channel half; 40 depthwise values per
+//     thread: 4 channels), and the statistics -> mean / rstd are formed once per block
+//   * no halo inside a run: the last conv0 row of a tile is the first of the next one; the wave that computes it stores
+//     it twice (tile row 8 and the other one of two halo rows), so nothing is recomputed or copied.  A step is then
+//     8 x 40 = 320 positions = exactly 10 position tiles of 32 = 20 (position tile, channel half) units, five per wave;
+//     only the first step of a pass also computes the halo row (one more unit per wave)
+//   * rows outside [0, len1) -- the depthwise conv's zero padding -- are written as zeros by the conv0 epilogue itself
+//   * depthwise stage: 80 positions x 16 four-channel chunks = 1,280 items, five per thread
+//   * the 19 mel rows of the next step are requested before the current step's products and normalised into the other
+//     row buffer behind its depthwise stage
+// Every output element is formed by the same instructions on the same operands whatever the run length (and as in the
+// two-kernel path): the run length only decides which block forms it.
+// LDS tile: position p (row * 40 + f) owns 64 channels at a pitch of 136 bytes.  The conv0 epilogue stores 8 bytes per
+// lane for 32 consecutive positions: 32 x 136 bytes touch every bank pair once.  The depthwise stage reads 8 bytes per
+// lane, 16 lanes per position; lanes 0-15 / 16-31 of a half-wave read output frames tl / tl + 1, whose inputs lie
+// 80 positions = 42.5 x 256 bytes apart: the two 128-byte pieces fall on the two halves of the 64 banks.  The second halo
+// row starts at a multiple of 256 bytes for the same reason.
+#define SUB_TT 4                    // c1 frames per tile
+#define SUB_R1 (2 * SUB_TT + 1)     // c0 rows per tile
+#define SUB_RM (2 * SUB_R1 + 1)     // mel rows per tile
+#define SUB_CG 64                   // channels per pass
+#define SUB_PP 68                   // halves per position of the LDS tile (136 bytes)
+#define SUB_HALO1 24576             // halves: the second halo row (49,152 bytes = 192 x 256, behind rows 0 .. 8)
+#define SUB_MAX_RUN 16              // tiles a block walks at most
+#define SUB_MEL_PER_THREAD ((SUB_RM * QV_NMEL + 255) / 256)
 __global__ __launch_bounds__(256) void k_sub01(const float *__restrict__ feats, int tm_max, const int32_t *__restrict__ len_mel,
                                                const double *__restrict__ stats, const float *__restrict__ w0t,
                                                const float *__restrict__ b0, const int32_t *__restrict__ len1,
                                                const float *__restrict__ w1t, const float *__restrict__ b1,
-                                               half_t *__restrict__ out, int t2_max) {
-    __shared__ __attribute__((aligned(16))) float rows[SUB_RM][QV_NMEL + 2];
+                                               half_t *__restrict__ out, int t2_max, int run) {
+    __shared__ __attribute__((aligned(16))) float rows[2][SUB_RM][QV_NMEL + 2];
     __shared__ float mean_s[QV_NMEL], rstd_s[QV_NMEL];
-    // conv0 tile, position-major: position p = row * 40 + f owns 64 channels = eight 16-byte chunks; chunk c is stored at
-    // ((c + p) & 7) so that the 8-byte stores of the conv0 epilogue (32 positions x 2 halves per wave) spread over the banks
-    __shared__ __attribute__((aligned(16))) half_t tile[SUB_R1 * 40][SUB_CG];
-    // both convolutions' taps (rows 0 .. 8) and biases (row 9) for all 256 channels: fetched once per block, next to the mel
-    // rows' latency (per channel group from global memory they were 72 load instructions per thread and a latency in
-    // front of every group's matrix products)
-    __shared__ __attribute__((aligned(16))) float w0s[10][QV_SUBC], w1s[10][QV_SUBC];
-    // ~73 KB of static LDS: gfx950 only (160 KB per CU, two blocks resident); every other target stops at 64 KB per block
-    static_assert(sizeof(rows) + sizeof(tile) + sizeof(w0s) + sizeof(w1s) + sizeof(mean_s) + sizeof(rstd_s) <= 80 * 1024,
+    __shared__ __attribute__((aligned(256))) half_t tile[SUB_HALO1 + 40 * SUB_PP];
+    static_assert(SUB_HALO1 >= SUB_R1 * 40 * SUB_PP && (SUB_HALO1 * 2) % 256 == 0, "k_sub01: the second halo row lies behind the tile");
+    // ~68 KB of static LDS: gfx950 only (160 KB per CU, two blocks resident); every other target stops at 64 KB per block
+    static_assert(sizeof(rows) + sizeof(tile) + sizeof(mean_s) + sizeof(rstd_s) <= 80 * 1024,
                   "k_sub01: two blocks per CU need <= 80 KB of LDS each");
-    const int b = blockIdx.z, t2_0 = blockIdx.y * SUB_TT, tid = threadIdx.x;
+    const int b = blockIdx.z, tid = threadIdx.x;
+    const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT;
+    const int tile0 = blockIdx.y * run;                                     // first tile of the run
+    const int nk = n_tiles - tile0 < run ? n_tiles - tile0 : run;           // tiles this block walks (>= 1 by the grid)
     const int tin = len_mel[b], l1 = len1[b];
     const float *x = feats + (size_t)b * tm_max * QV_NMEL;
-    if (tid < QV_NMEL) mel_mean_rstd(stats, b, tid, tin, mean_s[tid], rstd_s[tid]);
-    for (int i = tid; i < 10 * QV_SUBC / 4; i += 256) {
-        const int k = i / (QV_SUBC / 4), c = (i % (QV_SUBC / 4)) * 4;
-        *(f32x4 *)&w0s[k][c] = *(const f32x4 *)((k < 9 ? w0t + k * QV_SUBC : b0) + c);
-        *(f32x4 *)&w1s[k][c] = *(const f32x4 *)((k < 9 ? w1t + k * QV_SUBC : b1) + c);
-    }
-    __syncthreads();
-    const int t1_0 = 2 * t2_0 - 1;         // first c0 row of the tile
-    const int tm_0 = 2 * t1_0 - 1;         // first mel row
-    for (int i = tid; i < SUB_RM * (QV_NMEL + 2); i += 256) {
-        int r = i / (QV_NMEL + 2), f = i % (QV_NMEL + 2) - 1, t = tm_0 + r;
-        rows[r][f + 1] = (t >= 0 && t < tin && f >= 0 && f < QV_NMEL) ? (x[t * QV_NMEL + f] - mean_s[f]) * rstd_s[f] : 0.f;
-    }
-    const int c8 = (tid & 7) * 8, pl = tid >> 3;   // depthwise stage: 8 channels per thread, 32 positions per pass
     const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+    const int ct = wave & 1, pt0 = wave >> 1;           // conv0 stage: the wave's channel half, its position tiles pt0 + 2 i
+    // depthwise stage: 4 channels; frame tlb + 2 (wave >> 1) of the tile, positions fq .. fq + 4
+    const int c4 = (tid & 15) * 4, tlb = (tid >> 4) & 1, th = wave >> 1, fq = ((tid >> 5) & 3) * 5;
     int koff[5];
     conv0_tap_offsets(hi, koff);
-    // Round 4: the block walks the four 64-channel groups itself (the grid had one block per group: four blocks each
-    // waited for the statistics, fetched and normalised the same 19 mel rows -- three global latencies in front of
-    // ~7 k cycles of arithmetic, the larger part of a block's life).  The tile is reused from group to group.
+    // the mel rows of tile `tl`: row r is mel frame 16 tl - 3 + r.  Requested here, normalised and stored by mel_store
+    // (normalisation as in k_conv0: frames past the utterance and the conv padding read as 0)
+    float pf[SUB_MEL_PER_THREAD];
+    auto mel_fetch = [&](int tl) {
+#pragma unroll
+        for (int i = 0; i < SUB_MEL_PER_THREAD; ++i) {
+            // (always a load from inside the utterance: no branch around it; mel_store drops what lies outside)
+            const int e = min(tid + 256 * i, SUB_RM * QV_NMEL - 1), r = e / QV_NMEL, f = e - r * QV_NMEL;
+            const int t = min(max(16 * tl - 3 + r, 0), tin - 1);
+            pf[i] = x[t * QV_NMEL + f];
+        }
+    };
+    auto mel_store = [&](int tl, int buf) {
+#pragma unroll
+        for (int i = 0; i < SUB_MEL_PER_THREAD; ++i) {
+            const int e = tid + 256 * i, r = e / QV_NMEL, f = e - r * QV_NMEL, t = 16 * tl - 3 + r;
+            if (e < SUB_RM * QV_NMEL) rows[buf][r][f + 1] = (t >= 0 && t < tin) ? (pf[i] - mean_s[f]) * rstd_s[f] : 0.f;
+        }
+    };
+    mel_fetch(tile0);
+    if (tid < QV_NMEL) mel_mean_rstd(stats, b, tid, tin, mean_s[tid], rstd_s[tid]);
+    if (tid < 2 * 2 * SUB_RM) rows[tid & 1][(tid >> 1) % SUB_RM][(tid >> 1) / SUB_RM ? QV_NMEL + 1 : 0] = 0.f;   // the padding columns
+    __syncthreads();
+    mel_store(tile0, 0);
+    __syncthreads();
+    int it = 0;                     // steps done: step `it` reads rows[it & 1]
     for (int cg = 0; cg < QV_SUBC; cg += SUB_CG) {
-        // ---- conv0 + ReLU into the LDS tile on the f32 matrix pipe (rows outside [0, l1) are the depthwise conv's zero
-        // padding): the 360 positions are 12 tiles of 32 (the last one 8 wide), wave w owns tiles w, w + 4, w + 8 and
-        // both 32-channel halves of the group
-        {
-            __syncthreads();        // the mel rows and the weights are in LDS / the previous group's depthwise stage has left the tile
-            float wa[2][5], bc[2][16];
-            conv0_weights(&w0s[0][0], &w0s[9][0], cg, l31, hi, wa[0], bc[0]);
-            conv0_weights(&w0s[0][0], &w0s[9][0], cg + 32, l31, hi, wa[1], bc[1]);
-#pragma unroll
-            for (int pt = wave; pt < (SUB_R1 * 40 + 31) / 32; pt += 4) {
-                const int p = pt * 32 + l31, pc = p < SUB_R1 * 40 ? p : SUB_R1 * 40 - 1;
-                const int r = pc / 40, f1 = pc - r * 40;
-                float xb[5];
-                conv0_taps(&rows[0][0], 2 * r, f1, koff, xb);
-                half_t *trow = &tile[pc][4 * hi];       // lanes past the last position rewrite position 359 with its own values
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    const f32x16 acc = conv0_tile(wa[ct], bc[ct], xb);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) *(half4 *)(trow + (((ct * 4 + q + pc) & 7) << 3)) = conv0_relu4(acc, q);
-                }
-            }
-        }
-        // rows outside [0, l1) are the depthwise conv's zero padding, not conv0 outputs: only the first block of an
-        // utterance and the ones at its end have any, and they zero them behind the products
-        if (t1_0 < 0 || t1_0 + SUB_R1 > l1) {
-            __syncthreads();
-            for (int i = tid; i < SUB_R1 * 40 * (SUB_CG / 8); i += 256) {
-                const int pp = i >> 3, t1 = t1_0 + pp / 40;
-                if (t1 < 0 || t1 >= l1) *(f32x4 *)&tile[pp][(i & 7) << 3] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-        __syncthreads();            // conv0 done: the tile is complete
-        // ---- depthwise 3x3 stride 2 over the tile
-        float w[9][8], bs[8];
+        float wa[5], bc[16];
+        conv0_weights(w0t, b0, cg + 32 * ct, l31, hi, wa, bc);
+        float w[9][4], bs[4];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            const f32x4 wa = *(const f32x4 *)&w1s[k][cg + c8], wb = *(const f32x4 *)&w1s[k][cg + c8 + 4];
+            const f32x4 v = *(const f32x4 *)(w1t + k * QV_SUBC + cg + c4);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { w[k][c] = wa[c]; w[k][4 + c] = wb[c]; }
+            for (int c = 0; c < 4; ++c) w[k][c] = v[c];
         }
         {
-            const f32x4 ba = *(const f32x4 *)&w1s[9][cg + c8], bb = *(const f32x4 *)&w1s[9][cg + c8 + 4];
+            const f32x4 v = *(const f32x4 *)(b1 + cg + c4);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { bs[c] = ba[c]; bs[4 + c] = bb[c]; }
+            for (int c = 0; c < 4; ++c) bs[c] = v[c];
         }
-        for (int p = pl; p < SUB_TT * 20; p += 32) {
-            int tl = p / 20, fo = p - tl * 20, t2 = t2_0 + tl;
-            if (t2 >= t2_max) continue;
-            float acc[8];
+        for (int k = 0; k < nk; ++k, ++it) {
+            const int tl0 = tile0 + k;
+            const int t1_0 = 2 * SUB_TT * tl0 - 1;          // the halo row; the new rows are t1_0 + 1 .. t1_0 + 8
+            const float *rw = &rows[it & 1][0][0];
+            // the next step's mel rows (the first tile again behind the last step of a pass)
+            const int nxt = k + 1 < nk ? tl0 + 1 : tile0;
+            const bool more = k + 1 < nk || cg + SUB_CG < QV_SUBC;
+            if (more) mel_fetch(nxt);
+            // ---- conv0 + ReLU into the LDS tile on the f32 matrix pipe
+            if (k == 0) {           // the halo row of the run: 40 positions, wave = (position tile pt0, channel half ct)
+                const int f1 = pt0 * 32 + l31, f1c = f1 < 40 ? f1 : 39;
+                float xb[5];
+                conv0_taps(rw, 0, f1c, koff, xb);
+                const f32x16 acc = conv0_tile(wa, bc, xb);
+                if (f1 < 40) {
+                    half_t *trow = tile + f1 * SUB_PP + 32 * ct + 4 * hi;
+                    const bool zero = t1_0 < 0 || t1_0 >= l1;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) acc[c] = bs[c];
-#pragma unroll
-            for (int dt = 0; dt < 3; ++dt)
-#pragma unroll
-                for (int df = 0; df < 3; ++df) {
-                    int f = 2 * fo - 1 + df;
-                    if (f < 0 || f >= 40) continue;
-                    const int pp = (2 * tl + dt) * 40 + f;
-                    half8 v = *(const half8 *)&tile[pp][(((tid & 7) + pp) & 7) << 3];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) acc[c] = __builtin_fmaf(w[dt * 3 + df][c], (float)v[c], acc[c]);
+                    for (int q = 0; q < 4; ++q) *(half4 *)(trow + 8 * q) = zero ? half4{0, 0, 0, 0} : conv0_relu4(acc, q);
                 }
-            half8 o;
+            }
+            half_t *const halo_w = tile + ((k + 1) & 1 ? SUB_HALO1 : 0);       // where the NEXT step finds its halo row
+            const half_t *const halo_r = tile + (k & 1 ? SUB_HALO1 : 0);
+            {
+                // unit i: new positions (pt0 + 2 i) * 32 + l31 of 320, new row r = tile row r + 1.  The products of unit
+                // i + 1 are issued in front of unit i's conversion and stores
+                float xb[5];
+                conv0_taps(rw, 2 * (pt0 * 32 + l31 >= 40 ? 2 : 1), (pt0 * 32 + l31) % 40, koff, xb);
+                f32x16 acc = conv0_tile(wa, bc, xb);
 #pragma unroll
-            for (int c = 0; c < 8; ++c) o[c] = (half_t)acc[c];
-            *(half8 *)(out + (((size_t)b * t2_max + t2) * 20 + fo) * QV_SUBC + cg + c8) = o;
+                for (int i = 0; i < 5; ++i) {
+                    const int n = (pt0 + 2 * i) * 32 + l31, r = n / 40, f1 = n - r * 40;
+                    f32x16 nacc = acc;
+                    if (i + 1 < 5) {
+                        const int n2 = n + 64, r2 = n2 / 40;
+                        conv0_taps(rw, 2 * (r2 + 1), n2 - r2 * 40, koff, xb);
+                        nacc = conv0_tile(wa, bc, xb);
+                    }
+                    half_t *trow = tile + (n + 40) * SUB_PP + 32 * ct + 4 * hi;
+                    const bool zero = t1_0 + 1 + r >= l1;           // (t1_0 + 1 + r >= 0 always)
+                    half4 h[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) h[q] = zero ? half4{0, 0, 0, 0} : conv0_relu4(acc, q);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) *(half4 *)(trow + 8 * q) = h[q];
+                    if (i == 4 && r == 2 * SUB_TT - 1) {            // the tile's last row is the next step's halo row
+                        half_t *hrow = halo_w + f1 * SUB_PP + 32 * ct + 4 * hi;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) *(half4 *)(hrow + 8 * q) = h[q];
+                    }
+                    acc = nacc;
+                }
+            }
+            __syncthreads();            // conv0 done: the tile is complete
+            // ---- depthwise 3x3 stride 2 over the tile: all nine reads of an item are issued, then its 36 FMAs; the tap
+            // left of the first position (f = -1) reads position 0 instead and its FMAs are dropped
+            {
+                const int tl = tlb + 2 * th, t2 = SUB_TT * tl0 + tl;
+                const half_t *rb[3];
+#pragma unroll
+                for (int dt = 0; dt < 3; ++dt)
+                    rb[dt] = (dt == 0 && tl == 0 ? halo_r : tile + (2 * tl + dt) * 40 * SUB_PP) + c4 + (2 * fq - 1) * SUB_PP;
+                half_t *o = out + (((size_t)b * t2_max + (t2 < t2_max ? t2 : t2_max - 1)) * 20 + fq) * QV_SUBC + cg + c4;
+#pragma unroll
+                for (int i = 0; i < 5; ++i) {
+                    const bool edge = i == 0 && fq == 0;
+                    half4 v[3][3];
+#pragma unroll
+                    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+                        for (int df = 0; df < 3; ++df)
+                            v[dt][df] = *(const half4 *)(rb[dt] + (2 * i + (i == 0 && df == 0 && edge ? 1 : df)) * SUB_PP);
+                    float acc[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[c] = bs[c];
+#pragma unroll
+                    for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+                        for (int df = 0; df < 3; ++df)
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                const float a = __builtin_fmaf(w[dt * 3 + df][c], (float)v[dt][df][c], acc[c]);
+                                acc[c] = (i == 0 && df == 0 && edge) ? acc[c] : a;
+                            }
+                    half4 h;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) h[c] = (half_t)acc[c];
+                    if (t2 < t2_max) *(half4 *)(o + i * QV_SUBC) = h;
+                }
+            }
+            if (more) mel_store(nxt, (it + 1) & 1);
+            __syncthreads();            // the depthwise stage has left the tile; the next step's mel rows are in LDS
         }
     }
 }
@@ -1467,7 +1537,7 @@ void qv_kernel_variant_set(int which, int mode) {
 }
 int qv_kernel_variant(int which) {
     static const struct Env { int v[QV_KV_COUNT]; Env() {
-        const char *names[QV_KV_COUNT] = {"QVERSE_LOGMEL", "QVERSE_ORT_SUB", "QVERSE_SPANS", "QVERSE_FWD_GRAPH", "QVERSE_CTC", nullptr, nullptr, nullptr};
+        const char *names[QV_KV_COUNT] = {"QVERSE_LOGMEL", "QVERSE_ORT_SUB", "QVERSE_SPANS", "QVERSE_FWD_GRAPH", "QVERSE_CTC", "QVERSE_SUB_RUN", nullptr, nullptr};
         const int dflt[QV_KV_COUNT] = {1, 1, 1, 1, 1, 0, 0, 0};
         for (int i = 0; i < QV_KV_COUNT; ++i) {
             const char *e = names[i] ? getenv(names[i]) : nullptr;
@@ -1500,11 +1570,31 @@ void launch_conv0(const float *feats, int tm_max, const int32_t *len_in, const d
     hipLaunchKernelGGL(k_conv0, dim3(1, t1_max, batch), dim3(256), 0, s, feats, tm_max, len_in, stats, w, bias, out, t1_max);
 }
 
+// Tiles per block of k_sub01, from the launch shape alone (the forward graph is keyed on the shape; no output value depends
+// on it).  A CU holds two blocks, so the chip takes 512 at a time: the cost of a run length is (rounds of 512 blocks) x
+// (2 x tiles + 1: a block's statistics, first mel rows and halo row cost about half a tile).  64 x 10 s = 64 x 63 tiles:
+// 8 runs of 8 = 512 blocks; a small batch gets short runs and fills the chip instead.  QV_KV_SUB_RUN forces 1, 2 or
+// SUB_MAX_RUN tiles (tests: the run length changes no bit).
+int qv_sub01_run_tiles(int batch, int t2_max) {
+    const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, forced = qv_kernel_variant(QV_KV_SUB_RUN);
+    int best = 1;
+    if (forced >= 1 && forced <= 3) best = forced == 3 ? SUB_MAX_RUN : forced;
+    else {
+        long best_cost = -1;
+        for (int run = 1; run <= SUB_MAX_RUN; ++run) {
+            const long blocks = (long)batch * ((n_tiles + run - 1) / run), cost = (blocks + 511) / 512 * (2 * run + 1);
+            if (best_cost < 0 || cost < best_cost) { best = run; best_cost = cost; }
+        }
+    }
+    return best < n_tiles ? best : (n_tiles > 0 ? n_tiles : 1);
+}
+
 void launch_sub01(const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0,
                   const float *b0, const int32_t *len1, const float *w1, const float *b1, half_t *out, int t2_max, int batch,
                   hipStream_t s) {
-    hipLaunchKernelGGL(k_sub01, dim3(1, (t2_max + SUB_TT - 1) / SUB_TT, batch), dim3(256), 0, s, feats, tm_max,
-                       len_mel, stats, w0, b0, len1, w1, b1, out, t2_max);
+    const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, run = qv_sub01_run_tiles(batch, t2_max);
+    hipLaunchKernelGGL(k_sub01, dim3(1, (n_tiles + run - 1) / run, batch), dim3(256), 0, s, feats, tm_max,
+                       len_mel, stats, w0, b0, len1, w1, b1, out, t2_max, run);
 }
 
 void launch_dwconv2d(const half_t *in, int tin_max, int fin, const int32_t *len_in, const float *w, const float *bias,

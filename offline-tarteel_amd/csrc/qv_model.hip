@@ -1014,7 +1014,8 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
         // another policy is never replayed after qv_debug_gemm_tiles / QVERSE_GEMM_* changed it)
         FwdKey key = {audio, logprobs, posp, n_max,
                       {B, M, T, t3min, tm_max, t1m, t2m, t_max_out, t_min_pad, att_variant,
-                       qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB), qv_gemm_policy_epoch()}};
+                       qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB) | (qv_kernel_variant(QV_KV_SUB_RUN) << 4),
+                       qv_gemm_policy_epoch()}};
         const int64_t tick = ++a.fwd_tick;
         FwdGraph *hit = nullptr;
         for (int i = 0; i < a.n_fwd_graph; ++i)
@@ -1161,6 +1162,11 @@ int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int k, int which, int iters
     return QV_OK;
 }
 
+void qv_model_frame_counts(int64_t n_samples, int32_t out[4]) {
+    out[0] = (int32_t)(n_samples / 160 + 1);
+    for (int i = 1; i < 4; ++i) out[i] = stage_len(out[i - 1]);
+}
+
 int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *out, hipStream_t s) {
     QvActs &a = m->ctx_acts[k];
     size_t M = (size_t)a.last_rows;
@@ -1169,6 +1175,9 @@ int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *
         launch_melapply(a.feats, a.lens_dev, a.last_tm_max, a.mel_stats, out, a.last_batch, s);
     } else if (what == 10) {   // the log-mel features as k_logmel left them, [B][tm_max][80]
         QV_HIP(hipMemcpyAsync(out, a.feats, sizeof(float) * (size_t)a.last_batch * a.last_tm_max * QV_NMEL, hipMemcpyDeviceToDevice, s));
+    } else if (what == 11) {   // conv.2 output of the f16 path (k_sub01 / the two-kernel path) as it sits in HBM
+        if (m->ort || !a.c1) { qv_set_error(eng, "tap 11 exists on the f16 front end only"); return QV_ERR_ARG; }
+        launch_to_float(a.c1, out, (size_t)a.last_batch * a.last_t2m * 20 * QV_SUBC, s);
     } else if (what >= 6 && what <= 9) {
         // QV_PREC_ORT_MIXED: the dense subsampling tensors in front of / behind the quantisers, as they sit in HBM
         if (!m->ort) { qv_set_error(eng, "taps 6..9 exist under QV_PREC_ORT_MIXED only"); return QV_ERR_ARG; }

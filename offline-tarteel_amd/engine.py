@@ -189,6 +189,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_debug_attention_variant.argtypes = [i32]
     lib.qv_debug_kernel_variant.argtypes = [i32, i32]
     lib.qv_debug_forward_graph_stats.argtypes = [vp, vp, vp]
+    lib.qv_debug_sub01_plan.argtypes = [i64, i32, vp, vp]
     lib.qv_weights_info.argtypes = [vp, C.c_char_p, i32]
     lib.qv_profile_inject_logprobs.argtypes = [vp, vp, i32, vp, i32]
     lib.qv_profile_stages.argtypes = [vp, i32]
@@ -645,8 +646,9 @@ class Engine:
     def kernel_variant(self, which: int, mode: int):
         """process-wide variant of one kernel (qv_debug_kernel_variant): which 0 = log-mel FFT (0 LDS, 1 registers),
         1 = precision 2's conv.0 (0 VALU, 1 f32 matrix pipe), 2 = span pass (0 one walk per span, 1 prefix-shared),
-        3 = forward of a multi-context engine (0 plain launches, 1 hipGraph replay of a repeating shape);
-        -1 = environment / default.  Identical bits either way."""
+        3 = forward of a multi-context engine (0 plain launches, 1 hipGraph replay of a repeating shape),
+        5 = tiles of four conv.2 frames a block of the fused subsampling kernel walks (0 from the launch shape, 1 / 2 tiles,
+        3 the maximum); -1 = environment / default.  Identical bits either way."""
         self._check(self.lib.qv_debug_kernel_variant(int(which), int(mode)), "qv_debug_kernel_variant")
 
     def forward_graph_stats(self) -> dict:
@@ -925,7 +927,22 @@ class Engine:
         self._check(rc, "qv_debug_ctc_loss")
         return out
 
-    def forward_tap(self, what: int, layer: int, shape):
+    TAP_C1 = 11   # forward_tap code: conv.2 output of the f16 front end (k_sub01's own result), f32[B, t2_max, 20, 256]
+
+    def sub01_plan(self, n_samples: int, batch: int = 1) -> dict:
+        """the forward's own frame arithmetic for a clip of n_samples (qv_debug_sub01_plan): frames after the log-mel front
+        end and after conv.0 / conv.2 / conv.5, and the tiles of four conv.2 frames a block of the fused subsampling kernel
+        walks when `batch` clips, the longest of n_samples, are launched."""
+        fr, run = (C.c_int32 * 4)(), C.c_int32(0)
+        self._check(self.lib.qv_debug_sub01_plan(int(n_samples), int(batch), fr, C.byref(run)), "qv_debug_sub01_plan")
+        return {"mel": fr[0], "c0": fr[1], "c1": fr[2], "frames": fr[3], "run_tiles": run.value}
+
+    def forward_tap(self, what: int, layer: int, shape=None, c1_frames: int | None = None, batch: int | None = None):
+        """a tensor of the last forward as f32 (qv_debug_forward_tap).  what = TAP_C1 needs no `shape`: give the batch size
+        and the longest clip's conv.2 frame count (sub01_plan(...)["c1"])."""
+        if shape is None:
+            assert what == self.TAP_C1 and c1_frames and batch, "only the c1 tap derives its shape"
+            shape = (batch, c1_frames, 20, 256)
         out = self.torch.empty(shape, dtype=self.torch.float32, device=f"cuda:{self.device}")
         rc = self.lib.qv_debug_forward_tap(self.h, what, layer, C.c_void_p(out.data_ptr()), self._stream())
         self._check(rc, "qv_debug_forward_tap")
