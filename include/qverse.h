@@ -494,6 +494,10 @@ int qv_debug_kernel_variant(int32_t which, int32_t mode);
  * conv.2 frames a block of the fused subsampling kernel walks when `batch` clips, the longest of n_samples, are launched
  * under the current which-5 variant. */
 int qv_debug_sub01_plan(int64_t n_samples, int32_t batch, int32_t *frames_out, int32_t *run_tiles_out);
+/* ... and of the kernel behind it (conv.3 + conv.5 fused, which 6, no environment variable: 0 = chosen from the launch shape, 1 / 2 =
+ * one / two steps of three conv.5 frames, 3 = the most a block ever walks, 16 steps): run_frames_out = conv.5 frames one block
+ * walks when `batch` clips, the longest of n_samples, are launched under the current which-6 variant. */
+int qv_debug_sub35_plan(int64_t n_samples, int32_t batch, int32_t *run_frames_out);
 
 /* How many forwards of this engine were replayed as a hipGraph launch, and how many graphs were captured, since creation
  * (tests / bench.py: shows that the replay path -- and not the plain launches -- is what ran). */

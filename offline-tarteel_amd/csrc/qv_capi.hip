@@ -1192,6 +1192,14 @@ extern "C" int qv_debug_sub01_plan(int64_t n_samples, int32_t batch, int32_t *fr
     return QV_OK;
 }
 
+extern "C" int qv_debug_sub35_plan(int64_t n_samples, int32_t batch, int32_t *run_frames_out) {
+    if (n_samples < 400 || batch < 1 || !run_frames_out) return QV_ERR_ARG;
+    int32_t fr[4];
+    qv_model_frame_counts(n_samples, fr);
+    *run_frames_out = qv_sub35_run_frames(batch, fr[3]);
+    return QV_OK;
+}
+
 extern "C" int qv_debug_forward_graph_stats(qv_engine *eng, int64_t *replays, int64_t *captures) {
     QV_SERIALISE(eng);
     if (!eng || !eng->model || !replays || !captures) return QV_ERR_ARG;

@@ -133,7 +133,9 @@ const char *qv_gemm_kernel_name(int epi, const GemmArgs &g);
 //                                   0 = the wave program of rounds 1-5
 //   QV_KV_SUB_RUN (QVERSE_SUB_RUN)  tiles of four c1 frames a block of k_sub01 walks: 0 = chosen from the launch shape (default);
 //                                   1 / 2 = one / two tiles; 3 = the most a block ever walks (16)
-enum { QV_KV_LOGMEL = 0, QV_KV_ORT_SUB = 1, QV_KV_SPANS = 2, QV_KV_FWD_GRAPH = 3, QV_KV_CTC = 4, QV_KV_SUB_RUN = 5, QV_KV_COUNT = 8 };
+//   QV_KV_SUB35   (no variable)     steps of three c2 frames a block of k_sub35 walks: 0 = chosen from the launch shape (default);
+//                                   1 / 2 = one / two steps; 3 = the most a block ever walks (16)
+enum { QV_KV_LOGMEL = 0, QV_KV_ORT_SUB = 1, QV_KV_SPANS = 2, QV_KV_FWD_GRAPH = 3, QV_KV_CTC = 4, QV_KV_SUB_RUN = 5, QV_KV_SUB35 = 6, QV_KV_COUNT = 8 };
 int qv_kernel_variant(int which);
 void qv_kernel_variant_set(int which, int mode);   // mode < 0: back to the environment / default
 

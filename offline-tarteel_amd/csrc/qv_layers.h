@@ -27,6 +27,17 @@ void launch_dwconv2d(const half_t *in, int tin_max, int fin, const int32_t *len_
                      half_t *out, int tout_max, int fout, int batch, hipStream_t s);
 void launch_pack_rows(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, half_t *y,
                       int32_t *row_map, int batch, hipStream_t s);
+// conv.3 + ReLU + conv.5 in one kernel (k_sub35): c1 [B][t2_max][20][256] -> PACKED c2, frame t3 < len3[b] of utterance b at
+// rows (row_off[b] + t3) * 10 .. + 9 of out [10 * rows][256], and row_map[row_off[b] + t3] = b << 16 | t3
+void launch_sub35(const half_t *c1, int t2_max, const half_t *w3, const float *b3, const float *w5, const float *b5,
+                  const int32_t *len2, const int32_t *len3, const int32_t *row_off, half_t *out, int32_t *row_map, int t3_max,
+                  int batch, hipStream_t s);
+void qv_sub35_init();   // the kernel's LDS opt-in; call once outside stream capture
+// c2 frames a block of k_sub35 walks at this launch shape (and the current QV_KV_SUB35)
+int qv_sub35_run_frames(int batch, int t3_max);
+// packed f16 rows (row_off == nullptr: dense ones) -> dense f32 [B][t_max][row_elems] (valid frames only; debug taps)
+void launch_unpack_rows_f32(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, float *y,
+                            int batch, hipStream_t s);
 void launch_layernorm(const float *x, const float *g, const float *b, half_t *y, int M, hipStream_t s);
 void launch_layernorm2(float *x, const float *g1, const float *b1, const float *g2, const float *b2, half_t *y, int M,
                        hipStream_t s);

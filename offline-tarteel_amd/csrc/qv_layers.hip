@@ -481,6 +481,209 @@ __global__ void k_pack_rows(const half_t *__restrict__ x, int t_max, int row_ele
     for (int i = threadIdx.x * 8; i < row_elems; i += blockDim.x * 8) *(half8 *)(q + i) = *(const half8 *)(p + i);
 }
 
+// conv.3 (pointwise 256 -> 256) + ReLU + conv.5 (depthwise 3x3 / s2) in one kernel: the [B][T2][20][256] activation
+// between them (c1p, 164.5 MB at B = 64 x 10 s) never goes to HBM, and c2 comes out PACKED (frame t3 < len3[b] of
+// utterance b at rows (off[b] + t3) * 10 .. + 9), with row_map beside it: no k_pack_rows, no work on padding frames.
+// A block of eight waves owns one utterance and a run of consecutive c2 frames and walks it S35_TC frames a step:
+//   * a step's 2 S35_TC new c1 frames are 120 consecutive rows of c1 = one 128-row GEMM tile (8 rows of padding whose
+//     products are dropped).  They go global -> registers (MUBUF buffer_load_dwordx4, one step ahead, in flight under
+//     the products and the depthwise stage of the step before) -> LDS in the GEMM kernels' swizzled image (four
+//     64-deep K-tiles of 128-byte rows, chunk c of row r at c ^ ((r >> 1) & 7)).  Rows past the utterance's buffer
+//     read as zero through the descriptor's bounds check; nothing below reads what is computed from them.
+//   * wave w owns output channels 32 w .. 32 w + 31 and keeps ITS [32 x 256] slice of conv.3's weights in registers for
+//     the whole run (16 MFMA operand fragments = 64 VGPRs): weights are fetched once per block and never staged.
+//   * c1p of the step -- (half_t) relu(acc + bias), acc from mfma_f32_32x32x16_f16(W fragment, A fragment, acc) over
+//     K = 0, 16, .. 240 from zero: the instructions and the order of k_gemm / k_gemm256 with EPI_F16_RELU -- is written
+//     into an LDS tile as f16.  Its last frame is the next step's first: the epilogue stores it twice (tile and the
+//     other one of two halo slots); only a run's first step computes the frame in front of it.
+//   * the depthwise stage reads the tile: thread = 4 channels (lane) x positions wave, wave + 8, ..; sum from the bias,
+//     fmaf per tap, dt outer / df inner, as k_dwconv2d.  Taps outside the utterance or the frequency axis are DROPPED
+//     by selects (the row / the tap was formed from clamped addresses), never multiplied by zero; the only branch is
+//     the store guard.
+// Every output element is formed by the same instructions on the same operands whatever the run length.
+#define S35_TC 3                                    // c2 frames per step
+#define S35_ROWS (2 * S35_TC * 20)                  // new c1 rows per step (of a 128-row GEMM tile)
+#define S35_PITCH 260                               // halves per c1p row of the LDS tile (520 bytes: 32 rows x 8-byte stores touch every bank pair once)
+#define S35_A_BYTES (128 * 256 * 2)                 // the A tile
+#define S35_HALO (S35_ROWS * S35_PITCH)             // halves: the two halo slots (20 rows each) lie behind the new rows
+#define S35_LDS (S35_A_BYTES + (S35_ROWS + 40) * S35_PITCH * 2)
+#define S35_MAX_RUN 16                              // steps a block walks at most
+static_assert(S35_ROWS <= 128 && S35_LDS <= 160 * 1024, "k_sub35: one block per CU, 160 KB of LDS");
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(512, 1) void k_sub35(const half_t *__restrict__ c1, int t2_max, const half_t *__restrict__ w3,
+                                                  const float *__restrict__ b3, const float *__restrict__ w5,
+                                                  const float *__restrict__ b5, const int32_t *__restrict__ len2,
+                                                  const int32_t *__restrict__ len3, const int32_t *__restrict__ row_off,
+                                                  half_t *__restrict__ out, int32_t *__restrict__ row_map, int run) {
+    extern __shared__ __attribute__((aligned(256))) unsigned char s35[];
+    unsigned char *const sA = s35;
+    half_t *const tile = (half_t *)(s35 + S35_A_BYTES);
+    const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
+    const int l2 = len2[b], l3 = len3[b], ob = row_off[b];
+    const int t3_first = blockIdx.y * run * S35_TC;
+    if (t3_first >= l3) return;                     // (block-uniform) the run lies in the utterance's padding
+    const int t3_end = l3 < t3_first + run * S35_TC ? l3 : t3_first + run * S35_TC;
+    const int nsteps = (t3_end - t3_first + S35_TC - 1) / S35_TC;
+
+    // ---- conv.3's weights and bias of the wave's 32 channels; conv.5's of the thread's 4
+    half8 wf[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) wf[ks] = *(const half8 *)(w3 + (size_t)(wave * 32 + l31) * QV_SUBC + ks * 16 + hi * 8);
+    f32x4 bq[4];    // accumulator register r is channel 32 wave + 8 (r >> 2) + 4 hi + (r & 3)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bq[q] = *(const f32x4 *)(b3 + wave * 32 + 8 * q + 4 * hi);
+    const int c4 = lane * 4;
+    float w[9][4], bs[4];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const f32x4 v = *(const f32x4 *)(w5 + k * QV_SUBC + c4);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) w[k][c] = v[c];
+    }
+    {
+        const f32x4 v = *(const f32x4 *)(b5 + c4);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) bs[c] = v[c];
+    }
+
+    // ---- staging: piece (g, kt) of this thread = tile row 16 wave + 8 g + (lane >> 3), 16-byte chunk lane & 7 of K-tile kt
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(c1 + (size_t)b * t2_max * 20 * QV_SUBC), 0,
+                                                                        t2_max * 20 * QV_SUBC * 2, 0x00020000);
+    u32x4_t ra[8];
+    int dstA[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int row = wave * 16 + g * 8 + (lane >> 3), c = lane & 7;
+        dstA[g] = row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
+    }
+    auto fetch = [&](int row0) {    // the 128 c1 rows from row0 (>= 0) of the utterance on
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int voff = (row0 + wave * 16 + g * 8 + (lane >> 3)) * (QV_SUBC * 2) + (lane & 7) * 16;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) ra[g * 4 + kt] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, kt * 128, 0);
+        }
+    };
+    auto put = [&]() {
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) *(u32x4_t *)(sA + kt * (128 * 128) + dstA[g]) = ra[g * 4 + kt];
+    };
+    // ---- products of tile rows 64 fp .. 64 fp + 63, ReLU, f16.  Row R < n_rows goes to dst + R * pitch; a row of the
+    // step's last frame also to the halo slot `halo_w` (nullptr: none)
+    auto mm_pair = [&](int fp, half_t *dst, int n_rows, half_t *halo_w) {
+        f32x16 acc[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+            const int c = (ks & 3) * 2 + hi;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int row = fp * 64 + i * 32 + l31;
+                const half8 af = *(const half8 *)(sA + (ks >> 2) * (128 * 128) + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks], af, acc[i], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int R = fp * 64 + i * 32 + l31;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                half4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float x = acc[i][q * 4 + e] + bq[q][e];
+                    x = x > 0.f ? x : 0.f;
+                    o[e] = (half_t)x;
+                }
+                const int col = wave * 32 + 8 * q + 4 * hi;
+                if (R < n_rows) *(half4 *)(dst + R * S35_PITCH + col) = o;
+                if (halo_w && R >= S35_ROWS - 20 && R < S35_ROWS) *(half4 *)(halo_w + (R - (S35_ROWS - 20)) * S35_PITCH + col) = o;
+            }
+        }
+    };
+
+    const int row_first = 2 * t3_first * 20;        // first new c1 row of the run
+    if (t3_first > 0) {
+        // the frame in front of the run -> halo slot 0
+        fetch(row_first - 20);
+        put();
+        __syncthreads();
+        fetch(row_first);
+        mm_pair(0, tile + S35_HALO, 20, nullptr);
+        __syncthreads();
+    } else {
+        fetch(row_first);   // (frame -1 does not exist: the taps on it are dropped)
+    }
+    for (int k = 0; k < nsteps; ++k) {
+        half_t *const halo_r = tile + S35_HALO + (k & 1) * 20 * S35_PITCH;
+        half_t *const halo_w = tile + S35_HALO + ((k + 1) & 1) * 20 * S35_PITCH;
+        put();
+        __syncthreads();        // the step's rows are in LDS; the depthwise stage of the step before has left the tile
+        if (k + 1 < nsteps) fetch(row_first + (k + 1) * S35_ROWS);
+        mm_pair(0, tile, S35_ROWS, nullptr);
+        mm_pair(1, tile, S35_ROWS, halo_w);
+        __syncthreads();        // the tile is complete; the A tile is free
+        // ---- depthwise 3x3 stride 2 over the tile
+        const int t3_0 = t3_first + k * S35_TC;
+        if (tid < S35_TC && t3_0 + tid < l3) row_map[ob + t3_0 + tid] = (b << 16) | (t3_0 + tid);
+#pragma unroll
+        for (int i = 0; i < (S35_TC * 10 + 7) / 8; ++i) {
+            const int p_raw = wave + 8 * i, p = p_raw < S35_TC * 10 ? p_raw : S35_TC * 10 - 1;
+            const int tl = p / 10, fo = p - tl * 10, t3 = t3_0 + tl;
+            const bool edge = fo == 0, skip0 = t3 == 0, skip2 = 2 * t3 + 1 >= l2;
+            const half_t *rb[3];
+            rb[0] = (tl == 0 ? halo_r : tile + (2 * tl - 1) * 20 * S35_PITCH) + c4;
+            rb[1] = tile + (2 * tl) * 20 * S35_PITCH + c4;
+            rb[2] = tile + (2 * tl + 1) * 20 * S35_PITCH + c4;
+            half4 v[3][3];
+#pragma unroll
+            for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+                for (int df = 0; df < 3; ++df)
+                    v[dt][df] = *(const half4 *)(rb[dt] + (2 * fo - 1 + (df == 0 && edge ? 1 : df)) * S35_PITCH);
+            float acc[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] = bs[c];
+#pragma unroll
+            for (int dt = 0; dt < 3; ++dt) {
+                float a[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) a[c] = acc[c];
+#pragma unroll
+                for (int df = 0; df < 3; ++df)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float x = __builtin_fmaf(w[dt * 3 + df][c], (float)v[dt][df][c], a[c]);
+                        a[c] = (df == 0 && edge) ? a[c] : x;
+                    }
+                const bool skip = dt == 0 ? skip0 : dt == 2 ? skip2 : false;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[c] = skip ? acc[c] : a[c];
+            }
+            half4 h;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) h[c] = (half_t)acc[c];
+            if (p_raw < S35_TC * 10 && t3 < l3) *(half4 *)(out + ((size_t)(ob + t3) * 10 + fo) * QV_SUBC + c4) = h;
+        }
+    }
+}
+
+// packed rows (or, row_off == nullptr, dense f16 rows) -> the dense f32 view [B][t_max][row_elems] of a debug tap (frames
+// >= len[b] are left alone: the caller zeroed them)
+__global__ void k_unpack_rows_f32(const half_t *__restrict__ x, int t_max, int row_elems, const int32_t *__restrict__ len,
+                                  const int32_t *__restrict__ row_off, float *__restrict__ y) {
+    const int b = blockIdx.z, t = blockIdx.y;
+    if (t >= len[b]) return;
+    const half_t *p = x + (row_off ? (size_t)row_off[b] + t : (size_t)b * t_max + t) * row_elems;
+    float *q = y + ((size_t)b * t_max + t) * row_elems;
+    for (int i = threadIdx.x; i < row_elems; i += blockDim.x) q[i] = (float)p[i];
+}
+
 // ------------------------------------------------------------------ LayerNorm ----------
 // one wave per row of 512: f32 in -> f16 out (GEMM operand).  Two-pass variance in registers.
 __device__ __forceinline__ void ln_row(const float v[8], const float *__restrict__ gam, const float *__restrict__ bet, int lane,
@@ -1606,6 +1809,47 @@ void launch_dwconv2d(const half_t *in, int tin_max, int fin, const int32_t *len_
 void launch_pack_rows(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, half_t *y,
                       int32_t *row_map, int batch, hipStream_t s) {
     hipLaunchKernelGGL(k_pack_rows, dim3(1, t_max, batch), dim3(256), 0, s, x, t_max, row_elems, len, row_off, y, row_map);
+}
+
+// Steps of S35_TC c2 frames per block of k_sub35, from the launch shape alone (like qv_sub01_run_tiles).  One block per CU,
+// 256 CUs: the cost of a run length is (rounds of 256 blocks) x (steps + 1: a block's weight fetch and halo frame cost
+// about a step).  64 x 10 s = 64 x 42 steps: 4 runs of 11 = 256 blocks.  QV_KV_SUB35 forces 1, 2 or S35_MAX_RUN steps.
+static int sub35_run_steps(int batch, int t3_max) {
+    const int n_steps = (t3_max + S35_TC - 1) / S35_TC, forced = qv_kernel_variant(QV_KV_SUB35);
+    int best = 1;
+    if (forced >= 1 && forced <= 3) best = forced == 3 ? S35_MAX_RUN : forced;
+    else {
+        long best_cost = -1;
+        for (int run = 1; run <= S35_MAX_RUN; ++run) {
+            const long blocks = (long)batch * ((n_steps + run - 1) / run), cost = (blocks + 255) / 256 * (run + 1);
+            if (best_cost < 0 || cost < best_cost) { best = run; best_cost = cost; }
+        }
+    }
+    return best < n_steps ? best : (n_steps > 0 ? n_steps : 1);
+}
+int qv_sub35_run_frames(int batch, int t3_max) { return sub35_run_steps(batch, t3_max) * S35_TC; }
+
+// 145 KB of dynamic LDS: opted into once, outside any stream capture (qv_model_create calls this; launch_sub35 for the tools)
+void qv_sub35_init() {
+    static const int once = [] {
+        (void)hipFuncSetAttribute((const void *)k_sub35, hipFuncAttributeMaxDynamicSharedMemorySize, S35_LDS);
+        return 0;
+    }();
+    (void)once;
+}
+
+void launch_sub35(const half_t *c1, int t2_max, const half_t *w3, const float *b3, const float *w5, const float *b5,
+                  const int32_t *len2, const int32_t *len3, const int32_t *row_off, half_t *out, int32_t *row_map, int t3_max,
+                  int batch, hipStream_t s) {
+    qv_sub35_init();
+    const int n_steps = (t3_max + S35_TC - 1) / S35_TC, run = sub35_run_steps(batch, t3_max);
+    hipLaunchKernelGGL(k_sub35, dim3(1, (n_steps + run - 1) / run, batch), dim3(512), S35_LDS, s, c1, t2_max, w3, b3, w5, b5, len2,
+                       len3, row_off, out, row_map, run);
+}
+
+void launch_unpack_rows_f32(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, float *y,
+                            int batch, hipStream_t s) {
+    hipLaunchKernelGGL(k_unpack_rows_f32, dim3(1, t_max, batch), dim3(256), 0, s, x, t_max, row_elems, len, row_off, y);
 }
 
 void launch_layernorm(const float *x, const float *g, const float *b, half_t *y, int M, hipStream_t s) {

@@ -260,6 +260,7 @@ struct QvActs {
     int lens_slot = 0, lens_last = 0;   // next slot to fill; slot of the last forward (qv_model_tap reads its offsets)
     float *tap_x;        // [N_LAYERS+1][M][512] when save_taps
     int last_batch = 0, last_tmax = 0, last_tm_max = 0, last_rows = 0, last_t2m = 0;
+    bool sub35 = false;  // f16 front end: conv.3 + conv.5 as k_sub35, c2 packed (c1p / c2p do not exist)
     // QV_PREC_ORT_MIXED: the float32 tensors in front of the quantisers, the s8 operand buffer, the range keys
     float *c1f, *c1pf, *c2f, *gluf, *dwf;
     int8_t *q8;
@@ -687,7 +688,7 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const hal
 }
 
 // activations, staging buffer and events of execution context k
-int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused) {
+int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused, bool sub35_unfused) {
     QvActs &a = m->ctx_acts[k];
     const size_t Bz = (size_t)m->max_batch, M = Bz * m->t3_cap;
     const int t_pad_cap = (m->t3_cap + 31) / 32 * 32;
@@ -696,9 +697,12 @@ int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused) {
     // the conv0 activation only exists on the two-kernel cross-check path (QVERSE_SUB_UNFUSED=1)
     if (sub_unfused) TRY(dal(eng, m, Bz * m->t1_cap * 40 * QV_SUBC, &a.c0));
     TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1));
-    TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1p));
+    // the conv.3 activation and the dense conv.6 output only exist where conv.3 / conv.5 / conv.6 / k_pack_rows run as four
+    // launches: the ORT front end and the cross-check path of k_sub35 (QVERSE_SUB35_UNFUSED=1)
+    a.sub35 = !m->ort && !sub35_unfused;
+    if (!a.sub35) TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1p));
     TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2));
-    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2p));
+    if (!a.sub35) TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2p));
     TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2k));
     TRY(dal(eng, m, M * QV_D, &a.x));
     TRY(dal(eng, m, M * QV_D, &a.ln));
@@ -776,7 +780,10 @@ int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out) {
     m->n_ctx = eng->n_ctx;
     const char *su = getenv("QVERSE_SUB_UNFUSED");
     const bool sub_unfused = su && su[0] == '1';
-    for (int k = 0; k < m->n_ctx; ++k) TRY(alloc_context(eng, m, k, sub_unfused));
+    const char *s35 = getenv("QVERSE_SUB35_UNFUSED");
+    const bool sub35_unfused = s35 && s35[0] == '1';
+    qv_sub35_init();
+    for (int k = 0; k < m->n_ctx; ++k) TRY(alloc_context(eng, m, k, sub_unfused, sub35_unfused));
     return QV_OK;
 }
 
@@ -894,20 +901,29 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
     }
     GemmArgs g = {};
     g.alpha = 1.f;
-    g.A = a.c1; g.W = m->pw3_w; g.bias = m->pw3_b; g.out = a.c1p;
-    g.M = B * t2m * 20; g.N = QV_SUBC; g.K = QV_SUBC; g.lda = QV_SUBC; g.ldw = QV_SUBC; g.ldo = QV_SUBC;
-    launch_gemm(EPI_F16_RELU, g, s);
-    launch_dwconv2d(a.c1p, t2m, 20, d_l2, m->dw5_w, m->dw5_b, a.c2, t3m, 10, B, s);
-    g.A = a.c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = a.c2p; g.M = B * t3m * 10;
-    launch_gemm(EPI_F16_RELU, g, s);
-    launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
+    g.N = QV_SUBC; g.K = QV_SUBC; g.lda = QV_SUBC; g.ldw = QV_SUBC; g.ldo = QV_SUBC;
+    if (a.sub35) {
+        // conv.3 + conv.5 in one kernel, c2 packed from here on: conv.6 runs on the valid rows only and writes c2k itself
+        launch_sub35(a.c1, t2m, m->pw3_w, m->pw3_b, m->dw5_w, m->dw5_b, d_l2, d_l3, d_off, a.c2, a.row_map, t3m, B, s);
+        g.A = a.c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = a.c2k; g.M = M * 10;
+        launch_gemm(EPI_F16_RELU, g, s);
+    } else {
+        // cross-check path: four launches, c1p and the dense c2 / c2p through HBM
+        g.A = a.c1; g.W = m->pw3_w; g.bias = m->pw3_b; g.out = a.c1p; g.M = B * t2m * 20;
+        launch_gemm(EPI_F16_RELU, g, s);
+        launch_dwconv2d(a.c1p, t2m, 20, d_l2, m->dw5_w, m->dw5_b, a.c2, t3m, 10, B, s);
+        g.A = a.c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = a.c2p; g.M = B * t3m * 10;
+        launch_gemm(EPI_F16_RELU, g, s);
+        launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
+    }
     // Linear(2560 -> 512) and xscaling (x * sqrt(d_model)) in one epilogue
     g.A = a.c2k; g.W = m->sub_out_w; g.bias = m->sub_out_b; g.out = a.x;
     g.M = M; g.N = QV_D; g.K = 2560; g.lda = 2560; g.ldw = 2560; g.ldo = QV_D; g.alpha = sqrtf((float)QV_D);
     g.in_flight = m->n_ctx;
     launch_gemm(EPI_F32, g, s);
     } else {
-        launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
+        // (front end skipped: the encoder still needs a row_map; on the packed path the c2 buffer stands in for c2p)
+        launch_pack_rows(a.sub35 ? a.c2 : a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
     }
     if (m->save_taps) QV_HIP(hipMemcpyAsync(a.tap_x, a.x, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
 
@@ -1014,7 +1030,7 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
         // another policy is never replayed after qv_debug_gemm_tiles / QVERSE_GEMM_* changed it)
         FwdKey key = {audio, logprobs, posp, n_max,
                       {B, M, T, t3min, tm_max, t1m, t2m, t_max_out, t_min_pad, att_variant,
-                       qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB) | (qv_kernel_variant(QV_KV_SUB_RUN) << 4),
+                       qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB) | (qv_kernel_variant(QV_KV_SUB_RUN) << 4) | (qv_kernel_variant(QV_KV_SUB35) << 8),
                        qv_gemm_policy_epoch()}};
         const int64_t tick = ++a.fwd_tick;
         FwdGraph *hit = nullptr;
@@ -1178,6 +1194,13 @@ int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *
     } else if (what == 11) {   // conv.2 output of the f16 path (k_sub01 / the two-kernel path) as it sits in HBM
         if (m->ort || !a.c1) { qv_set_error(eng, "tap 11 exists on the f16 front end only"); return QV_ERR_ARG; }
         launch_to_float(a.c1, out, (size_t)a.last_batch * a.last_t2m * 20 * QV_SUBC, s);
+    } else if (what == 12) {   // conv.5 output of the f16 path in the dense view [B][t3_max][10][256], frames >= len3[b] zero
+        if (m->ort) { qv_set_error(eng, "tap 12 exists on the f16 front end only"); return QV_ERR_ARG; }
+        const int32_t *d_l3 = a.lens_dev + 4 * m->max_batch, *d_off = a.lens_dev + 5 * m->max_batch;
+        const size_t n = (size_t)a.last_batch * a.last_tmax * 10 * QV_SUBC;
+        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * n, s));
+        // (k_sub35 leaves c2 packed; the four-launch path leaves it dense: row_off = nullptr)
+        launch_unpack_rows_f32(a.c2, a.last_tmax, 10 * QV_SUBC, d_l3, a.sub35 ? d_off : nullptr, out, a.last_batch, s);
     } else if (what >= 6 && what <= 9) {
         // QV_PREC_ORT_MIXED: the dense subsampling tensors in front of / behind the quantisers, as they sit in HBM
         if (!m->ort) { qv_set_error(eng, "taps 6..9 exist under QV_PREC_ORT_MIXED only"); return QV_ERR_ARG; }

@@ -190,6 +190,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_debug_kernel_variant.argtypes = [i32, i32]
     lib.qv_debug_forward_graph_stats.argtypes = [vp, vp, vp]
     lib.qv_debug_sub01_plan.argtypes = [i64, i32, vp, vp]
+    lib.qv_debug_sub35_plan.argtypes = [i64, i32, vp]
     lib.qv_weights_info.argtypes = [vp, C.c_char_p, i32]
     lib.qv_profile_inject_logprobs.argtypes = [vp, vp, i32, vp, i32]
     lib.qv_profile_stages.argtypes = [vp, i32]
@@ -648,7 +649,8 @@ class Engine:
         1 = precision 2's conv.0 (0 VALU, 1 f32 matrix pipe), 2 = span pass (0 one walk per span, 1 prefix-shared),
         3 = forward of a multi-context engine (0 plain launches, 1 hipGraph replay of a repeating shape),
         5 = tiles of four conv.2 frames a block of the fused subsampling kernel walks (0 from the launch shape, 1 / 2 tiles,
-        3 the maximum); -1 = environment / default.  Identical bits either way."""
+        3 the maximum), 6 = steps of three conv.5 frames a block of the conv.3 + conv.5 kernel walks (same codes);
+        -1 = environment / default.  Identical bits either way."""
         self._check(self.lib.qv_debug_kernel_variant(int(which), int(mode)), "qv_debug_kernel_variant")
 
     def forward_graph_stats(self) -> dict:
@@ -936,6 +938,15 @@ class Engine:
         fr, run = (C.c_int32 * 4)(), C.c_int32(0)
         self._check(self.lib.qv_debug_sub01_plan(int(n_samples), int(batch), fr, C.byref(run)), "qv_debug_sub01_plan")
         return {"mel": fr[0], "c0": fr[1], "c1": fr[2], "frames": fr[3], "run_tiles": run.value}
+
+    TAP_C2 = 12   # forward_tap code: conv.5 output of the f16 front end, dense f32[B, t3_max, 10, 256], frames >= len3[b] zero
+
+    def sub35_plan(self, n_samples: int, batch: int = 1) -> dict:
+        """conv.5 frames one block of the fused conv.3 + conv.5 kernel walks when `batch` clips, the longest of n_samples,
+        are launched (qv_debug_sub35_plan; kernel_variant(6, .) forces 1 step, 2 steps or the maximum)."""
+        run = C.c_int32(0)
+        self._check(self.lib.qv_debug_sub35_plan(int(n_samples), int(batch), C.byref(run)), "qv_debug_sub35_plan")
+        return {"run_frames": run.value}
 
     def forward_tap(self, what: int, layer: int, shape=None, c1_frames: int | None = None, batch: int | None = None):
         """a tensor of the last forward as f32 (qv_debug_forward_tap).  what = TAP_C1 needs no `shape`: give the batch size
