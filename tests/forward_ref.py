@@ -1,5 +1,5 @@
-"""Reference-side helpers for the length tests of the acoustic forward (tests/test_gpu_forward_lengths.py,
-tests/test_forward_ref_host.py).  Everything here runs on the CPU with oracle/fastconformer_ref.py alone.
+"""Reference-side helpers for the length tests and the per-layer tap tests of the acoustic forward
+(tests/test_gpu_forward_lengths.py, tests/test_gpu_layer_taps.py, tests/test_forward_ref_host.py).  Everything here runs on the CPU with oracle/fastconformer_ref.py alone.
 
   * the twin (`F16Ops`): the fp32 restatement with the ONE rounding the device design chooses -- float16 operands of every
     Linear / Conv, float32 accumulation and bias.  Its distance `e` from the fp32 restatement is the reference-side floor
@@ -10,6 +10,9 @@ tests/test_forward_ref_host.py).  Everything here runs on the CPU with oracle/fa
     is visible in the log-probs while `e` does not move.
   * two PLANTED reference errors (context managers): what a position off-by-one or a dropped last key frame in an
     attention kernel would compute.  A test whose bound such an oracle passes proves nothing about that error.
+  * `telltale_weights`, `PLANTS`, `layer_power`, `tap_floor` (second half of the file): the weight set on which one wrong
+    tensor in one layer shows at the tap behind that layer, the 46 wrong tensors, what each does to each of the 17 taps,
+    and the taps' own float16 floor.
 """
 
 from __future__ import annotations
@@ -289,3 +292,192 @@ def check_rules(tag, got, ref, rows=None) -> list:
     for (n, e, da, db), b in zip(figures, (range(len(T)) if rows is None else rows)):
         assert da <= ref["bound"][b], (tag, n, "rule (a)", da, ref["bound"][b])
     return figures
+
+
+# ------------------------------------------------------------------ every layer, every tensor ---------------------------
+# tests/test_gpu_layer_taps.py holds the tap behind each of the 17 layers to the fp32 oracle; what follows is the reference
+# side of it: a weight set on which ONE wrong per-layer tensor shows at that layer's tap, the wrong tensors themselves
+# ("plants": the oracle evaluated on misrouted weights, never a kernel), and the precision floor of the taps.
+
+TAP_BOUND = 1.5e-2            # the project's bound on a layer tap (test_gpu_forward.py, test_gpu_forward_lengths.py)
+SUB_BOUND = 5e-2              # ... and on the sqrt(512)-scaled subsampling output
+_L0 = "encoder.layers.0."
+LAYER_SUFFIXES = tuple(k[len(_L0):] for k in R.weight_shapes(1) if k.startswith(_L0))       # the 39 tensors of a layer
+UNOBSERVABLE = "self_attn.linear_k.bias"
+
+# gains on top of sharp_weights(); "running_var" is spread around 1, not scaled.  See telltale_weights().
+TELLTALE_OUT_GAIN = 1.0 / 16.0
+TELLTALE_VAR_SPREAD = 6.0
+TELLTALE_GAINS = (("self_attn.pos_bias_u", 16.0), ("self_attn.pos_bias_v", 5.0), ("self_attn.linear_q.bias", 6.0),
+                  ("conv.batch_norm.running_mean", 5.0))
+
+
+def telltale_weights(w: dict) -> dict:
+    """The weight set on which a wrong tensor in ANY layer moves that layer's tap by >= 4x the tap bound
+    (test_forward_ref_host.py::test_every_plant_shows_at_its_layer_tap).  sharp_weights(w), and then:
+
+      * pre_encode.out weight and bias x 1/16: the encoder's input stream is sub * sqrt(512), +-30 on the seeded weights, so
+        in layer 0 every branch output (O(1)) is a 3 % ripple that norm_out shrinks to the size of the tap bound.  With 1/16
+        the stream entering layer 0 is O(1) like the one entering layers 1 .. 16 (each a norm_out output).
+      * batch_norm.running_var = 1 + 6 (v - 1): the seeded variances lie in 1 .. 1.3, so a neighbour's differs by a few
+        per cent, in a tensor that a Swish and a pointwise conv still follow.  Spread to 1 .. 2.8 it changes the scale by
+        tens of per cent (and stays positive: v >= 1).
+      * batch_norm.running_mean x5: "mean not scaled by gamma / sqrt(var + eps)" is an error of mean * (1 - 1 / s); with
+        the seeded mean (std 0.1) and s within 0.6 .. 1.1 that is 1.3 bounds in the worst layer, x5 makes it >= 6.
+      * pos_bias_u x16, pos_bias_v x5, linear_q.bias x6 (on top of the sharp x4): the three vectors that reach the output
+        only through a product with a key / position row inside the softmax.  At the sharp gain a neighbour's vector moves
+        a tap by 3e-2 - 5e-2 in the best layer and 6e-3 in the worst.  u needs most: u.k is the same for every query of a
+        head and only re-weights the keys, where v.p also moves the position profile.
+
+    What was tried and left out: linear_k.weight x1.5 (with u x12, v x4, q.bias x4) reaches the same power, but the sharper
+    softmax doubles the taps' own float16 floor (e_tap 1.1e-2 in layers 2 - 5: 1.5 e_tap would then BE the bound).  With
+    the keys left alone e_tap stays <= 8.1e-3.  Gains on the additive biases (every Linear / conv bias x4 or x8) do not work
+    either: the late layers saturate (Swish, softmax) and the early layers' deviations are normalised away by the norm_out's
+    that follow before they reach the log-probs (0.0 - 0.5 bounds there); the taps do not need them -- with O(1) layer
+    inputs a neighbour's bias (std 0.1) is already > 5 bounds.
+
+    linear_k.bias stays invisible on any weights: test_key_bias_is_invisible_by_construction."""
+    out = sharp_weights(w)
+    for name in ("encoder.pre_encode.out.weight", "encoder.pre_encode.out.bias"):
+        out[name] = (out[name] * TELLTALE_OUT_GAIN).contiguous()
+    for name in list(out):
+        if not name.startswith("encoder.layers."):
+            continue
+        if name.endswith("conv.batch_norm.running_var"):
+            out[name] = (1.0 + TELLTALE_VAR_SPREAD * (out[name] - 1.0)).contiguous()
+        for suffix, gain in TELLTALE_GAINS:
+            if name.endswith(suffix):
+                out[name] = (out[name] * gain).contiguous()
+    return out
+
+
+def _p(l: int) -> str:
+    return f"encoder.layers.{l}."
+
+
+def _misroute(suffix):
+    def plant(w, l):
+        return {_p(l) + suffix: w[_p((l + 1) % R.N_LAYERS) + suffix]}
+    return plant
+
+
+def _swap(a, b):
+    def plant(w, l):
+        return {_p(l) + a: w[_p(l) + b], _p(l) + b: w[_p(l) + a]}
+    return plant
+
+
+def _swap_norms(w, l):
+    out = {}
+    for part in (".weight", ".bias"):
+        out.update(_swap("norm_feed_forward1" + part, "norm_feed_forward2" + part)(w, l))
+    return out
+
+
+def _depthwise(change):
+    def plant(w, l):
+        name = _p(l) + "conv.depthwise_conv.weight"
+        return {name: change(w[name].clone()).contiguous()}
+    return plant
+
+
+def _drop_tap(k):
+    def change(t):
+        t[..., k] = 0.0
+        return t
+    return change
+
+
+def _mean_not_scaled(w, l):
+    """BatchNorm folded to y = x * s + (beta - mean * s), s = gamma / sqrt(var + eps), with the `* s` on the mean forgotten:
+    y = x * s + beta - mean.  The same thing as a running_mean of mean / s."""
+    c = _p(l) + "conv.batch_norm."
+    s = w[c + "weight"] / torch.sqrt(w[c + "running_var"] + 1e-5)
+    return {c + "running_mean": (w[c + "running_mean"] / s).contiguous()}
+
+
+# name -> plant(w, l): the entries of the weight dict that layer l reads wrongly
+MISROUTES = {"next:" + s: _misroute(s) for s in LAYER_SUFFIXES}
+STRUCTURAL = {
+    "swap:pos_bias_u<->pos_bias_v": _swap("self_attn.pos_bias_u", "self_attn.pos_bias_v"),
+    "swap:norm_feed_forward1<->norm_feed_forward2": _swap_norms,
+    "swap:feed_forward1<->feed_forward2.linear2.bias": _swap("feed_forward1.linear2.bias", "feed_forward2.linear2.bias"),
+    "depthwise:taps reversed": _depthwise(lambda t: t.flip(-1)),
+    "depthwise:first tap dropped": _depthwise(_drop_tap(0)),
+    "depthwise:last tap dropped": _depthwise(_drop_tap(R.CONV_K - 1)),
+    "batch_norm:mean not scaled": _mean_not_scaled,
+}
+PLANTS = {**MISROUTES, **STRUCTURAL}
+BLIND = "next:" + UNOBSERVABLE                 # the one plant no output can see
+LAYER_TAPS = ["sub"] + [f"layer{l}" for l in range(R.N_LAYERS)]
+
+
+def _rows_of(audio, lens, rows):
+    rows = list(rows)
+    sub_lens = [lens[r] for r in rows]
+    return audio[rows][:, : max(sub_lens)].contiguous(), sub_lens
+
+
+def _tap_dist(a, b, T) -> float:
+    """max |a - b| over the valid frames of every utterance"""
+    return max(maxdiff(a[i], b[i], n) for i, n in enumerate(T))
+
+
+@torch.no_grad()
+def layer_power(w, audio, lens, rows, against=None, plants=None, layers=None) -> dict:
+    """What each plant does to each layer's tap, on the utterances `rows` of a batch.  The fp32 oracle runs once with `sub`
+    and all 17 layer taps kept; a plant in layer l is then ONE R.conformer_layer call on the oracle's own input to layer l
+    (a wrong tensor of layer l cannot reach tap l any other way), so the 46 x 17 table costs about as much as 46 forwards
+    of two short clips.
+    `layers`: the layers to plant in (default: all 17; the lists below then have one entry per layer given).
+    {"t", "taps", "D": {plant: [17 distances planted vs true tap]}, "reeval": [17 distances of the unplanted re-evaluation
+     from the oracle's tap -- 0.0 each, test_single_layer_reevaluation_is_the_oracle], and with against = {l: tensor
+     [len(rows), >= T, 512]} (a device's taps of those rows) "A": {plant: [17 distances planted vs `against`]}}"""
+    sub_audio, sub_lens = _rows_of(audio, lens, rows)
+    taps = _Keep(LAYER_TAPS)
+    _, t = R.forward(w, sub_audio, sub_lens, taps=taps)
+    T = t.tolist()
+    tmax = taps["sub"].shape[1]
+    pos_emb = R.rel_pos_emb(tmax).unsqueeze(0)
+    pad = torch.arange(tmax)[None, :] >= t[:, None]
+    plants = PLANTS if plants is None else plants
+    out = {"t": T, "taps": taps, "D": {k: [] for k in plants}, "reeval": []}
+    if against is not None:
+        out["A"] = {k: [] for k in plants}
+    for l in (range(R.N_LAYERS) if layers is None else layers):
+        x = taps["sub"] * math.sqrt(R.D_MODEL) if l == 0 else taps[f"layer{l - 1}"]
+        true = taps[f"layer{l}"]
+        out["reeval"].append(_tap_dist(R.conformer_layer(w, _p(l), x, pos_emb, pad), true, T))
+        for key, plant in plants.items():
+            bad = R.conformer_layer({**w, **plant(w, l)}, _p(l), x, pos_emb, pad)
+            out["D"][key].append(_tap_dist(bad, true, T))
+            if against is not None:
+                out["A"][key].append(_tap_dist(bad, against[l][:, :tmax], T))
+    return out
+
+
+@torch.no_grad()
+def tap_floor(w, audio, lens, taps=None) -> dict:
+    """e_tap per layer: the larger of the two reference twins' distances (F16Ops; F16Ops with the attention kernels' roundings)
+    from the fp32 oracle's tap, over the valid frames of every utterance; `taps` = the fp32 oracle's, if already at hand.
+    {"t", "taps" (fp32), "lp", "twin", "twin_att", "e", "bound" (rule (a), per utterance), "e_tap" [17], "bound_tap" [17],
+     "e_sub"}"""
+    if taps is None:
+        taps = _Keep(LAYER_TAPS)
+        lp, t = R.forward(w, audio, lens, taps=taps)
+    else:
+        lp, t = R.forward(w, audio, lens)
+    T = t.tolist()
+    tw_taps, att_taps = _Keep(LAYER_TAPS), _Keep(LAYER_TAPS)
+    tw, _ = R.forward(w, audio, lens, taps=tw_taps, ort=F16Ops())
+    with attention_roundings():
+        tw_att, _ = R.forward(w, audio, lens, taps=att_taps, ort=F16Ops())
+    e_tap = [max(_tap_dist(tw_taps[k], taps[k], T), _tap_dist(att_taps[k], taps[k], T)) for k in LAYER_TAPS[1:]]
+    e = twin_floor(tw, lp, T)
+    return {"t": T, "taps": taps, "lp": lp, "twin": tw, "twin_att": tw_att, "e": e, "bound": [bound_a(x) for x in e],
+            "e_tap": e_tap, "bound_tap": [bound_tap(x) for x in e_tap],
+            "e_sub": math.sqrt(R.D_MODEL) * max(_tap_dist(tw_taps["sub"], taps["sub"], T), _tap_dist(att_taps["sub"], taps["sub"], T))}
+
+
+def bound_tap(e: float) -> float:
+    return max(TAP_BOUND, FLOOR_K * e)

@@ -2,7 +2,12 @@
 the f16-operand twin's distance `e` from the fp32 restatement is below 1e-2 on the "sharp attention" weights and within
 2x of what it is on the plain ones, the two planted errors stand out of the bound there (and the position error does
 NOT on the plain weights -- the gap those tests close), the structured set's argmax condition leaves (almost) no frame
-out, and the oracle is batch-invariant, so one padded call serves a ragged device batch."""
+out, and the oracle is batch-invariant, so one padded call serves a ragged device batch.
+
+Second half, the premises of tests/test_gpu_layer_taps.py: on forward_ref.telltale_weights every per-layer tensor read from the
+neighbouring layer, and seven slips inside a layer, move that layer's tap by >= 4 tap bounds in all 17 layers, while the taps' own
+float16 floor leaves the bound at the project's 1.5e-2; linear_k.bias alone is invisible, by construction; and on the sharp weights
+layer 0 hides such errors."""
 
 import pytest
 import torch
@@ -126,3 +131,104 @@ def test_samples_for_frames_is_the_smallest_count():
         assert R.sub_len(R.mel_frames(n)) == t
         assert n == 400 or R.sub_len(R.mel_frames(n - 160)) == t - 1
     assert R.sub_len(R.mel_frames(FR.MAX_SAMPLES)) == 766
+
+
+# ------------------------------------------------------------------ the instrument of tests/test_gpu_layer_taps.py -------
+# One wrong tensor in one layer: does the tap behind that layer show it?  Oracle against oracle, no kernel.
+
+TELL_FRAMES = [33, 129]
+
+
+@pytest.fixture(scope="module")
+def tell(refs):
+    """per kind ('telltale', and 'telltale_q' = what a precision-1 engine makes of it): the 46 x 17 power table and the
+    taps' float16 floor on the 33- and 129-frame clips of the ladder"""
+    rows = [FRAMES.index(t) for t in TELL_FRAMES]
+    audio, lens = FR._rows_of(refs["audio"], refs["lens"], rows)
+    w = FR.telltale_weights(refs["plain_w"])
+    out = {"audio": audio, "lens": lens}
+    for kind, wk in (("telltale", w), ("telltale_q", R.quantize_linear_weights(w))):
+        power = FR.layer_power(wk, audio, lens, range(len(lens)))
+        assert power["t"] == TELL_FRAMES
+        out[kind] = {"w": wk, "power": power, "floor": FR.tap_floor(wk, audio, lens, taps=power["taps"])}
+    return out
+
+
+KINDS = ["telltale", "telltale_q"]
+
+
+def test_telltale_weights_change_what_they_say(refs):
+    sharp, tell_w = refs["sharp_w"], FR.telltale_weights(refs["plain_w"])
+    gains = dict(FR.TELLTALE_GAINS)
+    for k, t in tell_w.items():
+        suffix = next((s for s in gains if k.endswith(s)), None)
+        if k.startswith("encoder.pre_encode.out."):
+            assert torch.equal(t, sharp[k] * FR.TELLTALE_OUT_GAIN), k
+        elif k.endswith("batch_norm.running_var"):
+            assert torch.equal(t, 1.0 + FR.TELLTALE_VAR_SPREAD * (sharp[k] - 1.0)) and float(t.min()) >= 1.0, k
+        elif suffix is not None and k.startswith("encoder.layers."):
+            assert torch.equal(t, sharp[k] * gains[suffix]), k
+        else:
+            assert torch.equal(t, sharp[k]), k
+    assert len(FR.LAYER_SUFFIXES) == 39 and FR.UNOBSERVABLE in FR.LAYER_SUFFIXES
+    assert len(FR.PLANTS) == 39 + 7
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_single_layer_reevaluation_is_the_oracle(tell, kind):
+    """a plant is ONE R.conformer_layer call on the oracle's own input to that layer: without a plant that call must give
+    the oracle's tap bit for bit, or the table measures something else"""
+    assert tell[kind]["power"]["reeval"] == [0.0] * R.N_LAYERS
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_tap_bound_is_the_projects_own(tell, kind):
+    """1.5 e_tap <= 1.5e-2 at every layer and 1.5 e <= 1e-2 on the log-probs: the bounds asserted on the device are the
+    project's 1.5e-2 / 1e-2, not floors this weight set inflated.  (If a candidate set breaks this, change the set.)"""
+    fl = tell[kind]["floor"]
+    print(f"[tell-ref] {kind}: e {' / '.join(f'{e:.2e}' for e in fl['e'])}, e_tap per layer " + " ".join(f"{e * 1e3:.1f}" for e in fl["e_tap"])
+          + f" (x 1e-3), e_sub {fl['e_sub']:.2e}")
+    for l, e in enumerate(fl["e_tap"]):
+        assert 0.0 < FR.FLOOR_K * e <= FR.TAP_BOUND, (l, e)
+    assert fl["bound_tap"] == [FR.TAP_BOUND] * R.N_LAYERS
+    assert fl["bound"] == [1e-2] * len(TELL_FRAMES), fl["e"]
+    assert FR.FLOOR_K * fl["e_sub"] <= FR.SUB_BOUND
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_every_plant_shows_at_its_layer_tap(tell, kind):
+    """The power of test_gpu_layer_taps.py: each of the 38 observable tensors of a layer replaced by the next layer's, and
+    each of the seven structural slips, in each of the 17 layers, moves that layer's tap by >= 4 bounds -- the factor
+    _planted_check uses.  On sharp_weights this test fails (see test_sharp_weights_hide_a_wrong_vector_in_layer_0)."""
+    D, bound = tell[kind]["power"]["D"], tell[kind]["floor"]["bound_tap"]
+    ratios = sorted((d / bound[l], key, l) for key, row in D.items() if key != FR.BLIND for l, d in enumerate(row))
+    assert len(ratios) == 45 * R.N_LAYERS
+    for r, key, l in ratios[:5]:
+        print(f"[tell-ref] {kind}: {key} in layer {l}: {r:.2f} bounds")
+    low = [(key, l, round(r, 2)) for r, key, l in ratios if r < 4.0]
+    assert not low, low
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_key_bias_is_invisible_by_construction(tell, kind):
+    """linear_k.bias adds u.b_k + q.b_k to every key's content score of a query row: one constant per row, which the
+    softmax removes; the position term and the values never see it.  No output of the model depends on it (float32 noise
+    only), so no test can hold it -- on these or any weights."""
+    d = tell[kind]["power"]["D"][FR.BLIND]
+    print(f"[tell-ref] {kind}: linear_k.bias of the next layer, per layer: max {max(d):.1e}")
+    assert max(d) <= 1e-4, d
+
+
+def test_sharp_weights_hide_a_wrong_vector_in_layer_0(refs, tell):
+    """The gap the telltale set closes, kept so that nobody removes it as redundant: on sharp_weights layer 0's input is
+    +-30, and some vector of layer 0 replaced by layer 1's moves the layer-0 tap by less than bound + the device's own
+    distance (1.5e-2 + 1e-2) -- a device with that error could pass the tap that test_gpu_forward*.py do compare."""
+    vectors = {k: p for k, p in FR.MISROUTES.items() if refs["sharp_w"]["encoder.layers.0." + k[len("next:"):]].numel() <= R.FF
+               and k != FR.BLIND}                    # biases, LayerNorm / BatchNorm vectors, pos_bias_u / v [8, 64]
+    assert len(vectors) == 26
+    D = FR.layer_power(refs["sharp_w"], tell["audio"], tell["lens"], range(len(TELL_FRAMES)), plants=vectors, layers=[0])["D"]
+    hidden = sorted((d[0], k) for k, d in D.items() if d[0] < FR.TAP_BOUND + 1e-2)
+    print(f"[tell-ref] sharp weights, layer 0: {len(hidden)} of {len(D)} vectors hidden, smallest {hidden[:3]}")
+    assert hidden
+    same = {k: tell["telltale"]["power"]["D"][k][0] for _, k in hidden}
+    assert min(same.values()) >= 4.0 * FR.TAP_BOUND, same
