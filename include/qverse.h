@@ -478,7 +478,7 @@ int qv_debug_attention_variant(int32_t mode);
 
 /* Process-wide variant of a single kernel, for the tests that compare two implementations of one stage bit for bit
  * (-1 = back to the environment / default).  which 0 (QVERSE_LOGMEL): the log-mel kernel's 256-point FFT -- 0 = Stockham
- * through LDS, 1 = in registers with DPP / v_permlane*_swap exchanges; which 1 (QVERSE_ORT_SUB): conv.0 of
+ * through LDS, 1 = in registers with DPP / v_permlane*_swap exchanges, 2 = as 1 with a wave walking a run of frames; which 1 (QVERSE_ORT_SUB): conv.0 of
  * QV_PREC_ORT_MIXED's front end -- 0 = VALU, 1 = v_mfma_f32_32x32x2_f32 on the integer-valued operands; which 2
  * (QVERSE_SPANS): match_verse's span pass -- 0 = one LCS walk per span, 1 = one walk per start verse with the count read
  * off at every ayah end; which 3 (QVERSE_FWD_GRAPH): the forward of an engine with more than one context -- 0 = plain
@@ -486,7 +486,7 @@ int qv_debug_attention_variant(int32_t mode);
  * (QVERSE_CTC): the alpha recursion of the CTC rerank -- 0 = the wave program of rounds 1-5, 1 = the parity-specialised
  * one (two-term log-sum-exp for blank states); which 5 (QVERSE_SUB_RUN): how many tiles of four conv.2 frames one block
  * of the fused subsampling kernel walks -- 0 = chosen from the launch shape, 1 / 2 = one / two tiles, 3 = the most a block
- * ever walks (16).  The variants of a kernel produce identical bits. */
+ * ever walks (16), 4 = the most it walks with the run's mel rows resident in LDS (4).  The variants of a kernel produce identical bits. */
 int qv_debug_kernel_variant(int32_t which, int32_t mode);
 
 /* The forward's own frame arithmetic, for the tests: frames_out[0..3] = log-mel frames of a clip of n_samples and its

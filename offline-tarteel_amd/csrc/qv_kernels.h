@@ -123,7 +123,8 @@ const char *qv_gemm_kernel_name(int epi, const GemmArgs &g);
 
 // Cross-check variants of single kernels (qv_debug_kernel_variant): the override if one is set, else the environment
 // variable (read once per process), else the default.  Variants of one kernel give identical bits unless stated.
-//   QV_KV_LOGMEL  (QVERSE_LOGMEL)   1 = FFT in registers, cross-lane strides over DPP / v_permlane*_swap (default);
+//   QV_KV_LOGMEL  (QVERSE_LOGMEL)   2 = FFT in registers, a wave walks a run of frames (k_logmel_run, default);
+//                                   1 = FFT in registers, cross-lane strides over DPP / v_permlane*_swap, one wave per frame;
 //                                   0 = Stockham FFT through LDS (the kernel of rounds 1-4)
 //   QV_KV_ORT_SUB (QVERSE_ORT_SUB)  precision 2's conv.0: 1 = f32 matrix pipe, four channel groups per block (default); 0 = VALU
 //   QV_KV_SPANS   (QVERSE_SPANS)    match_verse's span pass: 1 = prefix-shared walk per start verse (k_spans2, default); 0 = one walk per span
@@ -132,7 +133,8 @@ const char *qv_gemm_kernel_name(int epi, const GemmArgs &g);
 //   QV_KV_CTC     (QVERSE_CTC)      the alpha recursion of the CTC rerank: 1 = parity-specialised wave program (ctc_wave2, default);
 //                                   0 = the wave program of rounds 1-5
 //   QV_KV_SUB_RUN (QVERSE_SUB_RUN)  tiles of four c1 frames a block of k_sub01 walks: 0 = chosen from the launch shape (default);
-//                                   1 / 2 = one / two tiles; 3 = the most a block ever walks (16)
+//                                   1 / 2 = one / two tiles; 3 = the most a block ever walks (16, mel rows refetched per channel
+//                                   group); 4 = the most with the run's mel rows resident in LDS (4)
 //   QV_KV_SUB35   (no variable)     steps of three c2 frames a block of k_sub35 walks: 0 = chosen from the launch shape (default);
 //                                   1 / 2 = one / two steps; 3 = the most a block ever walks (16)
 enum { QV_KV_LOGMEL = 0, QV_KV_ORT_SUB = 1, QV_KV_SPANS = 2, QV_KV_FWD_GRAPH = 3, QV_KV_CTC = 4, QV_KV_SUB_RUN = 5, QV_KV_SUB35 = 6, QV_KV_COUNT = 8 };

@@ -291,6 +291,12 @@ __global__ __launch_bounds__(256) void k_dwconv2d(const half_t *__restrict__ in,
 //   * depthwise stage: 80 positions x 16 four-channel chunks = 1,280 items, five per thread
 //   * the 19 mel rows of the next step are requested before the current step's products and normalised into the other
 //     row buffer behind its depthwise stage
+//   * RESIDENT (runs of at most SUB_RES_RUN tiles): the normalised mel rows of the WHOLE run stay in LDS (16 run + 3 rows;
+//     tile k reads rows 16 k .. 16 k + 18).  The prologue fills them, all loads in flight at once; the four passes fetch,
+//     normalise and store nothing.  Without it every mel row of a run is loaded, normalised and stored four times.  LDS: 54,592 (tile +
+//     halo) + 640 + 67 x 328 = 77,208 bytes at a run of 4; a run of 5 would need 82,456 -- hence the cap, and the
+//     two-buffer variant stays for the longer runs QV_KV_SUB_RUN can force.  The same values from the same operations
+//     reach conv0 either way.
 // Every output element is formed by the same instructions on the same operands whatever the run length (and as in the
 // two-kernel path): the run length only decides which block forms it.
 // LDS tile: position p (row * 40 + f) owns 64 channels at a pitch of 136 bytes.  The conv0 epilogue stores 8 bytes per
@@ -301,23 +307,50 @@ __global__ __launch_bounds__(256) void k_dwconv2d(const half_t *__restrict__ in,
 #define SUB_TT 4                    // c1 frames per tile
 #define SUB_R1 (2 * SUB_TT + 1)     // c0 rows per tile
 #define SUB_RM (2 * SUB_R1 + 1)     // mel rows per tile
+#define SUB_MSTEP (4 * SUB_TT)       // mel rows from a tile to the next
 #define SUB_CG 64                   // channels per pass
 #define SUB_PP 68                   // halves per position of the LDS tile (136 bytes)
 #define SUB_HALO1 24576             // halves: the second halo row (49,152 bytes = 192 x 256, behind rows 0 .. 8)
 #define SUB_MAX_RUN 16              // tiles a block walks at most
+#define SUB_RES_RUN 4               // tiles a block walks at most with the run's mel rows resident in LDS
 #define SUB_MEL_PER_THREAD ((SUB_RM * QV_NMEL + 255) / 256)
+// QV_SUB01_STAMPS (tools/sub01_bench only, never the product build): wave 0 of one block in the middle of the grid adds up
+// its clock between the phase boundaries -- 0 prologue, 1 conv0 units (with a pass's weight fetch), 2 the barrier behind
+// them, 3 depthwise stage, 4 mel store, 5 the barrier behind it -- and leaves the sums in a buffer nothing else reads.
+// The stamps' waits forbid overlaps the product kernel has: read the shares, not the length.
+#ifdef QV_SUB01_STAMPS
+__device__ unsigned long long qv_sub01_stamps[6];
+__device__ __forceinline__ unsigned long long sub_clock() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#define SUB_STAMP_BEGIN unsigned long long st_acc[6] = {0, 0, 0, 0, 0, 0}, st_last = sub_clock()
+#define SUB_STAMP(p) do { const unsigned long long t_ = sub_clock(); st_acc[p] += t_ - st_last; st_last = t_; } while (0)
+#define SUB_STAMP_END do { if (blockIdx.y == gridDim.y / 2 && blockIdx.z == gridDim.z / 2 && threadIdx.x == 0) \
+    for (int p_ = 0; p_ < 6; ++p_) qv_sub01_stamps[p_] = st_acc[p_]; } while (0)
+#else
+#define SUB_STAMP_BEGIN
+#define SUB_STAMP(p)
+#define SUB_STAMP_END
+#endif
+template <bool RESIDENT>
 __global__ __launch_bounds__(256) void k_sub01(const float *__restrict__ feats, int tm_max, const int32_t *__restrict__ len_mel,
                                                const double *__restrict__ stats, const float *__restrict__ w0t,
                                                const float *__restrict__ b0, const int32_t *__restrict__ len1,
                                                const float *__restrict__ w1t, const float *__restrict__ b1,
                                                half_t *__restrict__ out, int t2_max, int run) {
-    __shared__ __attribute__((aligned(16))) float rows[2][SUB_RM][QV_NMEL + 2];
+    constexpr int N_ROWS = RESIDENT ? SUB_MSTEP * SUB_RES_RUN + 3 : 2 * SUB_RM;   // the run's rows, or two buffers of a tile's
+    __shared__ __attribute__((aligned(16))) float rows[N_ROWS][QV_NMEL + 2];
     __shared__ float mean_s[QV_NMEL], rstd_s[QV_NMEL];
     __shared__ __attribute__((aligned(256))) half_t tile[SUB_HALO1 + 40 * SUB_PP];
     static_assert(SUB_HALO1 >= SUB_R1 * 40 * SUB_PP && (SUB_HALO1 * 2) % 256 == 0, "k_sub01: the second halo row lies behind the tile");
     // ~68 KB of static LDS: gfx950 only (160 KB per CU, two blocks resident); every other target stops at 64 KB per block
     static_assert(sizeof(rows) + sizeof(tile) + sizeof(mean_s) + sizeof(rstd_s) <= 80 * 1024,
                   "k_sub01: two blocks per CU need <= 80 KB of LDS each");
+    SUB_STAMP_BEGIN;
     const int b = blockIdx.z, tid = threadIdx.x;
     const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT;
     const int tile0 = blockIdx.y * run;                                     // first tile of the run
@@ -346,16 +379,38 @@ __global__ __launch_bounds__(256) void k_sub01(const float *__restrict__ feats, 
 #pragma unroll
         for (int i = 0; i < SUB_MEL_PER_THREAD; ++i) {
             const int e = tid + 256 * i, r = e / QV_NMEL, f = e - r * QV_NMEL, t = 16 * tl - 3 + r;
-            if (e < SUB_RM * QV_NMEL) rows[buf][r][f + 1] = (t >= 0 && t < tin) ? (pf[i] - mean_s[f]) * rstd_s[f] : 0.f;
+            if (e < SUB_RM * QV_NMEL) rows[buf * SUB_RM + r][f + 1] = (t >= 0 && t < tin) ? (pf[i] - mean_s[f]) * rstd_s[f] : 0.f;
         }
     };
-    mel_fetch(tile0);
-    if (tid < QV_NMEL) mel_mean_rstd(stats, b, tid, tin, mean_s[tid], rstd_s[tid]);
-    if (tid < 2 * 2 * SUB_RM) rows[tid & 1][(tid >> 1) % SUB_RM][(tid >> 1) / SUB_RM ? QV_NMEL + 1 : 0] = 0.f;   // the padding columns
+    if (RESIDENT) {
+        // all 16 nk + 3 rows of the run at once: every load is issued before the statistics, one wait, then the stores
+        constexpr int PER_THREAD = (N_ROWS * QV_NMEL + 255) / 256;
+        const int n_el = (SUB_MSTEP * nk + 3) * QV_NMEL;
+        float pr[PER_THREAD];
+#pragma unroll
+        for (int i = 0; i < PER_THREAD; ++i) {
+            const int e = min(tid + 256 * i, n_el - 1), r = e / QV_NMEL, f = e - r * QV_NMEL;
+            const int t = min(max(16 * tile0 - 3 + r, 0), tin - 1);
+            pr[i] = x[t * QV_NMEL + f];
+        }
+        if (tid < QV_NMEL) mel_mean_rstd(stats, b, tid, tin, mean_s[tid], rstd_s[tid]);
+        for (int i = tid; i < 2 * N_ROWS; i += 256) rows[i >> 1][i & 1 ? QV_NMEL + 1 : 0] = 0.f;      // the padding columns
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PER_THREAD; ++i) {
+            const int e = tid + 256 * i, r = e / QV_NMEL, f = e - r * QV_NMEL, t = 16 * tile0 - 3 + r;
+            if (e < n_el) rows[r][f + 1] = (t >= 0 && t < tin) ? (pr[i] - mean_s[f]) * rstd_s[f] : 0.f;
+        }
+    } else {
+        mel_fetch(tile0);
+        if (tid < QV_NMEL) mel_mean_rstd(stats, b, tid, tin, mean_s[tid], rstd_s[tid]);
+        for (int i = tid; i < 2 * N_ROWS; i += 256) rows[i >> 1][i & 1 ? QV_NMEL + 1 : 0] = 0.f;      // the padding columns
+        __syncthreads();
+        mel_store(tile0, 0);
+    }
     __syncthreads();
-    mel_store(tile0, 0);
-    __syncthreads();
-    int it = 0;                     // steps done: step `it` reads rows[it & 1]
+    SUB_STAMP(0);
+    int it = 0;                     // steps done: step `it` reads its tile's rows (RESIDENT) / row buffer it & 1
     for (int cg = 0; cg < QV_SUBC; cg += SUB_CG) {
         float wa[5], bc[16];
         conv0_weights(w0t, b0, cg + 32 * ct, l31, hi, wa, bc);
@@ -374,10 +429,10 @@ __global__ __launch_bounds__(256) void k_sub01(const float *__restrict__ feats, 
         for (int k = 0; k < nk; ++k, ++it) {
             const int tl0 = tile0 + k;
             const int t1_0 = 2 * SUB_TT * tl0 - 1;          // the halo row; the new rows are t1_0 + 1 .. t1_0 + 8
-            const float *rw = &rows[it & 1][0][0];
-            // the next step's mel rows (the first tile again behind the last step of a pass)
+            const float *rw = &rows[RESIDENT ? SUB_MSTEP * k : (it & 1) * SUB_RM][0];
+            // the next step's mel rows (the first tile again behind the last step of a pass); RESIDENT: they are there
             const int nxt = k + 1 < nk ? tl0 + 1 : tile0;
-            const bool more = k + 1 < nk || cg + SUB_CG < QV_SUBC;
+            const bool more = !RESIDENT && (k + 1 < nk || cg + SUB_CG < QV_SUBC);
             if (more) mel_fetch(nxt);
             // ---- conv0 + ReLU into the LDS tile on the f32 matrix pipe
             if (k == 0) {           // the halo row of the run: 40 positions, wave = (position tile pt0, channel half ct)
@@ -424,7 +479,9 @@ __global__ __launch_bounds__(256) void k_sub01(const float *__restrict__ feats, 
                     acc = nacc;
                 }
             }
+            SUB_STAMP(1);
             __syncthreads();            // conv0 done: the tile is complete
+            SUB_STAMP(2);
             // ---- depthwise 3x3 stride 2 over the tile: all nine reads of an item are issued, then its 36 FMAs; the tap
             // left of the first position (f = -1) reads position 0 instead and its FMAs are dropped
             {
@@ -461,10 +518,14 @@ __global__ __launch_bounds__(256) void k_sub01(const float *__restrict__ feats, 
                     if (t2 < t2_max) *(half4 *)(o + i * QV_SUBC) = h;
                 }
             }
+            SUB_STAMP(3);
             if (more) mel_store(nxt, (it + 1) & 1);
+            SUB_STAMP(4);
             __syncthreads();            // the depthwise stage has left the tile; the next step's mel rows are in LDS
+            SUB_STAMP(5);
         }
     }
+    SUB_STAMP_END;
 }
 
 // dense [B][t_max][row_elems] -> packed [sum of len][row_elems]: utterance b's valid frames become
@@ -1741,7 +1802,7 @@ void qv_kernel_variant_set(int which, int mode) {
 int qv_kernel_variant(int which) {
     static const struct Env { int v[QV_KV_COUNT]; Env() {
         const char *names[QV_KV_COUNT] = {"QVERSE_LOGMEL", "QVERSE_ORT_SUB", "QVERSE_SPANS", "QVERSE_FWD_GRAPH", "QVERSE_CTC", "QVERSE_SUB_RUN", nullptr, nullptr};
-        const int dflt[QV_KV_COUNT] = {1, 1, 1, 1, 1, 0, 0, 0};
+        const int dflt[QV_KV_COUNT] = {2, 1, 1, 1, 1, 0, 0, 0};
         for (int i = 0; i < QV_KV_COUNT; ++i) {
             const char *e = names[i] ? getenv(names[i]) : nullptr;
             v[i] = (e && e[0] >= '0' && e[0] <= '9') ? atoi(e) : dflt[i];
@@ -1755,7 +1816,10 @@ int qv_kernel_variant(int which) {
 void launch_logmel(const float *audio, int64_t n_max, const int32_t *n_samples, const FrontendTab &ft, float *feats,
                    int tm_max, double *stats, int batch, hipStream_t s) {
     double *part = stats + (size_t)batch * 2 * QV_NMEL;
-    if (qv_kernel_variant(QV_KV_LOGMEL) == 1)
+    const int variant = qv_kernel_variant(QV_KV_LOGMEL);
+    if (variant == 2)
+        hipLaunchKernelGGL(lmv::k_logmel_run<QV_LOGMEL_RUN>, dim3((tm_max + 4 * QV_LOGMEL_RUN - 1) / (4 * QV_LOGMEL_RUN), batch), dim3(256), 0, s, audio, n_max, n_samples, ft, feats, tm_max);
+    else if (variant == 1)
         hipLaunchKernelGGL(lmv::k_logmel_reg<0>, dim3((tm_max + 3) / 4, batch), dim3(256), 0, s, audio, n_max, n_samples, ft, feats, tm_max);
     else
         hipLaunchKernelGGL(k_logmel, dim3((tm_max + 3) / 4, batch), dim3(256), 0, s, audio, n_max, n_samples, ft, feats, tm_max);
@@ -1777,14 +1841,16 @@ void launch_conv0(const float *feats, int tm_max, const int32_t *len_in, const d
 // on it).  A CU holds two blocks, so the chip takes 512 at a time: the cost of a run length is (rounds of 512 blocks) x
 // (2 x tiles + 1: a block's statistics, first mel rows and halo row cost about half a tile).  64 x 10 s = 64 x 63 tiles:
 // 8 runs of 8 = 512 blocks; a small batch gets short runs and fills the chip instead.  QV_KV_SUB_RUN forces 1, 2 or
-// SUB_MAX_RUN tiles (tests: the run length changes no bit).
+// SUB_MAX_RUN tiles, 4 forces SUB_RES_RUN (tests: the run length changes no bit).  The choice stops at SUB_RES_RUN tiles,
+// the longest run whose mel rows stay resident in LDS (k_sub01<true>); a run of 4 measured like one of 8 before that
+// (profiles/r09_a_run_length_sweep.txt), and resident rows take three of a run's four mel passes away.
 int qv_sub01_run_tiles(int batch, int t2_max) {
     const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, forced = qv_kernel_variant(QV_KV_SUB_RUN);
     int best = 1;
-    if (forced >= 1 && forced <= 3) best = forced == 3 ? SUB_MAX_RUN : forced;
+    if (forced >= 1 && forced <= 4) best = forced == 3 ? SUB_MAX_RUN : forced == 4 ? SUB_RES_RUN : forced;
     else {
         long best_cost = -1;
-        for (int run = 1; run <= SUB_MAX_RUN; ++run) {
+        for (int run = 1; run <= SUB_RES_RUN; ++run) {
             const long blocks = (long)batch * ((n_tiles + run - 1) / run), cost = (blocks + 511) / 512 * (2 * run + 1);
             if (best_cost < 0 || cost < best_cost) { best = run; best_cost = cost; }
         }
@@ -1796,8 +1862,11 @@ void launch_sub01(const float *feats, int tm_max, const int32_t *len_mel, const 
                   const float *b0, const int32_t *len1, const float *w1, const float *b1, half_t *out, int t2_max, int batch,
                   hipStream_t s) {
     const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, run = qv_sub01_run_tiles(batch, t2_max);
-    hipLaunchKernelGGL(k_sub01, dim3(1, (n_tiles + run - 1) / run, batch), dim3(256), 0, s, feats, tm_max,
-                       len_mel, stats, w0, b0, len1, w1, b1, out, t2_max, run);
+    const dim3 grid(1, (n_tiles + run - 1) / run, batch);
+    if (run <= SUB_RES_RUN)
+        hipLaunchKernelGGL(k_sub01<true>, grid, dim3(256), 0, s, feats, tm_max, len_mel, stats, w0, b0, len1, w1, b1, out, t2_max, run);
+    else
+        hipLaunchKernelGGL(k_sub01<false>, grid, dim3(256), 0, s, feats, tm_max, len_mel, stats, w0, b0, len1, w1, b1, out, t2_max, run);
 }
 
 void launch_dwconv2d(const half_t *in, int tin_max, int fin, const int32_t *len_in, const float *w, const float *bias,

@@ -645,11 +645,11 @@ class Engine:
         self._check(self.lib.qv_debug_attention_variant(int(mode)), "qv_debug_attention_variant")
 
     def kernel_variant(self, which: int, mode: int):
-        """process-wide variant of one kernel (qv_debug_kernel_variant): which 0 = log-mel FFT (0 LDS, 1 registers),
+        """process-wide variant of one kernel (qv_debug_kernel_variant): which 0 = log-mel FFT (0 LDS, 1 registers, 2 registers and a wave walks a run of frames),
         1 = precision 2's conv.0 (0 VALU, 1 f32 matrix pipe), 2 = span pass (0 one walk per span, 1 prefix-shared),
         3 = forward of a multi-context engine (0 plain launches, 1 hipGraph replay of a repeating shape),
         5 = tiles of four conv.2 frames a block of the fused subsampling kernel walks (0 from the launch shape, 1 / 2 tiles,
-        3 the maximum), 6 = steps of three conv.5 frames a block of the conv.3 + conv.5 kernel walks (same codes);
+        3 the maximum, 4 the maximum with the run's mel rows resident in LDS), 6 = steps of three conv.5 frames a block of the conv.3 + conv.5 kernel walks (same codes);
         -1 = environment / default.  Identical bits either way."""
         self._check(self.lib.qv_debug_kernel_variant(int(which), int(mode)), "qv_debug_kernel_variant")
 
