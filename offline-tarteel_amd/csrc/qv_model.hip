@@ -11,6 +11,7 @@
 // every activation buffer is allocated once at qv_create for (max_batch, max_samples).
 
 #include "qv_common.h"
+#include "qv_graph.h"
 #include "qv_layers.h"
 #include "qv_ort.h"
 
@@ -245,33 +246,46 @@ struct FwdKey {
         return audio == o.audio && logprobs == o.logprobs && pos == o.pos && n_max == o.n_max && !memcmp(v, o.v, sizeof(v));
     }
 };
-struct FwdGraph { FwdKey key; hipGraphExec_t exec; int64_t last_use; };
+
+// The length block of a batch, [6 * max_batch + 1] int32 (the device copy lens_dev and every pinned host slot): five rows
+// of [max_batch] -- samples, mel frames, frames after each stride-2 stage -- then [max_batch + 1] packed row offsets.
+struct LenRows {
+    int32_t *n_samples, *tm, *l1, *l2, *l3, *row_off;
+    LenRows(int32_t *base, int max_batch) : n_samples(base), tm(base + max_batch), l1(base + 2 * max_batch), l2(base + 3 * max_batch),
+                                            l3(base + 4 * max_batch), row_off(base + 5 * max_batch) {}
+    static size_t words(size_t max_batch) { return 6 * max_batch + 1; }
+};
+// Everything the host computes from the clip lengths of one batch; the schedule and the graph key read it and nothing else.
+// Encoder activations are PACKED: utterance b owns rows [off[b], off[b] + l3[b]) of every [M][*] tensor and M = sum of the
+// valid frame counts, so a ragged batch pays for no padding frames (equal lengths give off[b] = b * T, the dense layout).
+struct FwdShape {
+    int B, M, T, t_pad;                  // utterances; packed rows; T = t3m: attention tile count, relative-position table, Vt row pitch (t_pad: T rounded up to 32)
+    int tm_max, t1m, t2m, t3m, t3min;    // longest mel / stage-1 / stage-2 / stage-3 frame counts, shortest stage-3 count
+    int t_max_out, t_min_pad;            // frames per utterance of the caller's log-prob tensor; its first row that may need zeroing (-1: none do)
+};
+inline int pad32(int t) { return (t + 31) / 32 * 32; }
+using FwdGraphs = FwdGraphCache<FwdKey, hipGraphExec_t, QV_FWD_GRAPHS>;   // qv_graph_policy.h
 
 // per-context state: the activations of one batch in flight, their staging buffer, the context's forward graphs
 struct QvActs {
     float *feats, *x, *logits;
     double *mel_stats;   // [batch][80][2] per-feature sum / sum of squares, then the per-chunk partial sums (qv_melstats_doubles)
     half_t *c0, *c1, *c1p, *c2, *c2p, *c2k, *ln, *hbuf, *qk, *vt, *att, *glu, *dw, *xh;
-    int32_t *lens_dev;   // [5][max_batch]: n_samples, tm, l1, l2, l3; then [max_batch + 1] packed row offsets
+    int32_t *lens_dev;   // the length block (LenRows)
     int32_t *row_map;    // [M] utterance << 16 | frame of every packed row (written by k_pack_rows)
-    int32_t *lens_host = nullptr;   // pinned, QV_STAGE_SLOTS slots of [6 * max_batch + 1] (see QvCtx)
+    int32_t *lens_host = nullptr;   // pinned, QV_STAGE_SLOTS slots of one length block each (see QvCtx)
     hipEvent_t lens_copied[QV_STAGE_SLOTS] = {};
     bool lens_pending[QV_STAGE_SLOTS] = {};
     int lens_slot = 0, lens_last = 0;   // next slot to fill; slot of the last forward (qv_model_tap reads its offsets)
     float *tap_x;        // [N_LAYERS+1][M][512] when save_taps
-    int last_batch = 0, last_tmax = 0, last_tm_max = 0, last_rows = 0, last_t2m = 0;
+    FwdShape last = {};  // shape of the context's last forward (qv_model_tap, the GEMM replay hooks)
     bool sub35 = false;  // f16 front end: conv.3 + conv.5 as k_sub35, c2 packed (c1p / c2p do not exist)
     // QV_PREC_ORT_MIXED: the float32 tensors in front of the quantisers, the s8 operand buffer, the range keys
     float *c1f, *c1pf, *c2f, *gluf, *dwf;
     int8_t *q8;
     uint32_t *mm;        // [MM_SITES][max_batch][QV_MM_STRIDE]: {min, max} keys at the front of each utterance's slot
     float *tap_lnc, *tap_glu, *tap_dw;   // [N_LAYERS][M][512] each when save_taps
-    FwdGraph fwd_graph[QV_FWD_GRAPHS];
-    int n_fwd_graph = 0;
-    int64_t fwd_tick = 0, fwd_last_capture = 0;   // forwards seen by the context / the one that captured last
-    bool fwd_disabled = false;                    // a capture or instantiate failed on this context: plain launches from then on
-    FwdKey fwd_seen[QV_FWD_GRAPHS] = {};          // keys of the context's last few uncaptured forwards: a shape is captured when it comes back
-    int fwd_seen_at = 0;
+    FwdGraphs fwd_graphs;
 };
 
 struct QvModel {
@@ -293,6 +307,7 @@ struct QvModel {
     LayerW L[N_LAYERS];
     // capacities
     int max_batch, max_samples, tm_cap, t1_cap, t2_cap, t3_cap;
+    size_t rows_cap;     // max_batch * t3_cap: rows of the [M][*] activation tensors
     std::map<int, half_t *> pos_cache;  // t_max -> projected positions f16 [2*t_max-1][17*512]
     bool save_taps;
     // forward graphs of all contexts together (qv_debug_forward_graph_stats / _failures): graph launches, captures, and
@@ -657,6 +672,25 @@ int prepare_weights(qv_engine *eng, QvModel *m, const HostWeights &hw) {
 
 int stage_len(int t) { return (t + 2 - 3) / 2 + 1; }
 
+// GEMM arguments, out[M][ldo] = epilogue(alpha * A[M][K] x W[N][K]^T + bias) with A and W row-major at pitch K: one builder for
+// the f16 / W4 / W8 weights, one for the A8W8 ones (s8 operands in q8; K counts byte pairs; `own` says which utterance's range
+// keys a row reads: packed rows through row_map, dense ones through len).  Whatever else a site needs it sets itself.
+GemmArgs gemm_args(const half_t *A, const WMat &W, const float *bias, void *out, int M, int N, int K, int ldo, float alpha) {
+    GemmArgs g = {};
+    g.A = A; g.W = W.w; g.Wq = W.q; g.wscale = W.sc; g.W8 = W.q8; g.w8scale = W.sc8; g.bias = bias; g.out = out;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = ldo; g.alpha = alpha;
+    return g;
+}
+GemmArgs gemm_args(const int8_t *q8, const OrtConv &W, const float *bias, void *out, int M, int N, int K, int ldo,
+                   const RowOwner &own, const uint32_t *mm_in, uint32_t *mm_out) {
+    GemmArgs g = {};
+    g.A = (const half_t *)q8; g.Wi8 = W.wq; g.wsum = W.wsum; g.w_scale = W.scale; g.bias = bias; g.out = out;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = ldo; g.alpha = 1.f;
+    g.row_map = own.row_map; g.len = own.len; g.rows_per_utt = own.rows_per_utt; g.f_per_t = own.f_per_t;
+    g.mm_in = mm_in; g.mm_out = mm_out;
+    return g;
+}
+
 // projected relative positions for every layer, cached per t_max (weights are fixed)
 int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const half_t **out) {
     auto it = m->pos_cache.find(t_max);
@@ -675,10 +709,7 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const hal
     QV_HIP(hipMalloc((void **)&d_pe, pe.size() * sizeof(half_t)));
     QV_HIP(hipMalloc((void **)&d_out, (size_t)R * N_LAYERS * QV_D * sizeof(half_t)));
     QV_HIP(hipMemcpyAsync(d_pe, pe.data(), pe.size() * sizeof(half_t), hipMemcpyHostToDevice, stream));
-    GemmArgs g = {};
-    g.A = d_pe; g.W = m->pos_w.w; g.Wq = m->pos_w.q; g.wscale = m->pos_w.sc; g.bias = m->zero_bias; g.out = d_out;
-    g.M = R; g.N = N_LAYERS * QV_D; g.K = QV_D; g.lda = QV_D; g.ldw = QV_D; g.ldo = N_LAYERS * QV_D; g.alpha = 1.f;
-    launch_gemm(EPI_F16, g, stream);
+    launch_gemm(EPI_F16, gemm_args(d_pe, m->pos_w, m->zero_bias, d_out, R, N_LAYERS * QV_D, QV_D, N_LAYERS * QV_D, 1.f), stream);
     QV_HIP(hipStreamSynchronize(stream));
     QV_HIP(hipFree(d_pe));
     m->allocs.push_back(d_out);
@@ -690,8 +721,7 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const hal
 // activations, staging buffer and events of execution context k
 int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused, bool sub35_unfused) {
     QvActs &a = m->ctx_acts[k];
-    const size_t Bz = (size_t)m->max_batch, M = Bz * m->t3_cap;
-    const int t_pad_cap = (m->t3_cap + 31) / 32 * 32;
+    const size_t Bz = (size_t)m->max_batch, M = m->rows_cap, lens_words = LenRows::words(Bz);
     TRY(dal(eng, m, Bz * m->tm_cap * QV_NMEL, &a.feats));
     TRY(dal(eng, m, qv_melstats_doubles(Bz), &a.mel_stats));
     // the conv0 activation only exists on the two-kernel cross-check path (QVERSE_SUB_UNFUSED=1)
@@ -708,15 +738,15 @@ int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused, bool sub3
     TRY(dal(eng, m, M * QV_D, &a.ln));
     TRY(dal(eng, m, M * QV_FF, &a.hbuf));
     TRY(dal(eng, m, M * 2 * QV_D, &a.qk));
-    TRY(dal(eng, m, Bz * QV_D * t_pad_cap, &a.vt));
+    TRY(dal(eng, m, Bz * QV_D * pad32(m->t3_cap), &a.vt));
     TRY(dal(eng, m, M * QV_D, &a.att));
     TRY(dal(eng, m, M * QV_D, &a.glu));
     TRY(dal(eng, m, M * QV_D, &a.dw));
     TRY(dal(eng, m, M * QV_D, &a.xh));
     TRY(dal(eng, m, M * HEAD_N, &a.logits));
-    TRY(dal(eng, m, Bz * 6 + 1, &a.lens_dev));
+    TRY(dal(eng, m, lens_words, &a.lens_dev));
     TRY(dal(eng, m, M, &a.row_map));
-    QV_HIP(hipHostMalloc((void **)&a.lens_host, sizeof(int32_t) * (Bz * 6 + 1) * QV_STAGE_SLOTS, hipHostMallocDefault));
+    QV_HIP(hipHostMalloc((void **)&a.lens_host, sizeof(int32_t) * lens_words * QV_STAGE_SLOTS, hipHostMallocDefault));
     for (int i = 0; i < QV_STAGE_SLOTS; ++i) QV_HIP(hipEventCreateWithFlags(&a.lens_copied[i], hipEventDisableTiming));
     if (m->save_taps) TRY(dal(eng, m, (size_t)(N_LAYERS + 1) * M * QV_D, &a.tap_x));
     if (m->ort) {
@@ -762,8 +792,7 @@ int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out) {
     m->t1_cap = stage_len(m->tm_cap);
     m->t2_cap = stage_len(m->t1_cap);
     m->t3_cap = stage_len(m->t2_cap);
-    size_t Bz = (size_t)B, M = Bz * m->t3_cap;
-    int t_pad_cap = (m->t3_cap + 31) / 32 * 32;
+    const size_t Bz = (size_t)B, M = m->rows_cap = Bz * m->t3_cap;
     {
         // the GEMM kernels address their operands through buffer descriptors with a 32-bit size and 32-bit byte offsets:
         // refuse capacities where the largest operand (the first subsampling activation, the 2560-wide projection input,
@@ -791,308 +820,293 @@ void qv_model_destroy(QvModel *m) {
     if (!m) return;
     for (void *p : m->allocs) (void)hipFree(p);
     for (QvActs &a : m->ctx_acts) {
-        for (int i = 0; i < a.n_fwd_graph; ++i) (void)hipGraphExecDestroy(a.fwd_graph[i].exec);
+        for (int i = 0; i < a.fwd_graphs.n; ++i) (void)hipGraphExecDestroy(a.fwd_graphs.slot[i].handle);
         if (a.lens_host) (void)hipHostFree(a.lens_host);
         for (hipEvent_t e : a.lens_copied) if (e) (void)hipEventDestroy(e);
     }
     delete m;
 }
 
-int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, const int64_t *len_host, int batch, int64_t n_max,
-                     float *logprobs, int t_max_out, int32_t *t_out_host, hipStream_t s, bool zero_pad_rows, bool may_graph) {
+namespace {
+
+LenRows dev_lens(const QvModel *m, const QvActs &a) { return {a.lens_dev, m->max_batch}; }
+LenRows host_lens(const QvModel *m, const QvActs &a, int slot) { return {a.lens_host + slot * LenRows::words(m->max_batch), m->max_batch}; }
+
+// The shape of one batch: validates the clip lengths, fills the context's next pinned staging slot with the length block and
+// queues its copy to lens_dev (the slot is reused only after the event behind that copy), writes the frame counts to t_out_host.
+int fwd_shape(qv_engine *eng, const QvModel *m, QvActs &a, const int64_t *len_host, int batch, int64_t n_max, int t_max_out,
+              bool zero_pad_rows, int32_t *t_out_host, hipStream_t s, FwdShape *out) {
     if (batch < 1 || batch > m->max_batch) { qv_set_error(eng, "batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
-    QvActs &a = m->ctx_acts[k];
-    int B = batch, MB = m->max_batch;
-    int tm_max = 0, t1m = 0, t2m = 0, t3m = 0, t3min = INT32_MAX, rows = 0;
+    FwdShape sh = {};
+    sh.B = batch; sh.t3min = INT32_MAX; sh.t_max_out = t_max_out;
     const int slot = a.lens_slot;
     if (a.lens_pending[slot]) { QV_HIP(hipEventSynchronize(a.lens_copied[slot])); a.lens_pending[slot] = false; }
-    int32_t *lh = a.lens_host + (size_t)slot * (MB * 6 + 1);
-    for (int b = 0; b < B; ++b) {
+    const LenRows lh = host_lens(m, a, slot);
+    for (int b = 0; b < batch; ++b) {
         int64_t n = len_host[b];
         if (n < 400 || n > n_max || n > m->max_samples) {   // (samples, not mel frames: up to 159 samples more would still fit tm_cap)
             qv_set_error(eng, "utterance length out of range (need 400 <= n <= capacity)");
             return QV_ERR_CAPACITY;
         }
         int tm = (int)(n / 160 + 1), l1 = stage_len(tm), l2 = stage_len(l1), l3 = stage_len(l2);
-        lh[0 * MB + b] = (int32_t)n; lh[1 * MB + b] = tm; lh[2 * MB + b] = l1; lh[3 * MB + b] = l2; lh[4 * MB + b] = l3;
-        tm_max = std::max(tm_max, tm); t1m = std::max(t1m, l1); t2m = std::max(t2m, l2); t3m = std::max(t3m, l3);
-        t3min = std::min(t3min, l3);
+        lh.n_samples[b] = (int32_t)n; lh.tm[b] = tm; lh.l1[b] = l1; lh.l2[b] = l2; lh.l3[b] = l3;
+        sh.tm_max = std::max(sh.tm_max, tm); sh.t1m = std::max(sh.t1m, l1); sh.t2m = std::max(sh.t2m, l2); sh.t3m = std::max(sh.t3m, l3);
+        sh.t3min = std::min(sh.t3min, l3);
         t_out_host[b] = l3;
-        lh[5 * MB + b] = rows;   // first packed row of utterance b
-        rows += l3;
+        lh.row_off[b] = sh.M;   // first packed row of utterance b
+        sh.M += l3;
     }
-    lh[5 * MB + B] = rows;
-    if (t_max_out < t3m) { qv_set_error(eng, "t_max smaller than the longest utterance's frame count"); return QV_ERR_ARG; }
-    // Encoder activations are PACKED: utterance b owns rows [off[b], off[b] + l3[b]) of every [M][*]
-    // tensor and M = sum of the valid frame counts, so a ragged batch pays for no padding frames
-    // (equal lengths give off[b] = b * T, the dense layout).  T = longest utterance: attention tile
-    // count, relative-position table, Vt row pitch.
-    const int T = t3m;
-    const int M = rows;
-    const int t_pad = (T + 31) / 32 * 32;
-    QV_HIP(hipMemcpyAsync(a.lens_dev, lh, sizeof(int32_t) * (MB * 6 + 1), hipMemcpyHostToDevice, s));
+    lh.row_off[batch] = sh.M;
+    if (t_max_out < sh.t3m) { qv_set_error(eng, "t_max smaller than the longest utterance's frame count"); return QV_ERR_ARG; }
+    sh.T = sh.t3m; sh.t_pad = pad32(sh.T); sh.t_min_pad = zero_pad_rows ? std::min(t_max_out, sh.t3min) : -1;
+    QV_HIP(hipMemcpyAsync(a.lens_dev, lh.n_samples, sizeof(int32_t) * LenRows::words(m->max_batch), hipMemcpyHostToDevice, s));
     QV_HIP(hipEventRecord(a.lens_copied[slot], s));
     a.lens_pending[slot] = true;
     a.lens_last = slot;
     a.lens_slot = (slot + 1) % QV_STAGE_SLOTS;
-    const int32_t *d_n = a.lens_dev, *d_tm = d_n + MB, *d_l1 = d_n + 2 * MB, *d_l2 = d_n + 3 * MB, *d_l3 = d_n + 4 * MB,
-                  *d_off = d_n + 5 * MB;
-    const half_t *posp = nullptr;
-    TRY(get_pos(eng, m, T, s, &posp));
+    *out = sh;
+    return QV_OK;
+}
 
-    // dev-only timing experiments, compiled in with -DQV_DEV_HOOKS only (results are garbage when set): QVERSE_SKIP bit mask -- 1 k_layernorm, 2 k_layernorm2,
-    // 4 attention, 8 dwconv1d, 32 front-end (log-mel + subsampling convs), 64 every encoder GEMM
+// dev-only timing experiments, compiled in with -DQV_DEV_HOOKS only (results are garbage when set): QVERSE_SKIP bit mask -- 1 k_layernorm, 2 k_layernorm2,
+// 4 attention, 8 dwconv1d, 32 front-end (log-mel + subsampling convs), 64 every encoder GEMM
+// ... and QVERSE_DUP launches the (idempotent) kernels of a class TWICE -- results unchanged, the slowdown is
+// the class's marginal cost under the current overlap: 1 k_layernorm, 4 attention, 8 dwconv1d, 64 FFN-up/QKV/GLU GEMMs
 #ifdef QV_DEV_HOOKS
-    static const int skip = [] { const char *e = getenv("QVERSE_SKIP"); return e ? atoi(e) : 0; }();
-    // ... and QVERSE_DUP launches the (idempotent) kernels of a class TWICE -- results unchanged, the slowdown is
-    // the class's marginal cost under the current overlap: 1 k_layernorm, 4 attention, 8 dwconv1d, 64 FFN-up/QKV/GLU GEMMs
-    static const int dup = [] { const char *e = getenv("QVERSE_DUP"); return e ? atoi(e) : 0; }();
-#else   // product builds carry neither hook (python offline-tarteel_amd/build.py --dev-hooks compiles them in)
-    constexpr int skip = 0, dup = 0;
+int hook_skip() { static const int v = [] { const char *e = getenv("QVERSE_SKIP"); return e ? atoi(e) : 0; }(); return v; }
+int hook_dup() { static const int v = [] { const char *e = getenv("QVERSE_DUP"); return e ? atoi(e) : 0; }(); return v; }
+#else   // product builds carry neither hook (python offline-tarteel_amd/build.py --dev-hooks compiles them in): hooked() is the bare call
+constexpr int hook_skip() { return 0; }
+constexpr int hook_dup() { return 0; }
 #endif
-    const int att_variant = qv_attention_variant();   // read once per forward: all 17 layers use the same kernel
-    int t_min_pad = -1;
-    if (zero_pad_rows) {
-        t_min_pad = t_max_out;
-        for (int b = 0; b < B; ++b) t_min_pad = std::min(t_min_pad, (int)t_out_host[b]);
-    }
-    auto launch_all = [&]() -> int {
-    uint32_t *mm_base = a.mm;
-    auto mm_site = [&](int site) { return mm_base + (size_t)site * MB * QV_MM_STRIDE; };
-    if (m->ort) {
-        // QV_PREC_ORT_MIXED front-end: every Conv is DynamicQuantizeLinear -> ConvInteger (qv_ort.h); the strided /
-        // depthwise ones as exact integer stencils, the two pointwise ones on the i8 MFMA
-        launch_mm_init(a.mm, (size_t)MM_SITES * MB * QV_MM_STRIDE, s);
-        launch_logmel(audio, n_max, d_n, m->ft, a.feats, tm_max, a.mel_stats, B, s);
-        launch_mel_minmax(a.feats, d_n, tm_max, a.mel_stats, mm_site(MM_MEL), B, s);
-        for (int pass = 0; pass < 2; ++pass)
-            launch_sub01_ort(pass, a.feats, tm_max, d_tm, a.mel_stats, m->o_c0.wq, m->o_c0.scale, m->c0_b, d_l1, m->o_dw2.wq,
-                             m->o_dw2.scale, m->dw2_b, d_l2, mm_site(MM_MEL), mm_site(MM_C0), mm_site(MM_C1), a.c1f, t2m, B, s);
-        GemmArgs g = {};
-        g.alpha = 1.f;
-        g.len = d_l2; g.rows_per_utt = t2m * 20; g.f_per_t = 20;
-        launch_quant_rows(a.c1f, B * t2m * 20, QV_SUBC, RowOwner{nullptr, g.len, g.rows_per_utt, g.f_per_t}, mm_site(MM_C1), a.q8, s);
-        g.A = (const half_t *)a.q8; g.Wi8 = m->o_pw3.wq; g.wsum = m->o_pw3.wsum; g.w_scale = m->o_pw3.scale; g.bias = m->pw3_b;
-        g.out = a.c1pf; g.mm_in = mm_site(MM_C1); g.mm_out = mm_site(MM_C1P);
-        g.M = B * t2m * 20; g.N = QV_SUBC; g.K = QV_SUBC / 2; g.lda = QV_SUBC / 2; g.ldw = QV_SUBC / 2; g.ldo = QV_SUBC;
-        launch_gemm(EPI_F32_RELU, g, s);
-        launch_dwconv2d_ort(a.c1pf, t2m, 20, d_l2, m->o_dw5.wq, m->o_dw5.scale, m->dw5_b, d_l3, mm_site(MM_C1P), mm_site(MM_C2),
-                            a.c2f, t3m, 10, B, s);
-        g.len = d_l3; g.rows_per_utt = t3m * 10; g.f_per_t = 10;
-        launch_quant_rows(a.c2f, B * t3m * 10, QV_SUBC, RowOwner{nullptr, g.len, g.rows_per_utt, g.f_per_t}, mm_site(MM_C2), a.q8, s);
-        g.Wi8 = m->o_pw6.wq; g.wsum = m->o_pw6.wsum; g.w_scale = m->o_pw6.scale; g.bias = m->pw6_b;
-        g.out = a.c2p; g.mm_in = mm_site(MM_C2); g.mm_out = nullptr; g.M = B * t3m * 10;
-        launch_gemm(EPI_F16_RELU, g, s);
-        launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
-        GemmArgs o = {};
-        o.A = a.c2k; o.W = m->sub_out_w; o.bias = m->sub_out_b; o.out = a.x;
-        o.M = M; o.N = QV_D; o.K = 2560; o.lda = 2560; o.ldw = 2560; o.ldo = QV_D; o.alpha = sqrtf((float)QV_D);
-        o.in_flight = m->n_ctx;
-        launch_gemm(EPI_F32, o, s);
-    } else
-    if (!(skip & 32)) {
-    launch_logmel(audio, n_max, d_n, m->ft, a.feats, tm_max, a.mel_stats, B, s);
-    if (a.c0) {
-        // cross-check path: conv0 and the depthwise conv as two kernels through HBM
-        launch_conv0(a.feats, tm_max, d_tm, a.mel_stats, m->c0_w, m->c0_b, a.c0, t1m, B, s);
-        launch_dwconv2d(a.c0, t1m, 40, d_l1, m->dw2_w, m->dw2_b, a.c1, t2m, 20, B, s);
-    } else {
-        launch_sub01(a.feats, tm_max, d_tm, a.mel_stats, m->c0_w, m->c0_b, d_l1, m->dw2_w, m->dw2_b, a.c1, t2m, B, s);
-    }
-    GemmArgs g = {};
-    g.alpha = 1.f;
-    g.N = QV_SUBC; g.K = QV_SUBC; g.lda = QV_SUBC; g.ldw = QV_SUBC; g.ldo = QV_SUBC;
-    if (a.sub35) {
-        // conv.3 + conv.5 in one kernel, c2 packed from here on: conv.6 runs on the valid rows only and writes c2k itself
-        launch_sub35(a.c1, t2m, m->pw3_w, m->pw3_b, m->dw5_w, m->dw5_b, d_l2, d_l3, d_off, a.c2, a.row_map, t3m, B, s);
-        g.A = a.c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = a.c2k; g.M = M * 10;
-        launch_gemm(EPI_F16_RELU, g, s);
-    } else {
-        // cross-check path: four launches, c1p and the dense c2 / c2p through HBM
-        g.A = a.c1; g.W = m->pw3_w; g.bias = m->pw3_b; g.out = a.c1p; g.M = B * t2m * 20;
-        launch_gemm(EPI_F16_RELU, g, s);
-        launch_dwconv2d(a.c1p, t2m, 20, d_l2, m->dw5_w, m->dw5_b, a.c2, t3m, 10, B, s);
-        g.A = a.c2; g.W = m->pw6_w; g.bias = m->pw6_b; g.out = a.c2p; g.M = B * t3m * 10;
-        launch_gemm(EPI_F16_RELU, g, s);
-        launch_pack_rows(a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
-    }
-    // Linear(2560 -> 512) and xscaling (x * sqrt(d_model)) in one epilogue
-    g.A = a.c2k; g.W = m->sub_out_w; g.bias = m->sub_out_b; g.out = a.x;
-    g.M = M; g.N = QV_D; g.K = 2560; g.lda = 2560; g.ldw = 2560; g.ldo = QV_D; g.alpha = sqrtf((float)QV_D);
-    g.in_flight = m->n_ctx;
-    launch_gemm(EPI_F32, g, s);
-    } else {
-        // (front end skipped: the encoder still needs a row_map; on the packed path the c2 buffer stands in for c2p)
-        launch_pack_rows(a.sub35 ? a.c2 : a.c2p, t3m, 10 * QV_SUBC, d_l3, d_off, a.c2k, a.row_map, B, s);
-    }
-    if (m->save_taps) QV_HIP(hipMemcpyAsync(a.tap_x, a.x, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
+template <typename Fn>   // a launch of hook class `bit`: dropped under QVERSE_SKIP & bit, issued twice under QVERSE_DUP & bit (where may_dup)
+inline void hooked(int bit, Fn &&launch, bool may_dup = true) {
+    if (!(hook_skip() & bit)) launch();
+    if (may_dup && (hook_dup() & bit)) launch();
+}
 
-    if (!(skip & 1)) launch_layernorm(a.x, m->L[0].ln_g[0], m->L[0].ln_b[0], a.ln, M, s);
+// an encoder GEMM on M packed rows of utterances of up to T frames
+GemmArgs layer_gemm_args(const QvModel *m, const QvActs &a, int M, int T, const half_t *A, int K, const WMat &W, const float *bias,
+                         void *out, int N, int ldo, float alpha) {
+    GemmArgs g = gemm_args(A, W, bias, out, M, N, K, ldo, alpha);
+    g.out2 = a.vt; g.t_max = T; g.t_pad = pad32(T); g.row_map = a.row_map; g.in_flight = m->n_ctx;
+    return g;
+}
+// QV_PREC_ORT_MIXED: pointwise_conv1 + GLU of layer l on the s8 rows in q8; input range in the layer's first site, the output's goes to its second
+GemmArgs ort_pw1_args(const QvModel *m, const QvActs &a, int M, int l) {
+    uint32_t *mm_ln = a.mm + (size_t)MM_LAYER(l) * m->max_batch * QV_MM_STRIDE;
+    return gemm_args(a.q8, m->L[l].o_pw1, m->L[l].pw1_b, a.gluf, M, 2 * QV_D, QV_D / 2, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_ln,
+                     mm_ln + (size_t)m->max_batch * QV_MM_STRIDE);
+}
+
+// The forward schedule: what the stages of one forward share, and one function per stage -- launch_all calls them in launch
+// order.  A new fused kernel replaces launches inside ONE of them.
+struct Fwd {
+    qv_engine *eng; const QvModel *m; const QvActs &a; const FwdShape &sh; const LenRows d; const float *audio; int64_t n_max;
+    const half_t *posp; int att_variant; hipStream_t s;
+    uint32_t *mm(int site) const { return a.mm + (size_t)site * m->max_batch * QV_MM_STRIDE; }   // QV_PREC_ORT_MIXED: range keys of a quantiser site
+
+    void sub_out() const {   // Linear(2560 -> 512) and xscaling (x * sqrt(d_model)) in one epilogue
+        GemmArgs g = gemm_args(a.c2k, WMat{m->sub_out_w}, m->sub_out_b, a.x, sh.M, QV_D, 2560, QV_D, sqrtf((float)QV_D));
+        g.in_flight = m->n_ctx;
+        launch_gemm(EPI_F32, g, s);
+    }
+    void frontend_f16() const {
+        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, sh.B, s);
+        if (a.c0) {
+            // cross-check path: conv0 and the depthwise conv as two kernels through HBM
+            launch_conv0(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, a.c0, sh.t1m, sh.B, s);
+            launch_dwconv2d(a.c0, sh.t1m, 40, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, 20, sh.B, s);
+        } else {
+            launch_sub01(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, sh.B, s);
+        }
+        auto pw = [&](const half_t *A, const half_t *W, const float *bias, half_t *out, int M) {   // pointwise conv + ReLU
+            launch_gemm(EPI_F16_RELU, gemm_args(A, WMat{W}, bias, out, M, QV_SUBC, QV_SUBC, QV_SUBC, 1.f), s);
+        };
+        if (a.sub35) {
+            // conv.3 + conv.5 in one kernel, c2 packed from here on: conv.6 runs on the valid rows only and writes c2k itself
+            launch_sub35(a.c1, sh.t2m, m->pw3_w, m->pw3_b, m->dw5_w, m->dw5_b, d.l2, d.l3, d.row_off, a.c2, a.row_map, sh.t3m, sh.B, s);
+            pw(a.c2, m->pw6_w, m->pw6_b, a.c2k, sh.M * 10);
+        } else {
+            // cross-check path: four launches, c1p and the dense c2 / c2p through HBM
+            pw(a.c1, m->pw3_w, m->pw3_b, a.c1p, sh.B * sh.t2m * 20);
+            launch_dwconv2d(a.c1p, sh.t2m, 20, d.l2, m->dw5_w, m->dw5_b, a.c2, sh.t3m, 10, sh.B, s);
+            pw(a.c2, m->pw6_w, m->pw6_b, a.c2p, sh.B * sh.t3m * 10);
+            launch_pack_rows(a.c2p, sh.t3m, 10 * QV_SUBC, d.l3, d.row_off, a.c2k, a.row_map, sh.B, s);
+        }
+        sub_out();
+    }
+    // QV_PREC_ORT_MIXED front-end: every Conv is DynamicQuantizeLinear -> ConvInteger (qv_ort.h); the strided /
+    // depthwise ones as exact integer stencils, the two pointwise ones on the i8 MFMA
+    void frontend_ort() const {
+        const int B = sh.B, M2 = B * sh.t2m * 20, M3 = B * sh.t3m * 10;
+        const RowOwner own2 = {nullptr, d.l2, sh.t2m * 20, 20}, own3 = {nullptr, d.l3, sh.t3m * 10, 10};   // dense rows
+        launch_mm_init(a.mm, (size_t)MM_SITES * m->max_batch * QV_MM_STRIDE, s);
+        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, B, s);
+        launch_mel_minmax(a.feats, d.n_samples, sh.tm_max, a.mel_stats, mm(MM_MEL), B, s);
+        for (int pass = 0; pass < 2; ++pass)
+            launch_sub01_ort(pass, a.feats, sh.tm_max, d.tm, a.mel_stats, m->o_c0.wq, m->o_c0.scale, m->c0_b, d.l1, m->o_dw2.wq,
+                             m->o_dw2.scale, m->dw2_b, d.l2, mm(MM_MEL), mm(MM_C0), mm(MM_C1), a.c1f, sh.t2m, B, s);
+        launch_quant_rows(a.c1f, M2, QV_SUBC, own2, mm(MM_C1), a.q8, s);
+        launch_gemm(EPI_F32_RELU, gemm_args(a.q8, m->o_pw3, m->pw3_b, a.c1pf, M2, QV_SUBC, QV_SUBC / 2, QV_SUBC, own2, mm(MM_C1), mm(MM_C1P)), s);
+        launch_dwconv2d_ort(a.c1pf, sh.t2m, 20, d.l2, m->o_dw5.wq, m->o_dw5.scale, m->dw5_b, d.l3, mm(MM_C1P), mm(MM_C2), a.c2f, sh.t3m, 10, B, s);
+        launch_quant_rows(a.c2f, M3, QV_SUBC, own3, mm(MM_C2), a.q8, s);
+        launch_gemm(EPI_F16_RELU, gemm_args(a.q8, m->o_pw6, m->pw6_b, a.c2p, M3, QV_SUBC, QV_SUBC / 2, QV_SUBC, own3, mm(MM_C2), nullptr), s);
+        launch_pack_rows(a.c2p, sh.t3m, 10 * QV_SUBC, d.l3, d.row_off, a.c2k, a.row_map, B, s);
+        sub_out();
+    }
+    // an encoder GEMM (hook class 64; a residual GEMM accumulates into x, so it is never doubled)
+    void gemm(int epi, const half_t *A, int K, const WMat &W, const float *bias, void *out, int N, int ldo, float alpha) const {
+        const GemmArgs g = layer_gemm_args(m, a, sh.M, sh.T, A, K, W, bias, out, N, ldo, alpha);
+        hooked(64, [&] { launch_gemm(epi, g, s); }, epi != EPI_RESID);
+    }
+    void layernorm(const LayerW &L, int i, bool may_dup = true) const {   // x -> ln through the layer's i-th LayerNorm (hook class 1)
+        hooked(1, [&] { launch_layernorm(a.x, L.ln_g[i], L.ln_b[i], a.ln, sh.M, s); }, may_dup);
+    }
+    void ffn_half(const WMat &w1, const float *b1, const WMat &w2, const float *b2) const {   // 1/2 FFN on the normalised rows in ln
+        gemm(EPI_F16_SWISH, a.ln, QV_D, w1, b1, a.hbuf, QV_FF, QV_FF, 1.f);
+        gemm(EPI_RESID, a.hbuf, QV_FF, w2, b2, a.x, QV_D, QV_D, 0.5f);
+    }
+    void attention_block(const LayerW &L, int l) const {   // rel-pos MHSA
+        layernorm(L, 1);
+        gemm(EPI_QKV, a.ln, QV_D, L.qkv_w, L.qkv_b, a.qk, 3 * QV_D, 2 * QV_D, 1.f);
+        hooked(4, [&] {
+            launch_attention(a.qk, a.vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d.l3, d.row_off, a.att, sh.T, sh.t3min,
+                             sh.t_pad, sh.B, s, att_variant);
+        });
+        gemm(EPI_RESID, a.att, QV_D, L.out_w, L.out_b, a.x, QV_D, QV_D, 1.f);
+    }
+    void conv_module_f16(const LayerW &L) const {
+        layernorm(L, 2);
+        gemm(EPI_GLU, a.ln, QV_D, L.pw1_w, L.pw1_b, a.glu, 2 * QV_D, QV_D, 1.f);
+        hooked(8, [&] { launch_dwconv1d(a.glu, L.dw_w, L.dw_b, d.l3, d.row_off, a.dw, sh.T, sh.B, s); });
+        gemm(EPI_RESID, a.dw, QV_D, L.pw2_w, L.pw2_b, a.x, QV_D, QV_D, 1.f);
+    }
+    // norm_conv -> [DQL] pointwise_conv1 + GLU -> [DQL] depthwise_conv -> BatchNorm -> Swish -> [DQL] pointwise_conv2
+    int conv_module_ort(const LayerW &L, int l) const {
+        uint32_t *mm_ln = mm(MM_LAYER(l)), *mm_glu = mm(MM_LAYER(l) + 1), *mm_dw = mm(MM_LAYER(l) + 2);
+        const RowOwner own = {a.row_map, nullptr, 0, 0};
+        const size_t n = (size_t)sh.M * QV_D, tap_off = l * n;
+        launch_ln_minmax(a.x, L.ln_g[2], L.ln_b[2], sh.M, a.row_map, mm_ln, m->save_taps ? a.tap_lnc + tap_off : nullptr, s);
+        launch_ln_quant(a.x, L.ln_g[2], L.ln_b[2], sh.M, a.row_map, mm_ln, a.q8, s);
+        launch_gemm(EPI_GLU, ort_pw1_args(m, a, sh.M, l), s);
+        launch_dwconv1d_ort(a.gluf, L.o_dw.wq, L.o_dw.scale, L.o_dw_b, L.bn_alpha, L.bn_beta, d.l3, d.row_off, mm_glu, mm_dw, a.dwf, sh.T, sh.B, s);
+        launch_quant_rows(a.dwf, sh.M, QV_D, own, mm_dw, a.q8, s);
+        launch_gemm(EPI_RESID, gemm_args(a.q8, L.o_pw2, L.pw2_b, a.x, sh.M, QV_D, QV_D / 2, QV_D, own, mm_dw, nullptr), s);
+        if (m->save_taps) {
+            QV_HIP(hipMemcpyAsync(a.tap_glu + tap_off, a.gluf, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+            QV_HIP(hipMemcpyAsync(a.tap_dw + tap_off, a.dwf, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+        }
+        return QV_OK;
+    }
+    int save_x(int idx) const {   // debug taps: x in front of layer 0 (idx 0) / behind layer idx - 1
+        const size_t n = (size_t)sh.M * QV_D;
+        if (m->save_taps) QV_HIP(hipMemcpyAsync(a.tap_x + idx * n, a.x, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+        return QV_OK;
+    }
+    int layer_out(int l) const {   // norm_out (+ next layer's first LayerNorm; hook class 2)
+        const LayerW &L = m->L[l];
+        hooked(2, [&] {
+            if (l + 1 < N_LAYERS) launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], m->L[l + 1].ln_g[0], m->L[l + 1].ln_b[0], a.ln, sh.M, s);
+            // last layer: the f16 copy of the encoder output (CTC head operand) comes out of the same pass
+            else launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], nullptr, nullptr, a.xh, sh.M, s);
+        }, false);
+        return save_x(l + 1);
+    }
+    void ctc_head() const {
+        if (m->ort) {
+            // ConvASRDecoder is a 1x1 Conv1d in the exported graph: DynamicQuantizeLinear on the encoder output, ConvInteger
+            const RowOwner own = {a.row_map, nullptr, 0, 0};
+            launch_rows_minmax(a.x, sh.M, a.row_map, mm(MM_HEAD), s);
+            launch_quant_rows(a.x, sh.M, QV_D, own, mm(MM_HEAD), a.q8, s);
+            launch_gemm(EPI_F32, gemm_args(a.q8, m->o_head, m->head_b, a.logits, sh.M, HEAD_N, QV_D / 2, HEAD_N, own, mm(MM_HEAD), nullptr), s);
+        } else {
+            launch_gemm(EPI_F32, gemm_args(a.xh, WMat{m->head_w}, m->head_b, a.logits, sh.M, HEAD_N, QV_D, HEAD_N, 1.f), s);
+        }
+    }
+};
+
+// every launch of one forward, log-mel .. log-softmax
+int launch_all(qv_engine *eng, const QvModel *m, const QvActs &a, const FwdShape &sh, const float *audio, int64_t n_max, float *logprobs,
+               const half_t *posp, int att_variant, hipStream_t s) {
+    const Fwd f = {eng, m, a, sh, dev_lens(m, a), audio, n_max, posp, att_variant, s};
+    if (m->ort) f.frontend_ort();
+    else if (!(hook_skip() & 32)) f.frontend_f16();
+    else   // (front end skipped: the encoder still needs a row_map; on the packed path the c2 buffer stands in for c2p)
+        launch_pack_rows(a.sub35 ? a.c2 : a.c2p, sh.t3m, 10 * QV_SUBC, f.d.l3, f.d.row_off, a.c2k, a.row_map, sh.B, s);
+    TRY(f.save_x(0));
+    f.layernorm(m->L[0], 0, false);
     for (int l = 0; l < N_LAYERS; ++l) {
         const LayerW &L = m->L[l];
-        auto gemm = [&](int epi, const half_t *A, int K, const WMat &W, const float *bias, void *out, int N, int ldo,
-                        float alpha) {
-            GemmArgs g = {};
-            g.A = A; g.W = W.w; g.Wq = W.q; g.wscale = W.sc; g.W8 = W.q8; g.w8scale = W.sc8; g.bias = bias; g.out = out; g.out2 = a.vt;
-            g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = ldo; g.alpha = alpha; g.t_max = T; g.t_pad = t_pad;
-            g.row_map = a.row_map; g.in_flight = m->n_ctx;
-            if (!(skip & 64)) launch_gemm(epi, g, s);
-            if ((dup & 64) && epi != EPI_RESID) launch_gemm(epi, g, s);
-        };
-        // 1/2 FFN
-        gemm(EPI_F16_SWISH, a.ln, QV_D, L.ff1_w1, L.ff1_b1, a.hbuf, QV_FF, QV_FF, 1.f);
-        gemm(EPI_RESID, a.hbuf, QV_FF, L.ff1_w2, L.ff1_b2, a.x, QV_D, QV_D, 0.5f);
-        // rel-pos MHSA
-        if (!(skip & 1)) launch_layernorm(a.x, L.ln_g[1], L.ln_b[1], a.ln, M, s);
-        if (dup & 1) launch_layernorm(a.x, L.ln_g[1], L.ln_b[1], a.ln, M, s);
-        gemm(EPI_QKV, a.ln, QV_D, L.qkv_w, L.qkv_b, a.qk, 3 * QV_D, 2 * QV_D, 1.f);
-        if (!(skip & 4)) launch_attention(a.qk, a.vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d_l3, d_off, a.att, T, t3min, t_pad, B, s, att_variant);
-        if (dup & 4) launch_attention(a.qk, a.vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d_l3, d_off, a.att, T, t3min, t_pad, B, s, att_variant);
-        gemm(EPI_RESID, a.att, QV_D, L.out_w, L.out_b, a.x, QV_D, QV_D, 1.f);
-        // conv module
-        if (m->ort) {
-            // norm_conv -> [DQL] pointwise_conv1 + GLU -> [DQL] depthwise_conv -> BatchNorm -> Swish -> [DQL] pointwise_conv2
-            uint32_t *mm_ln = mm_site(MM_LAYER(l)), *mm_glu = mm_ln + (size_t)MB * QV_MM_STRIDE, *mm_dw = mm_glu + (size_t)MB * QV_MM_STRIDE;
-            const size_t tap_off = (size_t)l * M * QV_D;
-            launch_ln_minmax(a.x, L.ln_g[2], L.ln_b[2], M, a.row_map, mm_ln, m->save_taps ? a.tap_lnc + tap_off : nullptr, s);
-            launch_ln_quant(a.x, L.ln_g[2], L.ln_b[2], M, a.row_map, mm_ln, a.q8, s);
-            GemmArgs g = {};
-            g.A = (const half_t *)a.q8; g.Wi8 = L.o_pw1.wq; g.wsum = L.o_pw1.wsum; g.w_scale = L.o_pw1.scale; g.bias = L.pw1_b;
-            g.out = a.gluf; g.M = M; g.N = 2 * QV_D; g.K = QV_D / 2; g.lda = QV_D / 2; g.ldw = QV_D / 2; g.ldo = QV_D; g.alpha = 1.f;
-            g.row_map = a.row_map; g.mm_in = mm_ln; g.mm_out = mm_glu;
-            launch_gemm(EPI_GLU, g, s);
-            launch_dwconv1d_ort(a.gluf, L.o_dw.wq, L.o_dw.scale, L.o_dw_b, L.bn_alpha, L.bn_beta, d_l3, d_off, mm_glu, mm_dw, a.dwf,
-                                T, B, s);
-            launch_quant_rows(a.dwf, M, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_dw, a.q8, s);
-            g.Wi8 = L.o_pw2.wq; g.wsum = L.o_pw2.wsum; g.w_scale = L.o_pw2.scale; g.bias = L.pw2_b;
-            g.out = a.x; g.N = QV_D; g.mm_in = mm_dw; g.mm_out = nullptr;
-            launch_gemm(EPI_RESID, g, s);
-            if (m->save_taps) {
-                QV_HIP(hipMemcpyAsync(a.tap_glu + tap_off, a.gluf, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
-                QV_HIP(hipMemcpyAsync(a.tap_dw + tap_off, a.dwf, sizeof(float) * (size_t)M * QV_D, hipMemcpyDeviceToDevice, s));
-            }
-        } else {
-        if (!(skip & 1)) launch_layernorm(a.x, L.ln_g[2], L.ln_b[2], a.ln, M, s);
-        if (dup & 1) launch_layernorm(a.x, L.ln_g[2], L.ln_b[2], a.ln, M, s);
-        gemm(EPI_GLU, a.ln, QV_D, L.pw1_w, L.pw1_b, a.glu, 2 * QV_D, QV_D, 1.f);
-        if (!(skip & 8)) launch_dwconv1d(a.glu, L.dw_w, L.dw_b, d_l3, d_off, a.dw, T, B, s);
-        if (dup & 8) launch_dwconv1d(a.glu, L.dw_w, L.dw_b, d_l3, d_off, a.dw, T, B, s);
-        gemm(EPI_RESID, a.dw, QV_D, L.pw2_w, L.pw2_b, a.x, QV_D, QV_D, 1.f);
-        }
-        // 1/2 FFN
-        if (!(skip & 1)) launch_layernorm(a.x, L.ln_g[3], L.ln_b[3], a.ln, M, s);
-        if (dup & 1) launch_layernorm(a.x, L.ln_g[3], L.ln_b[3], a.ln, M, s);
-        gemm(EPI_F16_SWISH, a.ln, QV_D, L.ff2_w1, L.ff2_b1, a.hbuf, QV_FF, QV_FF, 1.f);
-        gemm(EPI_RESID, a.hbuf, QV_FF, L.ff2_w2, L.ff2_b2, a.x, QV_D, QV_D, 0.5f);
-        // norm_out (+ next layer's first LayerNorm)
-        if (skip & 2) { }
-        else if (l + 1 < N_LAYERS)
-            launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], m->L[l + 1].ln_g[0], m->L[l + 1].ln_b[0], a.ln, M, s);
-        else   // last layer: the f16 copy of the encoder output (CTC head operand) comes out of the same pass
-            launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], nullptr, nullptr, a.xh, M, s);
-        if (m->save_taps)
-            QV_HIP(hipMemcpyAsync(a.tap_x + (size_t)(l + 1) * M * QV_D, a.x, sizeof(float) * (size_t)M * QV_D,
-                                  hipMemcpyDeviceToDevice, s));
+        f.ffn_half(L.ff1_w1, L.ff1_b1, L.ff1_w2, L.ff1_b2);
+        f.attention_block(L, l);
+        if (m->ort) TRY(f.conv_module_ort(L, l));
+        else f.conv_module_f16(L);
+        f.layernorm(L, 3);
+        f.ffn_half(L.ff2_w1, L.ff2_b1, L.ff2_w2, L.ff2_b2);
+        TRY(f.layer_out(l));
     }
-    if (skip & 2) launch_to_half(a.x, a.xh, (size_t)M * QV_D, s);   // (timing experiments only: the pass that writes xh was skipped)
-    if (m->ort) {
-        // ConvASRDecoder is a 1x1 Conv1d in the exported graph: DynamicQuantizeLinear on the encoder output, ConvInteger
-        launch_rows_minmax(a.x, M, a.row_map, mm_site(MM_HEAD), s);
-        launch_quant_rows(a.x, M, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_site(MM_HEAD), a.q8, s);
-        GemmArgs g = {};
-        g.A = (const half_t *)a.q8; g.Wi8 = m->o_head.wq; g.wsum = m->o_head.wsum; g.w_scale = m->o_head.scale; g.bias = m->head_b;
-        g.out = a.logits; g.M = M; g.N = HEAD_N; g.K = QV_D / 2; g.lda = QV_D / 2; g.ldw = QV_D / 2; g.ldo = HEAD_N; g.alpha = 1.f;
-        g.row_map = a.row_map; g.mm_in = mm_site(MM_HEAD);
-        launch_gemm(EPI_F32, g, s);
-    } else {
-        GemmArgs g = {};
-        g.A = a.xh; g.W = m->head_w; g.bias = m->head_b; g.out = a.logits;
-        g.M = M; g.N = HEAD_N; g.K = QV_D; g.lda = QV_D; g.ldw = QV_D; g.ldo = HEAD_N; g.alpha = 1.f;
-        launch_gemm(EPI_F32, g, s);
-    }
+    if (hook_skip() & 2) launch_to_half(a.x, a.xh, (size_t)sh.M * QV_D, s);   // (timing experiments only: the pass that writes xh was skipped)
+    f.ctc_head();
     // packed logits -> the caller's dense [B][t_max_out][1025] log-prob tensor (valid frames only)
-    launch_logsoftmax(a.logits, HEAD_N, logprobs, M, a.row_map, t_max_out, s);
-    if (zero_pad_rows) launch_zero_pad_rows(logprobs, d_l3, t_max_out, t_min_pad, B, s);
+    launch_logsoftmax(a.logits, HEAD_N, logprobs, sh.M, a.row_map, sh.t_max_out, s);
+    if (sh.t_min_pad >= 0) launch_zero_pad_rows(logprobs, f.d.l3, sh.t_max_out, sh.t_min_pad, sh.B, s);
     return QV_OK;
-    };
+}
+
+// (the GEMM tile policy is host state that picks kernels: its epoch is part of the key, so a graph captured under
+// another policy is never replayed after qv_debug_gemm_tiles / QVERSE_GEMM_* changed it)
+FwdKey fwd_key(const FwdShape &sh, const float *audio, float *logprobs, const half_t *posp, int64_t n_max, int att_variant) {
+    return {audio, logprobs, posp, n_max,
+            {sh.B, sh.M, sh.T, sh.t3min, sh.tm_max, sh.t1m, sh.t2m, sh.t_max_out, sh.t_min_pad, att_variant, qv_kernel_variant(QV_KV_LOGMEL),
+             qv_kernel_variant(QV_KV_ORT_SUB) | (qv_kernel_variant(QV_KV_SUB_RUN) << 4) | (qv_kernel_variant(QV_KV_SUB35) << 8), qv_gemm_policy_epoch()}};
+}
+
+}  // namespace
+
+int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, const int64_t *len_host, int batch, int64_t n_max,
+                     float *logprobs, int t_max_out, int32_t *t_out_host, hipStream_t s, bool zero_pad_rows, bool may_graph) {
+    QvActs &a = m->ctx_acts[k];
+    FwdShape sh;
+    TRY(fwd_shape(eng, m, a, len_host, batch, n_max, t_max_out, zero_pad_rows, t_out_host, s, &sh));
+    const half_t *posp = nullptr;
+    TRY(get_pos(eng, m, sh.T, s, &posp));
+    const int att_variant = qv_attention_variant();   // read once per forward: all 17 layers use the same kernel
+    auto plain = [&] { return launch_all(eng, m, a, sh, audio, n_max, logprobs, posp, att_variant, s); };
     // One graph launch for the whole forward when this context has already run a batch of exactly this shape from
     // these buffers (a serving loop over a fixed staging buffer with equal-length or equally-ragged batches): the
     // ~300 launches replay as one submission -- +1.2 % at four batches in flight, +2 % at two (profiles/r05_q_*).
-    // A context captures the first QV_FWD_GRAPHS shapes it sees straight away (a serving loop is at full speed from its
-    // second batch); once those slots are taken, a new shape is captured only when it comes back within the context's
-    // last QV_FWD_GRAPHS uncaptured forwards (a loop over a few staging buffers, the three passes of the 30 s path) and
-    // the oldest graph makes room -- a stream of ever-changing ragged batches pays for QV_FWD_GRAPHS captures per
-    // context over its lifetime and no more.  Anything else -- caller streams
-    // (single-context engines), debug taps, stage / GEMM profiling -- takes the plain launches.  QVERSE_FWD_GRAPH=0
-    // (or qv_debug_kernel_variant(QV_KV_FWD_GRAPH, 0)) turns it off.
+    // Which shapes a context captures and which graph makes room: FwdGraphCache (qv_graph_policy.h).  Anything else --
+    // caller streams (single-context engines), debug taps, stage / GEMM profiling -- takes the plain launches.
+    // QVERSE_FWD_GRAPH=0 (or qv_debug_kernel_variant(QV_KV_FWD_GRAPH, 0)) turns it off.
+    FwdGraphs &graphs = a.fwd_graphs;
+    FwdGraphs::Plan plan = {graphs.PLAIN, -1, false};
     if (qv_kernel_variant(QV_KV_FWD_GRAPH) == 1 && may_graph && !m->save_taps && !eng->profile_stages && !qv_gemm_prof_on()) {
-        // (the GEMM tile policy is host state that picks kernels: its epoch is part of the key, so a graph captured under
-        // another policy is never replayed after qv_debug_gemm_tiles / QVERSE_GEMM_* changed it)
-        FwdKey key = {audio, logprobs, posp, n_max,
-                      {B, M, T, t3min, tm_max, t1m, t2m, t_max_out, t_min_pad, att_variant,
-                       qv_kernel_variant(QV_KV_LOGMEL), qv_kernel_variant(QV_KV_ORT_SUB) | (qv_kernel_variant(QV_KV_SUB_RUN) << 4) | (qv_kernel_variant(QV_KV_SUB35) << 8),
-                       qv_gemm_policy_epoch()}};
-        const int64_t tick = ++a.fwd_tick;
-        FwdGraph *hit = nullptr;
-        for (int i = 0; i < a.n_fwd_graph; ++i)
-            if (a.fwd_graph[i].key == key) hit = &a.fwd_graph[i];
-        bool seen = false;
-        for (const FwdKey &o : a.fwd_seen) seen = seen || o == key;
-        if (!hit && !seen) {
-            a.fwd_seen[a.fwd_seen_at] = key;
-            a.fwd_seen_at = (a.fwd_seen_at + 1) % QV_FWD_GRAPHS;
-        }
-        // a full context replaces its LEAST RECENTLY USED graph, and at most once per 2 * QV_FWD_GRAPHS forwards: a loop
-        // over more recurring shapes than slots must not pay a capture + instantiate + stream synchronise per cycle
-        // (it keeps replaying the shapes it holds and runs the others as plain launches)
-        const bool full = a.n_fwd_graph >= QV_FWD_GRAPHS;
-        const bool may_capture = !a.fwd_disabled && (full ? (seen && tick - a.fwd_last_capture >= 2 * QV_FWD_GRAPHS) : true);
-        bool ran_plain = false;
-        if (!hit && may_capture) {
-            hipGraph_t graph = nullptr;
+        const FwdKey key = fwd_key(sh, audio, logprobs, posp, n_max, att_variant);
+        plan = graphs.next(key);
+        if (plan.act == graphs.CAPTURE) {
             hipGraphExec_t exec = nullptr;
-            // Any failure of the capture machinery (a capture-unsafe call of the host on this thread invalidated it, a node type
-            // the runtime cannot instantiate) must not fail the batch: the plain launches would have succeeded.  The sticky
-            // error is cleared, graphs are switched off for this context and the launches are issued for real.
-            hipError_t e0 = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-            int rc = 0;
-            hipError_t e1 = hipSuccess, e2 = hipSuccess;
-            if (e0 == hipSuccess) {
-                rc = launch_all();
-                e1 = hipStreamEndCapture(s, &graph);
-                if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                if (e1 == hipSuccess) e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || !exec) {
-                (void)hipGetLastError();
-                a.fwd_disabled = true;
-                m->fwd_capture_failures++;
-                TRY(launch_all());
-                ran_plain = true;
-            } else {
-                int slot = a.n_fwd_graph;
-                if (!full) a.n_fwd_graph++;
-                else {
-                    slot = 0;
-                    for (int i = 1; i < QV_FWD_GRAPHS; ++i)
-                        if (a.fwd_graph[i].last_use < a.fwd_graph[slot].last_use) slot = i;
-                    QV_HIP(hipStreamSynchronize(s));   // its last replay may still be queued on this stream (rate-limited above)
-                    (void)hipGraphExecDestroy(a.fwd_graph[slot].exec);
+            bool captured = false;
+            TRY(qv_capture_graph(s, plain, &exec, &captured));
+            if (captured) {
+                if (plan.evict) {
+                    QV_HIP(hipStreamSynchronize(s));   // its last replay may still be queued on this stream (rate-limited by the policy)
+                    (void)hipGraphExecDestroy(graphs.slot[plan.slot].handle);
                 }
-                a.fwd_graph[slot] = {key, exec, tick};
-                a.fwd_last_capture = tick;
+                graphs.store(plan.slot, key, exec);
                 m->fwd_captures++;
-                hit = &a.fwd_graph[slot];
+                plan.act = graphs.REPLAY;
+            } else {   // graphs are switched off for this context and the launches are issued for real
+                graphs.disabled = true;
+                m->fwd_capture_failures++;
+                plan.act = graphs.PLAIN;
             }
         }
-        if (hit) { QV_HIP(hipGraphLaunch(hit->exec, s)); hit->last_use = tick; m->fwd_replays++; }
-        else if (!ran_plain) TRY(launch_all());
-    } else {
-        TRY(launch_all());
     }
+    if (plan.act == graphs.REPLAY) { QV_HIP(hipGraphLaunch(graphs.slot[plan.slot].handle, s)); m->fwd_replays++; }
+    else TRY(plain());
     QV_HIP(hipGetLastError());
-    a.last_batch = B; a.last_tmax = T; a.last_tm_max = tm_max; a.last_rows = M; a.last_t2m = t2m;
+    a.last = sh;
     return QV_OK;
 }
 
@@ -1103,29 +1117,26 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
 // them does not disturb the stream.
 static int replay_args(qv_engine *eng, QvModel *m, int k, int which, GemmArgs &g, int &epi) {
     QvActs &a = m->ctx_acts[k];
-    int M = a.last_rows;
+    const int M = a.last.M, T = a.last.T;
     if (M <= 0) { qv_set_error(eng, "replay needs a previous forward"); return QV_ERR_ARG; }
     const LayerW &L = m->L[0];
-    g = GemmArgs{};
-    g.M = M; g.out2 = a.vt; g.t_max = a.last_tmax; g.t_pad = (a.last_tmax + 31) / 32 * 32; g.alpha = 1.f;
-    g.row_map = a.row_map; g.in_flight = m->n_ctx;
-    const WMat *W;
+    auto args = [&](const half_t *A, int K, const WMat &W, const float *bias, void *out, int N, int ldo, float alpha) {
+        return layer_gemm_args(m, a, M, T, A, K, W, bias, out, N, ldo, alpha);
+    };
     switch (which) {
-        case 0: epi = EPI_F16_SWISH; g.A = a.ln; W = &L.ff1_w1; g.bias = L.ff1_b1; g.out = a.hbuf; g.N = QV_FF; g.K = QV_D; g.ldo = QV_FF; break;
-        case 1: epi = EPI_RESID; g.A = a.hbuf; W = &L.ff1_w2; g.bias = L.ff1_b2; g.out = a.x; g.N = QV_D; g.K = QV_FF; g.ldo = QV_D; g.alpha = 0.f; break;
-        case 2: epi = EPI_QKV; g.A = a.ln; W = &L.qkv_w; g.bias = L.qkv_b; g.out = a.qk; g.N = 3 * QV_D; g.K = QV_D; g.ldo = 2 * QV_D; break;
-        case 3: epi = EPI_RESID; g.A = a.att; W = &L.out_w; g.bias = L.out_b; g.out = a.x; g.N = QV_D; g.K = QV_D; g.ldo = QV_D; g.alpha = 0.f; break;
-        case 4: epi = EPI_GLU; g.A = a.ln; W = &L.pw1_w; g.bias = L.pw1_b; g.out = a.glu; g.N = 2 * QV_D; g.K = QV_D; g.ldo = QV_D; break;
+        case 0: epi = EPI_F16_SWISH; g = args(a.ln, QV_D, L.ff1_w1, L.ff1_b1, a.hbuf, QV_FF, QV_FF, 1.f); break;
+        case 1: epi = EPI_RESID; g = args(a.hbuf, QV_FF, L.ff1_w2, L.ff1_b2, a.x, QV_D, QV_D, 0.f); break;
+        case 2: epi = EPI_QKV; g = args(a.ln, QV_D, L.qkv_w, L.qkv_b, a.qk, 3 * QV_D, 2 * QV_D, 1.f); break;
+        case 3: epi = EPI_RESID; g = args(a.att, QV_D, L.out_w, L.out_b, a.x, QV_D, QV_D, 0.f); break;
+        case 4: epi = EPI_GLU; g = args(a.ln, QV_D, L.pw1_w, L.pw1_b, a.glu, 2 * QV_D, QV_D, 1.f); break;
         default: return QV_ERR_ARG;
     }
-    g.W = W->w; g.Wq = W->q; g.wscale = W->sc; g.W8 = W->q8; g.w8scale = W->sc8;
-    g.lda = g.K; g.ldw = g.K;
     if (which == 4 && m->ort) {
         // QV_PREC_ORT_MIXED: this GEMM is the A8W8 one (s8 operands left in q8 by the last forward; K counts byte pairs);
         // the range it folds into the GLU site is the one the last forward already left there
-        g.A = (const half_t *)a.q8; g.W = nullptr; g.Wi8 = L.o_pw1.wq; g.wsum = L.o_pw1.wsum; g.w_scale = L.o_pw1.scale;
-        g.out = a.gluf; g.K = QV_D / 2; g.lda = g.ldw = QV_D / 2;
-        g.mm_in = a.mm + (size_t)MM_LAYER(0) * m->max_batch * QV_MM_STRIDE; g.mm_out = (uint32_t *)g.mm_in + (size_t)m->max_batch * QV_MM_STRIDE;
+        const GemmArgs f16 = g;
+        g = ort_pw1_args(m, a, M, 0);
+        g.out2 = f16.out2; g.t_max = f16.t_max; g.t_pad = f16.t_pad; g.in_flight = f16.in_flight;
     }
     return QV_OK;
 }
@@ -1183,52 +1194,65 @@ void qv_model_frame_counts(int64_t n_samples, int32_t out[4]) {
     for (int i = 1; i < 4; ++i) out[i] = stage_len(out[i - 1]);
 }
 
+// qv_debug_forward_tap's `what` codes (include/qverse.h)
+enum Tap {
+    TAP_MEL_NORM = 0, TAP_SUB_OUT = 1, TAP_LAYER_OUT = 2, TAP_ORT_LNC = 3, TAP_ORT_GLU = 4, TAP_ORT_DW = 5, TAP_ORT_C1 = 6,
+    TAP_ORT_C1P = 7, TAP_ORT_C2 = 8, TAP_ORT_C2P = 9, TAP_LOGMEL = 10, TAP_C1 = 11, TAP_C2 = 12
+};
+
+// the [M][512] tensors a forward saved under QVERSE_DEBUG_TAPS=1: where tap `what` of `layer` starts (nullptr: no such tap)
+static const float *saved_tap(qv_engine *eng, const QvModel *m, const QvActs &a, int what, int layer) {
+    const size_t n = (size_t)a.last.M * QV_D;
+    switch (what) {
+        case TAP_SUB_OUT: return a.tap_x;
+        case TAP_LAYER_OUT: return layer >= -1 && layer < N_LAYERS ? a.tap_x + (size_t)(layer + 1) * n : nullptr;
+        case TAP_ORT_LNC: case TAP_ORT_GLU: case TAP_ORT_DW:
+            if (!m->ort || layer < 0 || layer >= N_LAYERS) { qv_set_error(eng, "taps 3..5 exist under QV_PREC_ORT_MIXED only"); return nullptr; }
+            return (what == TAP_ORT_LNC ? a.tap_lnc : what == TAP_ORT_GLU ? a.tap_glu : a.tap_dw) + (size_t)layer * n;
+        default: return nullptr;
+    }
+}
+
 int qv_model_tap(qv_engine *eng, QvModel *m, int k, int what, int layer, float *out, hipStream_t s) {
     QvActs &a = m->ctx_acts[k];
-    size_t M = (size_t)a.last_rows;
-    if (what == 0) {
-        // normalised features are never materialised on the fast path (conv0 normalises on load)
-        launch_melapply(a.feats, a.lens_dev, a.last_tm_max, a.mel_stats, out, a.last_batch, s);
-    } else if (what == 10) {   // the log-mel features as k_logmel left them, [B][tm_max][80]
-        QV_HIP(hipMemcpyAsync(out, a.feats, sizeof(float) * (size_t)a.last_batch * a.last_tm_max * QV_NMEL, hipMemcpyDeviceToDevice, s));
-    } else if (what == 11) {   // conv.2 output of the f16 path (k_sub01 / the two-kernel path) as it sits in HBM
+    const size_t B = (size_t)a.last.B, n_c1 = B * a.last.t2m * 20 * QV_SUBC, n_c2 = B * a.last.T * 10 * QV_SUBC;
+    const LenRows d = dev_lens(m, a);
+    switch (what) {
+    case TAP_MEL_NORM:   // normalised features are never materialised on the fast path (conv0 normalises on load)
+        launch_melapply(a.feats, d.n_samples, a.last.tm_max, a.mel_stats, out, a.last.B, s);
+        break;
+    case TAP_LOGMEL:     // the log-mel features as k_logmel left them, [B][tm_max][80]
+        QV_HIP(hipMemcpyAsync(out, a.feats, sizeof(float) * B * a.last.tm_max * QV_NMEL, hipMemcpyDeviceToDevice, s));
+        break;
+    case TAP_C1:         // conv.2 output of the f16 path (k_sub01 / the two-kernel path) as it sits in HBM
         if (m->ort || !a.c1) { qv_set_error(eng, "tap 11 exists on the f16 front end only"); return QV_ERR_ARG; }
-        launch_to_float(a.c1, out, (size_t)a.last_batch * a.last_t2m * 20 * QV_SUBC, s);
-    } else if (what == 12) {   // conv.5 output of the f16 path in the dense view [B][t3_max][10][256], frames >= len3[b] zero
+        launch_to_float(a.c1, out, n_c1, s);
+        break;
+    case TAP_C2:         // conv.5 output of the f16 path in the dense view [B][t3_max][10][256], frames >= len3[b] zero
         if (m->ort) { qv_set_error(eng, "tap 12 exists on the f16 front end only"); return QV_ERR_ARG; }
-        const int32_t *d_l3 = a.lens_dev + 4 * m->max_batch, *d_off = a.lens_dev + 5 * m->max_batch;
-        const size_t n = (size_t)a.last_batch * a.last_tmax * 10 * QV_SUBC;
-        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * n, s));
+        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * n_c2, s));
         // (k_sub35 leaves c2 packed; the four-launch path leaves it dense: row_off = nullptr)
-        launch_unpack_rows_f32(a.c2, a.last_tmax, 10 * QV_SUBC, d_l3, a.sub35 ? d_off : nullptr, out, a.last_batch, s);
-    } else if (what >= 6 && what <= 9) {
+        launch_unpack_rows_f32(a.c2, a.last.T, 10 * QV_SUBC, d.l3, a.sub35 ? d.row_off : nullptr, out, a.last.B, s);
+        break;
+    case TAP_ORT_C1: case TAP_ORT_C1P: case TAP_ORT_C2: case TAP_ORT_C2P:
         // QV_PREC_ORT_MIXED: the dense subsampling tensors in front of / behind the quantisers, as they sit in HBM
         if (!m->ort) { qv_set_error(eng, "taps 6..9 exist under QV_PREC_ORT_MIXED only"); return QV_ERR_ARG; }
-        const size_t B = (size_t)a.last_batch;
-        if (what == 6) QV_HIP(hipMemcpyAsync(out, a.c1f, sizeof(float) * B * a.last_t2m * 20 * QV_SUBC, hipMemcpyDeviceToDevice, s));
-        if (what == 7) QV_HIP(hipMemcpyAsync(out, a.c1pf, sizeof(float) * B * a.last_t2m * 20 * QV_SUBC, hipMemcpyDeviceToDevice, s));
-        if (what == 8) QV_HIP(hipMemcpyAsync(out, a.c2f, sizeof(float) * B * a.last_tmax * 10 * QV_SUBC, hipMemcpyDeviceToDevice, s));
-        if (what == 9) launch_to_float(a.c2p, out, B * a.last_tmax * 10 * QV_SUBC, s);
-    } else {
+        if (what == TAP_ORT_C2P) launch_to_float(a.c2p, out, n_c2, s);
+        else QV_HIP(hipMemcpyAsync(out, what == TAP_ORT_C1 ? a.c1f : what == TAP_ORT_C1P ? a.c1pf : a.c2f,
+                                   sizeof(float) * (what == TAP_ORT_C2 ? n_c2 : n_c1), hipMemcpyDeviceToDevice, s));
+        break;
+    default: {           // the saved [M][512] tensors (and unknown codes)
         if (!m->save_taps) { qv_set_error(eng, "set QVERSE_DEBUG_TAPS=1 before creating the engine"); return QV_ERR_ARG; }
-        const float *src = nullptr;
-        if (what == 1 || what == 2) {
-            int idx = what == 1 ? 0 : layer + 1;
-            if (idx < 0 || idx > N_LAYERS) return QV_ERR_ARG;
-            src = a.tap_x + (size_t)idx * M * QV_D;
-        } else if (what >= 3 && what <= 5) {
-            if (!m->ort || layer < 0 || layer >= N_LAYERS) { qv_set_error(eng, "taps 3..5 exist under QV_PREC_ORT_MIXED only"); return QV_ERR_ARG; }
-            src = (what == 3 ? a.tap_lnc : what == 4 ? a.tap_glu : a.tap_dw) + (size_t)layer * M * QV_D;
-        } else return QV_ERR_ARG;
+        const float *src = saved_tap(eng, m, a, what, layer);
+        if (!src) return QV_ERR_ARG;
         // unpack to the dense [B][t_max][512] view the tests read (padding frames zero)
-        const int T = a.last_tmax;
-        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * (size_t)a.last_batch * T * QV_D, s));
-        for (int b = 0; b < a.last_batch; ++b) {
-            const int32_t *off = a.lens_host + (size_t)a.lens_last * (m->max_batch * 6 + 1) + 5 * m->max_batch;   // this context's last forward
-            int r0 = off[b], n = off[b + 1] - r0;
-            QV_HIP(hipMemcpyAsync(out + (size_t)b * T * QV_D, src + (size_t)r0 * QV_D,
-                                  sizeof(float) * (size_t)n * QV_D, hipMemcpyDeviceToDevice, s));
-        }
+        const int T = a.last.T;
+        const int32_t *off = host_lens(m, a, a.lens_last).row_off;   // this context's last forward
+        QV_HIP(hipMemsetAsync(out, 0, sizeof(float) * B * T * QV_D, s));
+        for (int b = 0; b < a.last.B; ++b)
+            QV_HIP(hipMemcpyAsync(out + (size_t)b * T * QV_D, src + (size_t)off[b] * QV_D,
+                                  sizeof(float) * (size_t)(off[b + 1] - off[b]) * QV_D, hipMemcpyDeviceToDevice, s));
+    }
     }
     QV_HIP(hipStreamSynchronize(s));
     return QV_OK;

@@ -16,6 +16,7 @@
 // so scores are bit-identical to the reference's Python floats.
 
 #include "qv_common.h"
+#include "qv_graph.h"
 #include "qv_kernels.h"   // qv_kernel_variant
 
 #include <math.h>
@@ -2211,45 +2212,28 @@ int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int3
     // (4.26 vs 4.13 ms per step, within box noise) -- kernel boundaries cost the same inside a graph, and the
     // host's ~3.5 us per launch is not what limits the step.
     static const bool use_graph = [] { const char *e = getenv("QVERSE_POST_GRAPH"); return e && atoi(e) != 0; }();
+    QvCtx::PostGraph *hit = nullptr;
     if (use_graph && !c.post_graph_off && eng->n_ctx > 1 && stream == c.stream && lp == c.logprobs_ws && !eng->profile_stages) {
         // (the kernel variants that pick launches inside the chain are part of the key: a graph captured under another span pass
         // or CTC wave program must not be replayed after qv_debug_kernel_variant changed it)
         const int variants = qv_kernel_variant(QV_KV_SPANS) | (qv_kernel_variant(QV_KV_CTC) << 4) | ((QV_MAXW > 16) << 8);
-        QvCtx::PostGraph *hit = nullptr;
         for (int i = 0; i < c.n_post_graph; ++i)
             if (c.post_graph[i].lp == lp && c.post_graph[i].batch == batch && c.post_graph[i].t_max == t_max && c.post_graph[i].variants == variants)
                 hit = &c.post_graph[i];
-        bool ran_plain = false;
         if (!hit && c.n_post_graph < 4) {
-            hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
+            bool captured = false;
             // as for the forward graph: a failure of the capture machinery is not a failure of the batch
-            hipError_t e0 = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal), e1 = hipSuccess, e2 = hipSuccess;
-            if (e0 == hipSuccess) {
-                int rc = launch_chain();
-                e1 = hipStreamEndCapture(stream, &graph);
-                if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                if (e1 == hipSuccess) e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-                if (graph) (void)hipGraphDestroy(graph);
-            }
-            if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess || !exec) {
-                (void)hipGetLastError();
-                c.post_graph_off = true;
-                int rc = launch_chain();
-                if (rc) return rc;
-                ran_plain = true;
-            } else {
+            int rc = qv_capture_graph(stream, launch_chain, &exec, &captured);
+            if (rc) return rc;
+            if (captured) {
                 c.post_graph[c.n_post_graph] = {lp, batch, t_max, variants, exec};
                 hit = &c.post_graph[c.n_post_graph++];
-            }
+            } else c.post_graph_off = true;
         }
-        if (hit) {
-            QV_HIP(hipGraphLaunch(hit->exec, stream));
-        } else if (!ran_plain) {
-            int rc = launch_chain();
-            if (rc) return rc;
-        }
-    } else {
+    }
+    if (hit) QV_HIP(hipGraphLaunch(hit->exec, stream));
+    else {
         int rc = launch_chain();
         if (rc) return rc;
     }
