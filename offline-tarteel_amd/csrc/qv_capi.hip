@@ -3,6 +3,7 @@
 #include "qv_common.h"
 #include "qv_kernels.h"
 #include "qv_layers.h"
+#include "qv_tables_host.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -183,27 +184,6 @@ extern "C" int32_t qv_frames_for_samples(int64_t n) {
     return (int32_t)t;
 }
 
-// ------------------------------------------------------------------ blob reader --------
-struct Blob {
-    std::vector<uint8_t> data;
-    const void *get(const char *name, size_t *nbytes = nullptr) const {
-        uint32_t n;
-        memcpy(&n, data.data() + 8, 4);
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint8_t *e = data.data() + 16 + 40 * (size_t)i;
-            if (strncmp((const char *)e, name, 24) == 0) {
-                uint64_t off, nb;
-                memcpy(&off, e + 24, 8);
-                memcpy(&nb, e + 32, 8);
-                if (off + nb > data.size()) return nullptr;
-                if (nbytes) *nbytes = (size_t)nb;
-                return data.data() + off;
-            }
-        }
-        return nullptr;
-    }
-};
-
 template <typename T>
 static int upload(qv_engine *eng, const T *host, size_t count, const T **dev) {
     void *p = nullptr;
@@ -226,190 +206,38 @@ static int dalloc(qv_engine *eng, size_t count, T **dev) {
 
 #define QV_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
+// the tables file: read it, let qv_tables_host.h check it and build the host arrays, upload each under its own name
 static int load_tables(qv_engine *eng, const char *path) {
-    Blob blob;
+    std::vector<uint8_t> file;
     {
         std::ifstream f(path, std::ios::binary | std::ios::ate);
         if (!f) { qv_set_error(eng, std::string("cannot open tables file: ") + (path ? path : "(null)")); return QV_ERR_IO; }
-        std::streamsize sz = f.tellg();
+        const std::streamsize sz = f.tellg();
         f.seekg(0);
-        blob.data.resize((size_t)sz);
-        if (!f.read((char *)blob.data.data(), sz) || sz < 16 || memcmp(blob.data.data(), "QVTB0001", 8)) {
-            qv_set_error(eng, "tables file malformed (bad magic)");
-            return QV_ERR_IO;
-        }
+        file.resize(sz > 0 ? (size_t)sz : 0);
+        if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();   // refused below: bad magic
     }
-    const char *need[] = {"meta", "surah", "ayah", "surah_start", "surah_len", "clean_off", "clean", "alt_off", "alt",
-                          "nobsm_off", "nobsm", "clean_nw", "alt_nw", "nobsm_nw", "tok_off", "tok", "piece_off",
-                          "piece_codes", "tri_keys", "tri_idf", "vtri_off", "vtri"};
-    for (const char *n : need)
-        if (!blob.get(n)) { qv_set_error(eng, std::string("tables file lacks section ") + n); return QV_ERR_IO; }
-    const int32_t *meta = (const int32_t *)blob.get("meta");
-    int N = meta[0], NS = meta[1], K = meta[2], NT = meta[6];
-    if (K > QV_NSYM || meta[3] != QV_MAX_SPAN || meta[4] != QV_VOCAB) {
-        qv_set_error(eng, "tables file incompatible (alphabet/max_span/vocab)");
-        return QV_ERR_IO;
-    }
+    HostTables h;
+    std::string err;
+    if (int rc = qv_build_host_tables(file.data(), file.size(), h, err)) { qv_set_error(eng, err); return rc; }
     QvTables &t = eng->tab;
-    t.n_verses = N; t.n_surah = NS; t.n_tri = NT;
-    const uint8_t *surah = (const uint8_t *)blob.get("surah");
-    const uint16_t *ayah = (const uint16_t *)blob.get("ayah");
-    eng->h_surah.assign(surah, surah + N);
-    eng->h_ayah.assign(ayah, ayah + N);
-    QV_TRY(upload(eng, surah, N, &t.surah));
-    QV_TRY(upload(eng, ayah, N, &t.ayah));
-    QV_TRY(upload(eng, (const int32_t *)blob.get("surah_start"), NS + 1, &t.surah_start));
-    QV_TRY(upload(eng, (const int32_t *)blob.get("surah_len"), NS, &t.surah_len));
-    const uint32_t *coff = (const uint32_t *)blob.get("clean_off"), *aoff = (const uint32_t *)blob.get("alt_off"),
-                   *noff = (const uint32_t *)blob.get("nobsm_off");
-    const uint8_t *ctxt = (const uint8_t *)blob.get("clean"), *atxt = (const uint8_t *)blob.get("alt"),
-                  *ntxt = (const uint8_t *)blob.get("nobsm");
-    // padded clean array: verse texts separated by one space
-    std::vector<uint8_t> cpad;
-    std::vector<uint32_t> cpo(N), apo(N);
-    std::vector<uint16_t> clen(N), alen(N), nlen(N);
-    std::vector<int32_t> nrank(N, -1);
-    int n_nobsm = 0;
-    for (int v = 0; v < N; ++v) {
-        cpo[v] = (uint32_t)cpad.size();
-        clen[v] = (uint16_t)(coff[v + 1] - coff[v]);
-        cpad.insert(cpad.end(), ctxt + coff[v], ctxt + coff[v + 1]);
-        cpad.push_back(0);
-        apo[v] = aoff[v];
-        alen[v] = (uint16_t)(aoff[v + 1] - aoff[v]);
-        nlen[v] = (uint16_t)(noff[v + 1] - noff[v]);
-        if (nlen[v]) {
-            nrank[v] = n_nobsm++;
-            // the no-bismillah text must be a suffix of the clean text (it is clean[len(BSM):].strip())
-            if (nlen[v] > clen[v] || memcmp(ntxt + noff[v], ctxt + coff[v + 1] - nlen[v], nlen[v]) != 0) {
-                qv_set_error(eng, "tables: no_bsm text is not a suffix of text_clean");
-                return QV_ERR_IO;
-            }
-        }
-    }
-    {
-        std::vector<uint8_t> c8;
-        std::vector<uint32_t> o8(N + 1);
-        for (int v = 0; v < N; ++v) {
-            o8[v] = (uint32_t)c8.size();
-            c8.push_back(0);
-            c8.insert(c8.end(), ctxt + coff[v], ctxt + coff[v + 1]);
-            while (c8.size() & 7) c8.push_back(0xFF);
-        }
-        o8[N] = (uint32_t)c8.size();
-        c8.resize(c8.size() + 64, 0xFF);
-        QV_TRY(upload(eng, c8.data(), c8.size(), &t.clean8));
-        QV_TRY(upload(eng, o8.data(), (size_t)N + 1, &t.clean8_off));
-    }
-    cpad.resize(cpad.size() + 64, 0);
-    QV_TRY(upload(eng, cpad.data(), cpad.size(), &t.clean));
-    QV_TRY(upload(eng, cpo.data(), (size_t)N, &t.clean_off));
-    QV_TRY(upload(eng, clen.data(), (size_t)N, &t.clean_len));
-    QV_TRY(upload(eng, nlen.data(), (size_t)N, &t.nobsm_len));
-    {
-        std::vector<uint8_t> apad(atxt, atxt + aoff[N]);
-        apad.resize(apad.size() + 64, 0);  // texts are read 8 bytes at a time
-        QV_TRY(upload(eng, apad.data(), apad.size(), &t.alt));
-    }
-    QV_TRY(upload(eng, apo.data(), (size_t)N, &t.alt_off));
-    QV_TRY(upload(eng, alen.data(), (size_t)N, &t.alt_len));
-    QV_TRY(upload(eng, (const uint16_t *)blob.get("clean_nw"), (size_t)N, &t.nw[0]));
-    QV_TRY(upload(eng, (const uint16_t *)blob.get("alt_nw"), (size_t)N, &t.nw[1]));
-    QV_TRY(upload(eng, (const uint16_t *)blob.get("nobsm_nw"), (size_t)N, &t.nw[2]));
-    QV_TRY(upload(eng, nrank.data(), (size_t)N, &t.nobsm_rank));
-    {   // word ends of the clean texts (the verse tracker's prefix scores)
-        std::vector<uint32_t> wo(N + 1, 0);
-        std::vector<uint16_t> we;
-        const uint16_t *cnw = (const uint16_t *)blob.get("clean_nw");
-        for (int v = 0; v < N; ++v) {
-            wo[v] = (uint32_t)we.size();
-            for (int i = 0; i < clen[v]; ++i)
-                if (ctxt[coff[v] + i] == 0) we.push_back((uint16_t)i);
-            we.push_back(clen[v]);
-            if ((int)(we.size() - wo[v]) != cnw[v]) { qv_set_error(eng, "tables: clean_nw disagrees with the text"); return QV_ERR_IO; }
-        }
-        wo[N] = (uint32_t)we.size();
-        QV_TRY(upload(eng, wo.data(), wo.size(), &t.wend_off));
-        QV_TRY(upload(eng, we.data(), we.size(), &t.wend));
-        std::vector<int32_t> order(N);
-        for (int v = 0; v < N; ++v) order[v] = v;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return clen[a] > clen[b]; });
-        QV_TRY(upload(eng, order.data(), order.size(), &t.len_order));
-    }
-    // per-text match masks
-    t.n_text = 2 * N + n_nobsm;
-    std::vector<uint32_t> pmo(t.n_text);
-    std::vector<uint64_t> pmv;
-    auto add_text = [&](int tid, const uint8_t *s, int len) {
-        int stride = qv_tmpl_w((len + 63) / 64);
-        pmo[tid] = (uint32_t)pmv.size();
-        pmv.resize(pmv.size() + (size_t)QV_NSYM * stride, 0ull);
-        uint64_t *base = pmv.data() + pmo[tid];
-        for (int i = 0; i < len; ++i)
-            if (s[i] < QV_NSYM) base[(size_t)s[i] * stride + (i >> 6)] |= 1ull << (i & 63);
-    };
-    for (int v = 0; v < N; ++v) {
-        add_text(v, ctxt + coff[v], clen[v]);
-    }
-    for (int v = 0; v < N; ++v) add_text(N + v, atxt + aoff[v], alen[v]);
-    for (int v = 0; v < N; ++v)
-        if (nlen[v]) add_text(2 * N + nrank[v], ntxt + noff[v], nlen[v]);
-    pmv.resize(pmv.size() + 16, 0ull);
-    QV_TRY(upload(eng, pmv.data(), pmv.size(), &t.pmv));
-    QV_TRY(upload(eng, pmo.data(), pmo.size(), &t.pmv_off));
-    QV_TRY(upload(eng, (const uint32_t *)blob.get("tri_keys"), (size_t)NT, &t.tri_keys));
-    QV_TRY(upload(eng, (const double *)blob.get("tri_idf"), (size_t)NT, &t.tri_idf));
-    const uint32_t *vto = (const uint32_t *)blob.get("vtri_off");
-    QV_TRY(upload(eng, vto, (size_t)N + 1, &t.vtri_off));
-    const uint16_t *vt = (const uint16_t *)blob.get("vtri");
-    QV_TRY(upload(eng, vt, (size_t)vto[N], &t.vtri));
-    {   // inverted trigram index, split in four verse-range slices (one per wave of k_trigram)
-        std::vector<uint32_t> start(NT + 1, 0);
-        for (uint32_t p = 0; p < vto[N]; ++p) {
-            if (vt[p] >= NT) { qv_set_error(eng, "tables: trigram id out of range"); return QV_ERR_IO; }
-            ++start[vt[p] + 1];
-        }
-        for (int i = 0; i < NT; ++i) start[i + 1] += start[i];
-        std::vector<uint16_t> post(vto[N] + 64, 0);
-        std::vector<uint32_t> fill(start.begin(), start.end() - 1), slice((size_t)NT * 5);
-        for (int i = 0; i < NT; ++i) slice[(size_t)i * 5] = start[i];
-        int w = 0;
-        for (int v = 0; v < N; ++v) {
-            while (w < 3 && v >= (int)((long long)(w + 1) * N / 4)) {   // verse v opens slice w + 1
-                ++w;
-                for (int i = 0; i < NT; ++i) slice[(size_t)i * 5 + w] = fill[i];
-            }
-            for (uint32_t p = vto[v]; p < vto[v + 1]; ++p) post[fill[vt[p]]++] = (uint16_t)v;
-        }
-        for (++w; w <= 4; ++w)
-            for (int i = 0; i < NT; ++i) slice[(size_t)i * 5 + w] = fill[i];
-        QV_TRY(upload(eng, post.data(), post.size(), &t.tri_post));
-        std::vector<uint16_t> map((size_t)1 << 18, 0xFFFF);
-        const uint32_t *keys = (const uint32_t *)blob.get("tri_keys");
-        for (int i = 0; i < NT; ++i) {
-            if (keys[i] >= map.size() || NT >= 0xFFFF) { qv_set_error(eng, "tables: trigram key out of range"); return QV_ERR_IO; }
-            map[keys[i]] = (uint16_t)i;
-        }
-        QV_TRY(upload(eng, map.data(), map.size(), &t.tri_map));
-        QV_TRY(upload(eng, slice.data(), slice.size(), &t.tri_slice));
-    }
-    const uint32_t *to = (const uint32_t *)blob.get("tok_off");
-    QV_TRY(upload(eng, to, (size_t)N * QV_MAX_SPAN + 1, &t.tok_off));
-    QV_TRY(upload(eng, (const uint16_t *)blob.get("tok"), (size_t)to[(size_t)N * QV_MAX_SPAN], &t.tok));
-    {   // prefix flags of the token table (see QvTables::tok_pfx)
-        const uint16_t *tk = (const uint16_t *)blob.get("tok");
-        std::vector<uint8_t> pfx(N, 0);
-        for (int v = 0; v < N; ++v)
-            for (int k = 1; k < QV_MAX_SPAN; ++k) {
-                const uint32_t a0 = to[(size_t)v * QV_MAX_SPAN + k - 1], a1 = to[(size_t)v * QV_MAX_SPAN + k], b1 = to[(size_t)v * QV_MAX_SPAN + k + 1];
-                const uint32_t la = a1 - a0, lb = b1 - a1;
-                if (la > 0 && lb >= la && memcmp(tk + a0, tk + a1, sizeof(uint16_t) * la) == 0) pfx[v] |= (uint8_t)(1u << (k - 1));
-            }
-        QV_TRY(upload(eng, pfx.data(), pfx.size(), &t.tok_pfx));
-    }
-    const uint32_t *po = (const uint32_t *)blob.get("piece_off");
-    QV_TRY(upload(eng, po, (size_t)QV_VOCAB + 1, &t.piece_off));
-    QV_TRY(upload(eng, (const uint8_t *)blob.get("piece_codes"), (size_t)po[QV_VOCAB] + 16, &t.piece_codes));
+    t.n_verses = h.n_verses; t.n_surah = h.n_surah; t.n_tri = h.n_tri; t.n_text = h.n_text;
+    eng->h_surah = std::move(h.h_surah);
+    eng->h_ayah = std::move(h.h_ayah);
+#define UP(member) QV_TRY(upload(eng, h.member.data(), h.member.size(), &t.member))
+    UP(surah); UP(ayah); UP(surah_start); UP(surah_len);
+    UP(clean8); UP(clean8_off);
+    UP(clean); UP(clean_off); UP(clean_len); UP(nobsm_len);
+    UP(alt); UP(alt_off); UP(alt_len);
+    UP(nw[0]); UP(nw[1]); UP(nw[2]);
+    UP(nobsm_rank);
+    UP(wend_off); UP(wend); UP(len_order);
+    UP(pmv); UP(pmv_off);
+    UP(tri_keys); UP(tri_idf); UP(vtri_off); UP(vtri);
+    UP(tri_post); UP(tri_map); UP(tri_slice);
+    UP(tok_off); UP(tok); UP(tok_pfx);
+    UP(piece_off); UP(piece_codes);
+#undef UP
     return QV_OK;
 }
 

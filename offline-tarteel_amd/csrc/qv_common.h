@@ -10,9 +10,8 @@
 #include <vector>
 
 #include "../../include/qverse.h"
+#include "qv_limits.h"   // QV_NSYM, QV_OTHER, QV_MAX_SPAN, QV_MAX_VW, qv_tmpl_w
 
-#define QV_NSYM 40          // alphabet codes 0..39 (0 = ' '); 63 = matches nothing
-#define QV_OTHER 63
 // The matching window is a compile-time constant of the post-logits kernels (buffer pitches, LDS arrays, the word counts the
 // LCS core is instantiated for).  qv_postlogits.hip is compiled twice: as itself with the default window, and through
 // qv_postlogits_wide.hip with QV_MAXQ = QV_MAX_TRANSCRIPT_WIDE, kernels in namespace qv_wide and launchers named qv_post_*_wide.
@@ -21,11 +20,9 @@
 #define QV_MAXQ QV_MAX_TRANSCRIPT
 #endif
 #define QV_MAXW (QV_MAXQ / 64)
-#define QV_MAX_SPAN 6
 #define QV_CAND_CAP 2048
 #define QV_RUNNER_CAP 128
 #define QV_RAW_CAP 4096     // raw (pre-collapse) transcript code units per utterance
-#define QV_MAX_VW 11        // ceil(684 / 64): words of the longest verse text
 
 #define QV_HIP(expr)                                                                         \
     do {                                                                                     \
@@ -35,11 +32,6 @@
             return QV_ERR_HIP;                                                               \
         }                                                                                    \
     } while (0)
-
-// word counts the LCS core is instantiated for; verse match-mask rows are padded to these
-__host__ __device__ inline int qv_tmpl_w(int w) {
-    return w <= 1 ? 1 : w <= 2 ? 2 : w <= 3 ? 3 : w <= 4 ? 4 : w <= 6 ? 6 : w <= 8 ? 8 : w <= 11 ? 11 : 16;
-}
 
 struct qv_engine;
 void qv_set_error(qv_engine *e, const std::string &msg);

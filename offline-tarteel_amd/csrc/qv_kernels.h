@@ -16,18 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qv_limits.h"   // QV_D, QV_H, QV_DK, QV_FF, QV_NMEL, QV_SUBC
+
 typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define QV_D 512
-#define QV_H 8
-#define QV_DK 64
-#define QV_FF 2048
-#define QV_NMEL 80
-#define QV_SUBC 256
 
 enum {
     EPI_F16 = 0,        // out f16 = acc + bias

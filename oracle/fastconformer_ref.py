@@ -109,7 +109,7 @@ def _splitmix64(x: np.ndarray) -> np.ndarray:
 
 def _noise(n: int, key: int) -> np.ndarray:
     """zero-mean, unit-variance-ish (Irwin-Hall of 4 bytes), exact in float32; the HIP library's
-    own generator (csrc/qv_model.hip::init_random) is the same integer recipe."""
+    own generator (csrc/qv_weights_host.h::init_random) is the same integer recipe."""
     with np.errstate(over="ignore"):
         h = _splitmix64(np.arange(n, dtype=np.uint64) + np.uint64(key))
     s = ((h & np.uint64(0xFF)) + ((h >> np.uint64(8)) & np.uint64(0xFF)) + ((h >> np.uint64(16)) & np.uint64(0xFF))

@@ -594,3 +594,28 @@ def test_fuzz_batched_path_against_the_oracle(oracle):
         assert withheld <= n_cases // 50
     finally:
         eng.close()
+
+
+def test_engine_refuses_malformed_tables_before_any_upload(tmp_path):
+    """A tables file that breaks what the kernels assume -- a short section, a token id past the vocabulary, a verse longer
+    than k_frag's mask slice -- is refused by qv_create as QV_ERR_IO (FileNotFoundError, as for a missing file) with the
+    section's name: csrc/qv_tables_host.h validates on the host before the first upload, no kernel sees the file."""
+    from offline_tarteel_amd.engine import Engine
+    from tables_patch import MALFORMED, malformed
+
+    for case in ("ayah_halved", "tok_id_is_vocab", "verse_0_over_the_text_limit"):
+        with pytest.raises(FileNotFoundError, match=MALFORMED[case][1]) as ei:
+            Engine(device=0, with_model=False, max_batch=1, tables_path=malformed(case, tmp_path / (case + ".bin")))
+        print(case, "->", ei.value)
+
+
+def test_engine_on_the_committed_tables_matches_a_known_verse():
+    from offline_tarteel_amd.engine import Engine
+
+    eng = Engine(device=0, with_model=False, max_batch=1)
+    try:
+        r = eng.match_verse("قل هو الله احد")
+        assert (r["surah"], r["ayah"], r["ayah_end"], r["verse"], r["n_words"]) == (112, 1, None, 6221, 8), r   # n_words: of text_clean
+        assert r["score"] == 1.0, r
+    finally:
+        eng.close()

@@ -8,7 +8,7 @@
 File format ("QVWT0001"): u32 tensor count, then per tensor {u32 name_len, name, u32 numel,
 float32 data}; names are the NeMo state-dict keys of the CTC branch (encoder.*,
 ctc_decoder.decoder_layers.0.*), the same the engine's seeded init uses
-(csrc/qv_model.hip::weight_shapes, read through the library's host-only qv_weight_spec).  A ``.nemo`` file is a tar archive holding
+(csrc/qv_weights_host.h::weight_shapes, read through the library's host-only qv_weight_spec).  A ``.nemo`` file is a tar archive holding
 ``model_weights.ckpt`` (a torch state dict), readable without NeMo.
 
     python tools/convert_weights.py --onnx fastconformer_full_mixed.onnx --list          # what the file holds
