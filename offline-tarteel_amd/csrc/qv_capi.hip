@@ -242,7 +242,7 @@ static int load_tables(qv_engine *eng, const char *path) {
 }
 
 // workspace, staging buffers, stream and events of execution context k
-static int alloc_work(qv_engine *eng, int k) {
+static int alloc_work(qv_engine *eng, int k, const QvSwitches &sw) {
     QvCtx &c = eng->ctx[k];
     QvWork &w = c.work;
     int B = eng->cfg.max_batch, N = eng->tab.n_verses;
@@ -293,8 +293,7 @@ static int alloc_work(qv_engine *eng, int k) {
         // would be unrestricted).  Masked streams are BLOCKING streams: the caller must not use the legacy default
         // stream for its own work or the contexts serialise behind it.  Four 64-CU partitions with 256 x 256 tiles
         // everywhere reach the same throughput as three unpartitioned batches in flight (16.6 k vs 16.6 k utt/s).
-        static const int part = [] { const char *e = getenv("QVERSE_CU_PARTITION"); return e ? atoi(e) : 0; }();
-        if (part) {
+        if (sw[QV_SW_CU_PARTITION]) {
             uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             const int lo = 32 * k / eng->n_ctx, hi = 32 * (k + 1) / eng->n_ctx;
             for (int cu = lo; cu < hi; ++cu)
@@ -318,6 +317,7 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
         qv_set_error(nullptr, "qv_create: bad config (struct_size mismatch?)");
         return QV_ERR_ARG;
     }
+    const QvSwitches sw = qv_switches_now(/*creating=*/true);   // debug taps, unfused cross-check paths, CU partition
     qv_engine *eng = new qv_engine();
     memset(&eng->cfg, 0, sizeof eng->cfg);
     memcpy(&eng->cfg, cfg_in, (size_t)cfg_in->struct_size);
@@ -394,7 +394,7 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
     int rc = load_tables(eng, cfg->tables_path);
     if (rc) return fail(rc);
     for (int k = 0; k < eng->n_ctx; ++k) {
-        rc = alloc_work(eng, k);
+        rc = alloc_work(eng, k, sw);
         if (rc) return fail(rc);
     }
     {   // verse tracker workspace (qv_tracker_match)
@@ -406,7 +406,7 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
             return fail(rc);
     }
     if (cfg->with_model) {
-        rc = qv_model_create(eng, &eng->cfg, &eng->model);
+        rc = qv_model_create(eng, &eng->cfg, sw, &eng->model);
         if (rc) return fail(rc);
     }
     *out = eng;
@@ -1016,7 +1016,7 @@ extern "C" int qv_debug_kernel_variant(int32_t which, int32_t mode) {
 extern "C" int qv_debug_sub01_plan(int64_t n_samples, int32_t batch, int32_t *frames_out, int32_t *run_tiles_out) {
     if (n_samples < 400 || batch < 1 || !frames_out) return QV_ERR_ARG;
     qv_model_frame_counts(n_samples, frames_out);
-    if (run_tiles_out) *run_tiles_out = qv_sub01_run_tiles(batch, frames_out[2]);
+    if (run_tiles_out) *run_tiles_out = qv_sub01_run_tiles(batch, frames_out[2], qv_switches_now());
     return QV_OK;
 }
 
@@ -1024,7 +1024,7 @@ extern "C" int qv_debug_sub35_plan(int64_t n_samples, int32_t batch, int32_t *ru
     if (n_samples < 400 || batch < 1 || !run_frames_out) return QV_ERR_ARG;
     int32_t fr[4];
     qv_model_frame_counts(n_samples, fr);
-    *run_frames_out = qv_sub35_run_frames(batch, fr[3]);
+    *run_frames_out = qv_sub35_run_frames(batch, fr[3], qv_switches_now());
     return QV_OK;
 }
 

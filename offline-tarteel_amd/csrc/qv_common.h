@@ -11,6 +11,7 @@
 
 #include "../../include/qverse.h"
 #include "qv_limits.h"   // QV_NSYM, QV_OTHER, QV_MAX_SPAN, QV_MAX_VW, qv_tmpl_w
+#include "qv_switches.h"
 
 // The matching window is a compile-time constant of the post-logits kernels (buffer pitches, LDS arrays, the word counts the
 // LCS core is instantiated for).  qv_postlogits.hip is compiled twice: as itself with the default window, and through
@@ -257,7 +258,7 @@ int qv_post_match_verse_wide(qv_engine *eng, QvCtx &c, const uint8_t *codes_host
 
 // acoustic model (qv_model.hip)
 struct QvModel;
-int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out);
+int qv_model_create(qv_engine *eng, const qv_config *cfg, const QvSwitches &sw, QvModel **out);   // sw: qv_create's snapshot (taps, cross-check paths)
 void qv_model_destroy(QvModel *m);
 // `k` is the execution context whose activations (and forward graphs) the call works on
 int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio_dev, const int64_t *len_host, int batch,

@@ -11,12 +11,12 @@
 
 #include "qv_kernels.h"
 #include "qv_gemm_dequant.h"
+#include "qv_launch_plan.h"
 #include "qv_ort.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <atomic>
 #include <type_traits>
 #include <vector>
 
@@ -299,86 +299,28 @@ static void launch_gemm_inner(int epi, const GemmArgs &g, hipStream_t s, bool na
     }
 }
 
-static std::atomic<int> g_t256{-1}, g_bm{-1}, g_policy_epoch{0};
-void qv_gemm_set_t256(int mode) { g_t256.store(mode); g_policy_epoch.fetch_add(1); }
-void qv_gemm_set_bm(int mode) { g_bm.store(mode); g_policy_epoch.fetch_add(1); }
-int qv_gemm_policy_epoch() { return g_policy_epoch.load(); }
-
-namespace {
-struct GemmPlan { bool wide, narrow; int nst, bm; };
-
-// Tile and pipeline choice (measured per shape, tools/gemm_bench.hip):
-//  * 256 x 256 tiles, one block per CU (qv_gemm256.hip), when N % 256 == 0 and the grid is large enough (see below:
-//    FFN-up and QKV at B = 64 x 10 s, every N >= 512 shape at B = 256; more shapes with >= 3 batches in flight);
-//  * otherwise 128-wide tiles whenever N allows, register-staged loader waves (QVERSE_GEMM_LD=0: direct global->LDS
-//    loads with 2 stages at >= 400 tiles (two 64 KB blocks per CU), else 3, 4 when the K loop is long);
-//  * int4 weights with too few 128-wide tiles for two blocks per CU (FFN-down, out-projection: N = 512): the consumer
-//    wave of a lone block pays its dequantisation VALU in front of its own MFMAs; 64-wide tiles give every SIMD a
-//    second consumer wave to interleave with.
-GemmPlan gemm_plan(int epi, const GemmArgs &g) {
-    static const int env_nst = [] { const char *e = getenv("QVERSE_GEMM_NST"); return e ? atoi(e) : 0; }();
-    static const int env_narrow = [] { const char *e = getenv("QVERSE_GEMM_NARROW"); return e ? atoi(e) : -1; }();
-    static const int env_ld = [] { const char *e = getenv("QVERSE_GEMM_LD"); return e ? atoi(e) : 1; }();
-    static const int env_t256 = [] { const char *e = getenv("QVERSE_GEMM_T256"); return e ? atoi(e) : 1; }();
-    GemmPlan p;
-    p.narrow = g.N % 128 != 0;
-    if (g.Wq && !p.narrow && (g.N / 128) * ((g.M + 127) / 128) < 400) p.narrow = true;
-    if (env_narrow >= 0 && g.N % 128 == 0 && epi != EPI_GLU) p.narrow = env_narrow != 0;
-    const int tiles = (g.N / (p.narrow ? 64 : 128)) * ((g.M + 127) / 128);
-    p.nst = tiles >= 400 ? 2 : (g.K / 64 >= 16 ? 4 : 3);
-    if (p.narrow && p.nst > 3) p.nst = 3;
-    if (env_nst >= 2 && env_nst <= (p.narrow ? 3 : 4)) p.nst = env_nst;
-    if (env_ld == 1) p.nst = 0;
-    const int t256v = g_t256.load(), t256 = t256v >= 0 ? t256v : env_t256;
-    p.wide = false;
-    p.bm = 256;
-    if (t256 > 0 && g.N % 256 == 0 && g.bias && !(g.Wq && (g.K % 128 != 0 || g.K > 4096))) {
-        const int tiles256 = (g.N / 256) * ((g.M + 255) / 256);
-        // one batch at a time: a 256 x 256 grid must cover most of the chip (>= 160 tiles) or the 128-wide kernel's
-        // 252+ blocks finish sooner; with >= 3 batches in flight the other batches' kernels take the idle CUs and
-        // what counts is CU time per GEMM -- 128 tiles are enough, and the long-K shapes (FFN-down, the
-        // subsampling projection: 64 tiles at B = 64 x 10 s) go wide as well (+2.3 % end to end, same-box sweep)
-        static const int env_min = [] { const char *e = getenv("QVERSE_GEMM_MINTILES"); return e ? atoi(e) : 0; }();
-        static const int env_min_longk = [] { const char *e = getenv("QVERSE_GEMM_MINTILES_LONGK"); return e ? atoi(e) : 0; }();
-        const bool busy = g.in_flight >= 3;
-        // (four or more batches in flight: wide tiles wherever the shape allows, +1.4 % over the 128-tile threshold)
-        const int min_tiles = env_min > 0 ? env_min : g.in_flight >= 4 ? 1 : busy ? 128 : 160;
-        const int min_tiles_longk = env_min_longk > 0 ? env_min_longk : busy ? 1 : 160;
-        p.wide = t256 >= 2 || tiles256 >= (g.K >= 2048 ? min_tiles_longk : min_tiles);
-        // Tile height (round 6).  A 192-row tile moves 17 % more operand bytes per flop, so it is only worth its rounds:
-        // one batch at a time a GEMM takes ceil(tiles / 256 CUs) rounds of one tile time each (M = 24,064 = 64 clips x
-        // 30 s, N = 512: 188 tiles of 256 rows = one round with 68 CUs idle, 252 tiles of 192 rows = one round of 3/4 the
-        // length).  With three or more batches in flight the other batches' kernels take the idle CUs and CU time per
-        // GEMM is what counts (mode 2 applies the rule there too; tools/gemm_bench + bench.py measure both).
-        static const int env_bm = [] { const char *e = getenv("QVERSE_GEMM_BM"); return e ? atoi(e) : 1; }();
-        const int bmv = g_bm.load(), bm_mode = bmv >= 0 ? bmv : env_bm;
-        if (p.wide && bm_mode > 0) {
-            const long tiles192 = (long)(g.N / 256) * ((g.M + 191) / 192);
-            const long cost256 = ((tiles256 + 255) / 256) * 256, cost192 = ((tiles192 + 255) / 256) * 192;
-            if (bm_mode >= 3 || ((bm_mode == 2 || !busy) && cost192 * 108 <= cost256 * 100)) p.bm = 192;
-        }
-    }
-    return p;
+// what the tile policy (gemm_plan, qv_launch_plan.h) reads of a call
+static GemmShape gemm_shape(int epi, const GemmArgs &g) {
+    return {g.M, g.N, g.K, g.Wq ? GEMM_W_INT4 : g.Wi8 ? GEMM_W_A8W8 : g.W8 ? GEMM_W_INT8 : GEMM_W_F16, g.bias != nullptr, epi == EPI_GLU, g.in_flight};
 }
-}  // namespace
 
 // "k_gemm256<f16_swish>" / "k_gemm<resid,128>": the kernel launch_gemm picks for this call (measurement reports)
-const char *qv_gemm_kernel_name(int epi, const GemmArgs &g) {
+const char *qv_gemm_kernel_name(int epi, const GemmArgs &g, const QvSwitches &sw) {
     static const char *EPI[8] = {"f16", "f16_swish", "f16_relu", "glu", "resid", "f32", "qkv", "f32_relu"};
     static thread_local char buf[64];
-    const GemmPlan p = gemm_plan(epi, g);
+    const GemmPlan p = gemm_plan(gemm_shape(epi, g), sw);
     if (g.Wi8) snprintf(buf, sizeof buf, p.wide ? (p.bm == 192 ? "k_gemm256<%s,a8w8,192>" : "k_gemm256<%s,a8w8>") : "k_gemm<%s,128,a8w8>", EPI[epi]);
     else if (p.wide) snprintf(buf, sizeof buf, p.bm == 192 ? "k_gemm256<%s,192>" : "k_gemm256<%s>", EPI[epi]);
     else snprintf(buf, sizeof buf, "k_gemm<%s,%d>", EPI[epi], p.narrow ? 64 : 128);
     return buf;
 }
 
-void launch_gemm(int epi, const GemmArgs &g, hipStream_t s) {
+void launch_gemm(int epi, const GemmArgs &g, hipStream_t s, const QvSwitches &sw) {
     if (g.K % 64 != 0 || g.N % 64 != 0 || (g.Wq && g.K % 128 != 0)) {
         fprintf(stderr, "launch_gemm: unsupported shape N=%d K=%d\n", g.N, g.K);
         abort();
     }
-    const GemmPlan p = gemm_plan(epi, g);
+    const GemmPlan p = gemm_plan(gemm_shape(epi, g), sw);
     auto go = [&] {
         if (p.wide && launch_gemm256(epi, g, s, p.bm)) return;
         launch_gemm_inner(epi, g, s, p.narrow, p.nst);

@@ -16,7 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qv_limits.h"   // QV_D, QV_H, QV_DK, QV_FF, QV_NMEL, QV_SUBC
+#include "qv_limits.h"     // QV_D, QV_H, QV_DK, QV_FF, QV_NMEL, QV_SUBC
+#include "qv_switches.h"   // QvSwitches, the QV_KV_* / QV_SW_* ids, the qv_*_set setters
 
 typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -101,40 +102,15 @@ int64_t qv_pack_w4_given(const float *w, int N, int K, const float *scale, const
 // ... and for the W8A16 layout (N % 64 == 0, K % 64 == 0): scale = max|w| / 127 per row, q = round(w / scale)
 void qv_pack_w8(const float *w, int N, int K, uint8_t *q_out, float *scale_out);
 
-void launch_gemm(int epi, const GemmArgs &g, hipStream_t s);
+// every launcher that picks a kernel takes the caller's snapshot of the switches (qv_switches.h); the default is for the
+// stand-alone programs under tools/ -- inside the library a snapshot is taken once per run and passed down
+void launch_gemm(int epi, const GemmArgs &g, hipStream_t s, const QvSwitches &sw = qv_switches_now());
 // 256 x 256 tiles, one block per CU (qv_gemm256.hip): N % 256 == 0 only; false = nothing launched
 bool launch_gemm256(int epi, const GemmArgs &g, hipStream_t s, int bm = 256);   // bm: tile height, 256 or 192
-// tile policy of launch_gemm: 0 = 128-wide tiles only, 1 = 256 x 256 where the grid has >= 160 tiles (default), 2 = 256 x 256 wherever the shape allows; -1 = back to QVERSE_GEMM_T256 / the default
-void qv_gemm_set_t256(int mode);
-// tile height of the wide kernel: 0 = 256 rows always, 1 = 192 rows where that saves a round of tiles and fewer than three batches
-// are in flight (default), 2 = ... whatever is in flight, 3 = 192 rows always; -1 = back to QVERSE_GEMM_BM / the default
-void qv_gemm_set_bm(int mode);
-// changes whenever a qv_gemm_set_* switch does: part of the forward-graph key (a captured graph holds the old kernel choice)
-int qv_gemm_policy_epoch();
 // tools/gemm_bench only (QV_GEMM_Q_VARIANT builds): 256 x 256 tiles with four waves of 128 x 128 (tools/gemm256q.h)
 void qv_gemm_set_q(int mode);
 // the kernel launch_gemm picks for this call, e.g. "k_gemm256<f16_swish>" / "k_gemm<resid,128>" (thread-local buffer)
-const char *qv_gemm_kernel_name(int epi, const GemmArgs &g);
-
-// Cross-check variants of single kernels (qv_debug_kernel_variant): the override if one is set, else the environment
-// variable (read once per process), else the default.  Variants of one kernel give identical bits unless stated.
-//   QV_KV_LOGMEL  (QVERSE_LOGMEL)   2 = FFT in registers, a wave walks a run of frames (k_logmel_run, default);
-//                                   1 = FFT in registers, cross-lane strides over DPP / v_permlane*_swap, one wave per frame;
-//                                   0 = Stockham FFT through LDS (the kernel of rounds 1-4)
-//   QV_KV_ORT_SUB (QVERSE_ORT_SUB)  precision 2's conv.0: 1 = f32 matrix pipe, four channel groups per block (default); 0 = VALU
-//   QV_KV_SPANS   (QVERSE_SPANS)    match_verse's span pass: 1 = prefix-shared walk per start verse (k_spans2, default); 0 = one walk per span
-//   QV_KV_FWD_GRAPH (QVERSE_FWD_GRAPH) multi-context engines: 1 = a forward whose shape repeats on a context is replayed as one hipGraph
-//                                   launch (default); 0 = always the plain launches
-//   QV_KV_CTC     (QVERSE_CTC)      the alpha recursion of the CTC rerank: 1 = parity-specialised wave program (ctc_wave2, default);
-//                                   0 = the wave program of rounds 1-5
-//   QV_KV_SUB_RUN (QVERSE_SUB_RUN)  tiles of four c1 frames a block of k_sub01 walks: 0 = chosen from the launch shape (default);
-//                                   1 / 2 = one / two tiles; 3 = the most a block ever walks (16, mel rows refetched per channel
-//                                   group); 4 = the most with the run's mel rows resident in LDS (4)
-//   QV_KV_SUB35   (no variable)     steps of three c2 frames a block of k_sub35 walks: 0 = chosen from the launch shape (default);
-//                                   1 / 2 = one / two steps; 3 = the most a block ever walks (16)
-enum { QV_KV_LOGMEL = 0, QV_KV_ORT_SUB = 1, QV_KV_SPANS = 2, QV_KV_FWD_GRAPH = 3, QV_KV_CTC = 4, QV_KV_SUB_RUN = 5, QV_KV_SUB35 = 6, QV_KV_COUNT = 8 };
-int qv_kernel_variant(int which);
-void qv_kernel_variant_set(int which, int mode);   // mode < 0: back to the environment / default
+const char *qv_gemm_kernel_name(int epi, const GemmArgs &g, const QvSwitches &sw = qv_switches_now());
 
 // measurement hooks (bench.py roofline): per-launch HIP-event timing of the GEMMs
 void qv_gemm_prof_enable(bool on);

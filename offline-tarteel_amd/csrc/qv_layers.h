@@ -11,18 +11,20 @@ struct FrontendTab {
     const float *mel_w;     // [32][80]: tap-major (tap k of filter m at k * 80 + m), zero beyond a filter's mel_cnt
 };
 
+// A launcher that picks a kernel takes the caller's snapshot of the switches (qv_switches.h) as its last argument; the default
+// is for the stand-alone programs under tools/ -- inside the library a snapshot is taken once per run and passed down.
 size_t qv_melstats_doubles(size_t max_batch);   // size of the `stats` buffer launch_logmel needs (results + partial sums)
 void launch_logmel(const float *audio, int64_t n_max, const int32_t *n_samples, const FrontendTab &ft, float *feats,
-                   int tm_max, double *stats, int batch, hipStream_t s);
+                   int tm_max, double *stats, int batch, hipStream_t s, const QvSwitches &sw = qv_switches_now());
 void launch_melapply(const float *feats, const int32_t *n_samples, int tm_max, const double *stats, float *out, int batch,
                      hipStream_t s);
 void launch_conv0(const float *feats, int tm_max, const int32_t *len_in, const double *stats, const float *w,
                   const float *bias, half_t *out, int t1_max, int batch, hipStream_t s);
 void launch_sub01(const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0,
                   const float *b0, const int32_t *len1, const float *w1, const float *b1, half_t *out, int t2_max, int batch,
-                  hipStream_t s);
-// tiles of four c1 frames per block of k_sub01 at this launch shape (and the current QV_KV_SUB_RUN)
-int qv_sub01_run_tiles(int batch, int t2_max);
+                  hipStream_t s, const QvSwitches &sw = qv_switches_now());
+// tiles of four c1 frames per block of k_sub01 at this launch shape (sub01_run_tiles, qv_launch_plan.h)
+int qv_sub01_run_tiles(int batch, int t2_max, const QvSwitches &sw = qv_switches_now());
 void launch_dwconv2d(const half_t *in, int tin_max, int fin, const int32_t *len_in, const float *w, const float *bias,
                      half_t *out, int tout_max, int fout, int batch, hipStream_t s);
 void launch_pack_rows(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, half_t *y,
@@ -31,10 +33,10 @@ void launch_pack_rows(const half_t *x, int t_max, int row_elems, const int32_t *
 // rows (row_off[b] + t3) * 10 .. + 9 of out [10 * rows][256], and row_map[row_off[b] + t3] = b << 16 | t3
 void launch_sub35(const half_t *c1, int t2_max, const half_t *w3, const float *b3, const float *w5, const float *b5,
                   const int32_t *len2, const int32_t *len3, const int32_t *row_off, half_t *out, int32_t *row_map, int t3_max,
-                  int batch, hipStream_t s);
+                  int batch, hipStream_t s, const QvSwitches &sw = qv_switches_now());
 void qv_sub35_init();   // the kernel's LDS opt-in; call once outside stream capture
-// c2 frames a block of k_sub35 walks at this launch shape (and the current QV_KV_SUB35)
-int qv_sub35_run_frames(int batch, int t3_max);
+// c2 frames a block of k_sub35 walks at this launch shape (sub35_run_steps, qv_launch_plan.h)
+int qv_sub35_run_frames(int batch, int t3_max, const QvSwitches &sw = qv_switches_now());
 // packed f16 rows (row_off == nullptr: dense ones) -> dense f32 [B][t_max][row_elems] (valid frames only; debug taps)
 void launch_unpack_rows_f32(const half_t *x, int t_max, int row_elems, const int32_t *len, const int32_t *row_off, float *y,
                             int batch, hipStream_t s);
@@ -45,11 +47,7 @@ void launch_to_half(const float *x, half_t *y, size_t n, hipStream_t s);
 void launch_to_float(const half_t *x, float *y, size_t n, hipStream_t s);
 void launch_attention(const half_t *qk, const half_t *vt, const half_t *pos, int pos_ld, const float *bu, const float *bv,
                       const int32_t *len, const int32_t *row_off, half_t *out, int t_max, int t_min, int t_pad, int batch,
-                      hipStream_t s, int variant = -1);
-int qv_attention_variant();   // the process-wide variant as launch_attention would read it now
-// -1 environment / default (= 3); 0 two heads per block for every utterance, 1 one head per block, 2 one wave per query tile
-// (0..2 bit-identical); 3 = utterances of <= 128 frames on k_attention_short, longer ones as 0
-void qv_attention_set_variant(int mode);
+                      hipStream_t s, const QvSwitches &sw = qv_switches_now());   // sw[QV_SW_ATT]: attention_plan, qv_launch_plan.h
 void launch_dwconv1d(const half_t *x, const float *w, const float *bias, const int32_t *len, const int32_t *row_off, half_t *y,
                      int t_max, int batch, hipStream_t s);
 void launch_logsoftmax(const float *logits, int ld, float *out, int M, const int32_t *row_map, int t_out, hipStream_t s);

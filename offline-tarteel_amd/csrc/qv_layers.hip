@@ -9,8 +9,8 @@
 #include "qv_layers.h"
 #include <type_traits>
 
-#include <atomic>
 #include "qv_dev_util.h"
+#include "qv_launch_plan.h"
 #include "qv_logmel_reg.h"
 
 #include <math.h>
@@ -304,15 +304,13 @@ __global__ __launch_bounds__(256) void k_dwconv2d(const half_t *__restrict__ in,
 // lane, 16 lanes per position; lanes 0-15 / 16-31 of a half-wave read output frames tl / tl + 1, whose inputs lie
 // 80 positions = 42.5 x 256 bytes apart: the two 128-byte pieces fall on the two halves of the 64 banks.  The second halo
 // row starts at a multiple of 256 bytes for the same reason.
-#define SUB_TT 4                    // c1 frames per tile
+// (SUB_TT = 4 c1 frames per tile, SUB_MAX_RUN, SUB_RES_RUN: qv_limits.h)
 #define SUB_R1 (2 * SUB_TT + 1)     // c0 rows per tile
 #define SUB_RM (2 * SUB_R1 + 1)     // mel rows per tile
 #define SUB_MSTEP (4 * SUB_TT)       // mel rows from a tile to the next
 #define SUB_CG 64                   // channels per pass
 #define SUB_PP 68                   // halves per position of the LDS tile (136 bytes)
 #define SUB_HALO1 24576             // halves: the second halo row (49,152 bytes = 192 x 256, behind rows 0 .. 8)
-#define SUB_MAX_RUN 16              // tiles a block walks at most
-#define SUB_RES_RUN 4               // tiles a block walks at most with the run's mel rows resident in LDS
 #define SUB_MEL_PER_THREAD ((SUB_RM * QV_NMEL + 255) / 256)
 // QV_SUB01_STAMPS (tools/sub01_bench only, never the product build): wave 0 of one block in the middle of the grid adds up
 // its clock between the phase boundaries -- 0 prologue, 1 conv0 units (with a pass's weight fetch), 2 the barrier behind
@@ -562,13 +560,12 @@ __global__ void k_pack_rows(const half_t *__restrict__ x, int t_max, int row_ele
 //     by selects (the row / the tap was formed from clamped addresses), never multiplied by zero; the only branch is
 //     the store guard.
 // Every output element is formed by the same instructions on the same operands whatever the run length.
-#define S35_TC 3                                    // c2 frames per step
+// (S35_TC = 3 c2 frames per step, S35_MAX_RUN: qv_limits.h)
 #define S35_ROWS (2 * S35_TC * 20)                  // new c1 rows per step (of a 128-row GEMM tile)
 #define S35_PITCH 260                               // halves per c1p row of the LDS tile (520 bytes: 32 rows x 8-byte stores touch every bank pair once)
 #define S35_A_BYTES (128 * 256 * 2)                 // the A tile
 #define S35_HALO (S35_ROWS * S35_PITCH)             // halves: the two halo slots (20 rows each) lie behind the new rows
 #define S35_LDS (S35_A_BYTES + (S35_ROWS + 40) * S35_PITCH * 2)
-#define S35_MAX_RUN 16                              // steps a block walks at most
 static_assert(S35_ROWS <= 128 && S35_LDS <= 160 * 1024, "k_sub35: one block per CU, 160 KB of LDS");
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(512, 1) void k_sub35(const half_t *__restrict__ c1, int t2_max, const half_t *__restrict__ w3,
@@ -1035,7 +1032,7 @@ __device__ __forceinline__ void att_glds16(const void *g, void *l) {
 // 64 KB of LDS and < 256 registers: two blocks per CU, the headline batch (512 blocks) in one round.  Not the same
 // summation as the key-tiled kernels (single-pass softmax), so not bit-identical to them; WHICH kernel an utterance gets
 // depends on its own length only, never on the batch around it, so an utterance alone and in any batch has the same bits.
-#define ATT_SHORT_T 128
+// (ATT_SHORT_T = 128: qv_limits.h)
 #ifdef QV_ATT_STAMPS   // tools/att_bench.hip: shader-clock stamps of one block's waves at the phase boundaries
 __device__ long long g_att_stamp[4][8];
 #define ATT_STAMP(i) do { if (blockIdx.x == 3 && blockIdx.y == 17 && lane == 0) g_att_stamp[wave][i] = clock64(); } while (0)
@@ -1795,28 +1792,11 @@ __global__ __launch_bounds__(256) void k_zero_pad_rows(float *__restrict__ out, 
 
 // stats: [batch][80][2] results, followed by room for the [batch][MS_CHUNKS][80][2] partial sums (qv_melstats_doubles)
 size_t qv_melstats_doubles(size_t max_batch) { return max_batch * 2 * QV_NMEL * (1 + MS_CHUNKS); }
-static std::atomic<int> g_kernel_variant[QV_KV_COUNT] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
-void qv_kernel_variant_set(int which, int mode) {
-    if (which >= 0 && which < QV_KV_COUNT) g_kernel_variant[which].store(mode < 0 ? -1 : mode);
-}
-int qv_kernel_variant(int which) {
-    static const struct Env { int v[QV_KV_COUNT]; Env() {
-        const char *names[QV_KV_COUNT] = {"QVERSE_LOGMEL", "QVERSE_ORT_SUB", "QVERSE_SPANS", "QVERSE_FWD_GRAPH", "QVERSE_CTC", "QVERSE_SUB_RUN", nullptr, nullptr};
-        const int dflt[QV_KV_COUNT] = {2, 1, 1, 1, 1, 0, 0, 0};
-        for (int i = 0; i < QV_KV_COUNT; ++i) {
-            const char *e = names[i] ? getenv(names[i]) : nullptr;
-            v[i] = (e && e[0] >= '0' && e[0] <= '9') ? atoi(e) : dflt[i];
-        }
-    } } env;
-    if (which < 0 || which >= QV_KV_COUNT) return 0;
-    const int o = g_kernel_variant[which].load();
-    return o < 0 ? env.v[which] : o;
-}
 
 void launch_logmel(const float *audio, int64_t n_max, const int32_t *n_samples, const FrontendTab &ft, float *feats,
-                   int tm_max, double *stats, int batch, hipStream_t s) {
+                   int tm_max, double *stats, int batch, hipStream_t s, const QvSwitches &sw) {
     double *part = stats + (size_t)batch * 2 * QV_NMEL;
-    const int variant = qv_kernel_variant(QV_KV_LOGMEL);
+    const int variant = sw[QV_KV_LOGMEL];
     if (variant == 2)
         hipLaunchKernelGGL(lmv::k_logmel_run<QV_LOGMEL_RUN>, dim3((tm_max + 4 * QV_LOGMEL_RUN - 1) / (4 * QV_LOGMEL_RUN), batch), dim3(256), 0, s, audio, n_max, n_samples, ft, feats, tm_max);
     else if (variant == 1)
@@ -1837,31 +1817,12 @@ void launch_conv0(const float *feats, int tm_max, const int32_t *len_in, const d
     hipLaunchKernelGGL(k_conv0, dim3(1, t1_max, batch), dim3(256), 0, s, feats, tm_max, len_in, stats, w, bias, out, t1_max);
 }
 
-// Tiles per block of k_sub01, from the launch shape alone (the forward graph is keyed on the shape; no output value depends
-// on it).  A CU holds two blocks, so the chip takes 512 at a time: the cost of a run length is (rounds of 512 blocks) x
-// (2 x tiles + 1: a block's statistics, first mel rows and halo row cost about half a tile).  64 x 10 s = 64 x 63 tiles:
-// 8 runs of 8 = 512 blocks; a small batch gets short runs and fills the chip instead.  QV_KV_SUB_RUN forces 1, 2 or
-// SUB_MAX_RUN tiles, 4 forces SUB_RES_RUN (tests: the run length changes no bit).  The choice stops at SUB_RES_RUN tiles,
-// the longest run whose mel rows stay resident in LDS (k_sub01<true>); a run of 4 measured like one of 8 before that
-// (profiles/r09_a_run_length_sweep.txt), and resident rows take three of a run's four mel passes away.
-int qv_sub01_run_tiles(int batch, int t2_max) {
-    const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, forced = qv_kernel_variant(QV_KV_SUB_RUN);
-    int best = 1;
-    if (forced >= 1 && forced <= 4) best = forced == 3 ? SUB_MAX_RUN : forced == 4 ? SUB_RES_RUN : forced;
-    else {
-        long best_cost = -1;
-        for (int run = 1; run <= SUB_RES_RUN; ++run) {
-            const long blocks = (long)batch * ((n_tiles + run - 1) / run), cost = (blocks + 511) / 512 * (2 * run + 1);
-            if (best_cost < 0 || cost < best_cost) { best = run; best_cost = cost; }
-        }
-    }
-    return best < n_tiles ? best : (n_tiles > 0 ? n_tiles : 1);
-}
+int qv_sub01_run_tiles(int batch, int t2_max, const QvSwitches &sw) { return sub01_run_tiles(batch, t2_max, sw); }
 
 void launch_sub01(const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0,
                   const float *b0, const int32_t *len1, const float *w1, const float *b1, half_t *out, int t2_max, int batch,
-                  hipStream_t s) {
-    const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, run = qv_sub01_run_tiles(batch, t2_max);
+                  hipStream_t s, const QvSwitches &sw) {
+    const int n_tiles = (t2_max + SUB_TT - 1) / SUB_TT, run = sub01_run_tiles(batch, t2_max, sw);
     const dim3 grid(1, (n_tiles + run - 1) / run, batch);
     if (run <= SUB_RES_RUN)
         hipLaunchKernelGGL(k_sub01<true>, grid, dim3(256), 0, s, feats, tm_max, len_mel, stats, w0, b0, len1, w1, b1, out, t2_max, run);
@@ -1880,23 +1841,7 @@ void launch_pack_rows(const half_t *x, int t_max, int row_elems, const int32_t *
     hipLaunchKernelGGL(k_pack_rows, dim3(1, t_max, batch), dim3(256), 0, s, x, t_max, row_elems, len, row_off, y, row_map);
 }
 
-// Steps of S35_TC c2 frames per block of k_sub35, from the launch shape alone (like qv_sub01_run_tiles).  One block per CU,
-// 256 CUs: the cost of a run length is (rounds of 256 blocks) x (steps + 1: a block's weight fetch and halo frame cost
-// about a step).  64 x 10 s = 64 x 42 steps: 4 runs of 11 = 256 blocks.  QV_KV_SUB35 forces 1, 2 or S35_MAX_RUN steps.
-static int sub35_run_steps(int batch, int t3_max) {
-    const int n_steps = (t3_max + S35_TC - 1) / S35_TC, forced = qv_kernel_variant(QV_KV_SUB35);
-    int best = 1;
-    if (forced >= 1 && forced <= 3) best = forced == 3 ? S35_MAX_RUN : forced;
-    else {
-        long best_cost = -1;
-        for (int run = 1; run <= S35_MAX_RUN; ++run) {
-            const long blocks = (long)batch * ((n_steps + run - 1) / run), cost = (blocks + 255) / 256 * (run + 1);
-            if (best_cost < 0 || cost < best_cost) { best = run; best_cost = cost; }
-        }
-    }
-    return best < n_steps ? best : (n_steps > 0 ? n_steps : 1);
-}
-int qv_sub35_run_frames(int batch, int t3_max) { return sub35_run_steps(batch, t3_max) * S35_TC; }
+int qv_sub35_run_frames(int batch, int t3_max, const QvSwitches &sw) { return sub35_run_steps(batch, t3_max, sw) * S35_TC; }
 
 // 145 KB of dynamic LDS: opted into once, outside any stream capture (qv_model_create calls this; launch_sub35 for the tools)
 void qv_sub35_init() {
@@ -1909,9 +1854,9 @@ void qv_sub35_init() {
 
 void launch_sub35(const half_t *c1, int t2_max, const half_t *w3, const float *b3, const float *w5, const float *b5,
                   const int32_t *len2, const int32_t *len3, const int32_t *row_off, half_t *out, int32_t *row_map, int t3_max,
-                  int batch, hipStream_t s) {
+                  int batch, hipStream_t s, const QvSwitches &sw) {
     qv_sub35_init();
-    const int n_steps = (t3_max + S35_TC - 1) / S35_TC, run = sub35_run_steps(batch, t3_max);
+    const int n_steps = (t3_max + S35_TC - 1) / S35_TC, run = sub35_run_steps(batch, t3_max, sw);
     hipLaunchKernelGGL(k_sub35, dim3(1, (n_steps + run - 1) / run, batch), dim3(512), S35_LDS, s, c1, t2_max, w3, b3, w5, b5, len2,
                        len3, row_off, out, row_map, run);
 }
@@ -1939,62 +1884,35 @@ void launch_to_float(const half_t *x, float *y, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_to_float, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, n);
 }
 
-// Variants of the attention kernel (tests/test_gpu_forward.py): 3 = the default (an utterance of at most ATT_SHORT_T
-// frames on k_attention_short, a longer one on k_attention_ws with two heads per block), 0 = k_attention_ws with two heads per
-// block for every utterance, 1 = one head per block (3 K/V stages, 256-row ring), 2 = the one-wave-per-query-tile kernel the
-// specialised ones replaced, 4 = k_attention_x (round 6: four self-staging waves per (head, query group), two blocks per CU)
-// for every utterance, 5 = k_attention_short + k_attention_x; 0, 1, 2 and 4 are bit-identical, so are 3 and 5.
-// k_attention_x is 4-10 % faster than k_attention_ws launched back to back (tools/att_bench) and level with it inside the
-// forward with batches in flight (profiles/r06_p_attention_x_same_box.log), so it stays a variant.  The environment
-// (QVERSE_ATT_X=1 / QVERSE_ATT_HPB=1 / QVERSE_ATT_OLD=1 / QVERSE_ATT_TILED=1) is read ONCE per process; tests switch with
-// qv_debug_attention_variant() instead of setenv, which is not safe against launches from another thread.
-static std::atomic<int> g_att_variant{-1};
-void qv_attention_set_variant(int mode) { g_att_variant.store(mode); }
-static int attention_variant() {
-    static const int env = [] {
-        // QVERSE_ATT_OLD=1: one wave per query tile; QVERSE_ATT_HPB=1: one head per block; QVERSE_ATT_TILED=1: the
-        // two-heads-per-block kernel for every utterance (no k_attention_short)
-        // ... QVERSE_ATT_X=1: k_attention_x instead of k_attention_ws for the long utterances (variant 5)
-        const char *o = getenv("QVERSE_ATT_OLD"), *h = getenv("QVERSE_ATT_HPB"), *t = getenv("QVERSE_ATT_TILED"), *x = getenv("QVERSE_ATT_X");
-        return (o && o[0] == '1') ? 2 : (h && h[0] == '1') ? 1 : (t && t[0] == '1') ? 0 : (x && x[0] == '1') ? 5 : 3;
-    }();
-    const int v = g_att_variant.load();
-    return v < 0 ? env : v;
-}
-
-int qv_attention_variant() { return attention_variant(); }
-
+// which kernels a batch gets: attention_plan (qv_launch_plan.h).  The caller passes the snapshot it took ONCE (a forward:
+// qv_model.hip), so a test that flips the process-wide switch while batches of other contexts are in flight cannot change
+// kernels between the layers of one forward
 void launch_attention(const half_t *qk, const half_t *vt, const half_t *pos, int pos_ld, const float *bu, const float *bv,
                       const int32_t *len, const int32_t *row_off, half_t *out, int t_max, int t_min, int t_pad, int batch,
-                      hipStream_t s, int variant_in) {
-    // a forward pass passes the variant it read ONCE (qv_model.hip): a test that flips the process-wide switch while
-    // batches of other contexts are in flight cannot change kernels between the layers of one forward
-    const int variant = variant_in >= 0 ? variant_in : attention_variant();
-    if (variant == 2) {
+                      hipStream_t s, const QvSwitches &sw) {
+    const AttentionPlan p = attention_plan(sw[QV_SW_ATT], t_min, t_max);
+    if (p.run_short)
+        hipLaunchKernelGGL(k_attention_short, dim3(QV_H, batch), dim3(256), 0, s, qk, vt, pos, pos_ld, bu, bv, len, row_off,
+                           out, t_max, t_pad);
+    switch (p.rest) {
+    case ATT_OLD:
         hipLaunchKernelGGL(k_attention, dim3(QV_H, batch), dim3(256), 0, s, qk, vt, pos, pos_ld, bu, bv, len, row_off, out, t_max,
                            t_pad);
-        return;
-    }
-    // default (3): an utterance of at most ATT_SHORT_T frames goes to k_attention_short, a longer one to the
-    // wave-specialised kernel -- by its OWN length, so that its bits do not depend on the batch it travels in; a launch
-    // none of whose utterances qualify is skipped (t_min / t_max are the batch's shortest / longest utterance)
-    int t_short = 0;
-    if (variant == 3 || variant == 5) {      // 5: k_attention_short for short utterances, k_attention_x for the longer ones
-        t_short = ATT_SHORT_T;
-        if (t_min <= ATT_SHORT_T)
-            hipLaunchKernelGGL(k_attention_short, dim3(QV_H, batch), dim3(256), 0, s, qk, vt, pos, pos_ld, bu, bv, len, row_off,
-                               out, t_max, t_pad);
-        if (t_max <= ATT_SHORT_T) return;
-    }
-    if (variant == 4 || variant == 5)
+        break;
+    case ATT_X_192:
         hipLaunchKernelGGL((k_attention_x<192>), dim3(QV_H, (t_max + 127) / 128, batch), dim3(256), 0, s, qk, vt, pos,
-                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, t_short);
-    else if (variant == 1)
+                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, p.t_short);
+        break;
+    case ATT_WS_1_3_256:
         hipLaunchKernelGGL((k_attention_ws<1, 3, 256>), dim3(QV_H, (t_max + 127) / 128, batch), dim3(512), 0, s, qk, vt, pos,
-                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, t_short);
-    else
+                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, p.t_short);
+        break;
+    case ATT_WS_2_2_192:
         hipLaunchKernelGGL((k_attention_ws<2, 2, 192>), dim3(QV_H / 2, (t_max + 127) / 128, batch), dim3(768), 0, s, qk, vt, pos,
-                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, t_short);
+                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, p.t_short);
+        break;
+    default: break;   // ATT_NONE: every utterance was the short kernel's
+    }
 }
 
 void launch_dwconv1d(const half_t *x, const float *w, const float *bias, const int32_t *len, const int32_t *row_off, half_t *y,

@@ -21,6 +21,14 @@
 #define QV_SUBC 256
 #define QV_N_LAYERS 17
 
+// launch-shape constants the kernels (qv_layers.hip) and the host's launch plans (qv_launch_plan.h) share
+#define SUB_TT 4            // k_sub01: c1 frames per tile
+#define SUB_MAX_RUN 16      // k_sub01: tiles a block walks at most
+#define SUB_RES_RUN 4       // k_sub01: tiles a block walks at most with the run's mel rows resident in LDS
+#define S35_TC 3            // k_sub35: c2 frames per step
+#define S35_MAX_RUN 16      // k_sub35: steps a block walks at most
+#define ATT_SHORT_T 128     // longest utterance (encoder frames) k_attention_short takes
+
 #ifdef __HIPCC__
 #define QV_HOST_DEVICE __host__ __device__
 #else

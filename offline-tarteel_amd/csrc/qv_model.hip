@@ -98,10 +98,12 @@ extern "C" int qv_weight_random(uint64_t seed, int32_t index, float *out, int64_
 #define QV_FWD_GRAPHS 4
 // the forward's launches (log-mel .. log-softmax) as ONE hipGraph launch, keyed by everything a grid size or kernel
 // argument is computed from on the host; per-utterance lengths are read from lens_dev by the kernels
+// -- and by the switches its launchers pick kernels from, by value (QvSwitches::forward_part): a graph is only ever
+// replayed under the switches it was captured with
 struct FwdKey {
-    const float *audio; float *logprobs; const half_t *pos; int64_t n_max; int v[13];
+    const float *audio; float *logprobs; const half_t *pos; int64_t n_max; int v[9]; QvSwitches sw;
     bool operator==(const FwdKey &o) const {
-        return audio == o.audio && logprobs == o.logprobs && pos == o.pos && n_max == o.n_max && !memcmp(v, o.v, sizeof(v));
+        return audio == o.audio && logprobs == o.logprobs && pos == o.pos && n_max == o.n_max && !memcmp(v, o.v, sizeof(v)) && sw == o.sw;
     }
 };
 
@@ -553,6 +555,7 @@ GemmArgs gemm_args(const int8_t *q8, const OrtConv &W, const float *bias, void *
 int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const half_t **out) {
     auto it = m->pos_cache.find(t_max);
     if (it != m->pos_cache.end()) { *out = it->second; return QV_OK; }
+    const QvSwitches sw = qv_switches_now();
     int R = 2 * t_max - 1;
     std::vector<half_t> pe((size_t)R * QV_D);
     for (int r = 0; r < R; ++r) {
@@ -567,7 +570,7 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const hal
     QV_HIP(hipMalloc((void **)&d_pe, pe.size() * sizeof(half_t)));
     QV_HIP(hipMalloc((void **)&d_out, (size_t)R * N_LAYERS * QV_D * sizeof(half_t)));
     QV_HIP(hipMemcpyAsync(d_pe, pe.data(), pe.size() * sizeof(half_t), hipMemcpyHostToDevice, stream));
-    launch_gemm(EPI_F16, gemm_args(d_pe, m->pos_w, m->zero_bias, d_out, R, N_LAYERS * QV_D, QV_D, N_LAYERS * QV_D, 1.f), stream);
+    launch_gemm(EPI_F16, gemm_args(d_pe, m->pos_w, m->zero_bias, d_out, R, N_LAYERS * QV_D, QV_D, N_LAYERS * QV_D, 1.f), stream, sw);
     QV_HIP(hipStreamSynchronize(stream));
     QV_HIP(hipFree(d_pe));
     m->allocs.push_back(d_out);
@@ -626,7 +629,7 @@ int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused, bool sub3
 
 }  // namespace
 
-int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out) {
+int qv_model_create(qv_engine *eng, const qv_config *cfg, const QvSwitches &sw, QvModel **out) {
     if (cfg->precision != QV_PREC_FP16 && cfg->precision != QV_PREC_MIXED_INT4_INT8 && cfg->precision != QV_PREC_ORT_MIXED) {
         qv_set_error(eng, "unknown precision (QV_PREC_FP16, QV_PREC_MIXED_INT4_INT8 or QV_PREC_ORT_MIXED)");
         return QV_ERR_ARG;
@@ -669,15 +672,10 @@ int qv_model_create(qv_engine *eng, const qv_config *cfg, QvModel **out) {
             return QV_ERR_CAPACITY;
         }
     }
-    const char *tp = getenv("QVERSE_DEBUG_TAPS");
-    m->save_taps = tp && tp[0] == '1';
+    m->save_taps = sw[QV_SW_DEBUG_TAPS] != 0;
     m->n_ctx = eng->n_ctx;
-    const char *su = getenv("QVERSE_SUB_UNFUSED");
-    const bool sub_unfused = su && su[0] == '1';
-    const char *s35 = getenv("QVERSE_SUB35_UNFUSED");
-    const bool sub35_unfused = s35 && s35[0] == '1';
     qv_sub35_init();
-    for (int k = 0; k < m->n_ctx; ++k) TRY(alloc_context(eng, m, k, sub_unfused, sub35_unfused));
+    for (int k = 0; k < m->n_ctx; ++k) TRY(alloc_context(eng, m, k, sw[QV_SW_SUB_UNFUSED] != 0, sw[QV_SW_SUB35_UNFUSED] != 0));
     return QV_OK;
 }
 
@@ -738,8 +736,8 @@ int fwd_shape(qv_engine *eng, const QvModel *m, QvActs &a, const int64_t *len_ho
 // ... and QVERSE_DUP launches the (idempotent) kernels of a class TWICE -- results unchanged, the slowdown is
 // the class's marginal cost under the current overlap: 1 k_layernorm, 4 attention, 8 dwconv1d, 64 FFN-up/QKV/GLU GEMMs
 #ifdef QV_DEV_HOOKS
-int hook_skip() { static const int v = [] { const char *e = getenv("QVERSE_SKIP"); return e ? atoi(e) : 0; }(); return v; }
-int hook_dup() { static const int v = [] { const char *e = getenv("QVERSE_DUP"); return e ? atoi(e) : 0; }(); return v; }
+int hook_skip() { return qv_switches_env()[QV_SW_SKIP]; }
+int hook_dup() { return qv_switches_env()[QV_SW_DUP]; }
 #else   // product builds carry neither hook (python offline-tarteel_amd/build.py --dev-hooks compiles them in): hooked() is the bare call
 constexpr int hook_skip() { return 0; }
 constexpr int hook_dup() { return 0; }
@@ -768,29 +766,29 @@ GemmArgs ort_pw1_args(const QvModel *m, const QvActs &a, int M, int l) {
 // order.  A new fused kernel replaces launches inside ONE of them.
 struct Fwd {
     qv_engine *eng; const QvModel *m; const QvActs &a; const FwdShape &sh; const LenRows d; const float *audio; int64_t n_max;
-    const half_t *posp; int att_variant; hipStream_t s;
+    const half_t *posp; const QvSwitches &sw; hipStream_t s;
     uint32_t *mm(int site) const { return a.mm + (size_t)site * m->max_batch * QV_MM_STRIDE; }   // QV_PREC_ORT_MIXED: range keys of a quantiser site
 
     void sub_out() const {   // Linear(2560 -> 512) and xscaling (x * sqrt(d_model)) in one epilogue
         GemmArgs g = gemm_args(a.c2k, WMat{m->sub_out_w}, m->sub_out_b, a.x, sh.M, QV_D, 2560, QV_D, sqrtf((float)QV_D));
         g.in_flight = m->n_ctx;
-        launch_gemm(EPI_F32, g, s);
+        launch_gemm(EPI_F32, g, s, sw);
     }
     void frontend_f16() const {
-        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, sh.B, s);
+        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, sh.B, s, sw);
         if (a.c0) {
             // cross-check path: conv0 and the depthwise conv as two kernels through HBM
             launch_conv0(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, a.c0, sh.t1m, sh.B, s);
             launch_dwconv2d(a.c0, sh.t1m, 40, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, 20, sh.B, s);
         } else {
-            launch_sub01(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, sh.B, s);
+            launch_sub01(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, sh.B, s, sw);
         }
         auto pw = [&](const half_t *A, const half_t *W, const float *bias, half_t *out, int M) {   // pointwise conv + ReLU
-            launch_gemm(EPI_F16_RELU, gemm_args(A, WMat{W}, bias, out, M, QV_SUBC, QV_SUBC, QV_SUBC, 1.f), s);
+            launch_gemm(EPI_F16_RELU, gemm_args(A, WMat{W}, bias, out, M, QV_SUBC, QV_SUBC, QV_SUBC, 1.f), s, sw);
         };
         if (a.sub35) {
             // conv.3 + conv.5 in one kernel, c2 packed from here on: conv.6 runs on the valid rows only and writes c2k itself
-            launch_sub35(a.c1, sh.t2m, m->pw3_w, m->pw3_b, m->dw5_w, m->dw5_b, d.l2, d.l3, d.row_off, a.c2, a.row_map, sh.t3m, sh.B, s);
+            launch_sub35(a.c1, sh.t2m, m->pw3_w, m->pw3_b, m->dw5_w, m->dw5_b, d.l2, d.l3, d.row_off, a.c2, a.row_map, sh.t3m, sh.B, s, sw);
             pw(a.c2, m->pw6_w, m->pw6_b, a.c2k, sh.M * 10);
         } else {
             // cross-check path: four launches, c1p and the dense c2 / c2p through HBM
@@ -807,23 +805,23 @@ struct Fwd {
         const int B = sh.B, M2 = B * sh.t2m * 20, M3 = B * sh.t3m * 10;
         const RowOwner own2 = {nullptr, d.l2, sh.t2m * 20, 20}, own3 = {nullptr, d.l3, sh.t3m * 10, 10};   // dense rows
         launch_mm_init(a.mm, (size_t)MM_SITES * m->max_batch * QV_MM_STRIDE, s);
-        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, B, s);
+        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, B, s, sw);
         launch_mel_minmax(a.feats, d.n_samples, sh.tm_max, a.mel_stats, mm(MM_MEL), B, s);
         for (int pass = 0; pass < 2; ++pass)
             launch_sub01_ort(pass, a.feats, sh.tm_max, d.tm, a.mel_stats, m->o_c0.wq, m->o_c0.scale, m->c0_b, d.l1, m->o_dw2.wq,
-                             m->o_dw2.scale, m->dw2_b, d.l2, mm(MM_MEL), mm(MM_C0), mm(MM_C1), a.c1f, sh.t2m, B, s);
+                             m->o_dw2.scale, m->dw2_b, d.l2, mm(MM_MEL), mm(MM_C0), mm(MM_C1), a.c1f, sh.t2m, B, s, sw);
         launch_quant_rows(a.c1f, M2, QV_SUBC, own2, mm(MM_C1), a.q8, s);
-        launch_gemm(EPI_F32_RELU, gemm_args(a.q8, m->o_pw3, m->pw3_b, a.c1pf, M2, QV_SUBC, QV_SUBC / 2, QV_SUBC, own2, mm(MM_C1), mm(MM_C1P)), s);
+        launch_gemm(EPI_F32_RELU, gemm_args(a.q8, m->o_pw3, m->pw3_b, a.c1pf, M2, QV_SUBC, QV_SUBC / 2, QV_SUBC, own2, mm(MM_C1), mm(MM_C1P)), s, sw);
         launch_dwconv2d_ort(a.c1pf, sh.t2m, 20, d.l2, m->o_dw5.wq, m->o_dw5.scale, m->dw5_b, d.l3, mm(MM_C1P), mm(MM_C2), a.c2f, sh.t3m, 10, B, s);
         launch_quant_rows(a.c2f, M3, QV_SUBC, own3, mm(MM_C2), a.q8, s);
-        launch_gemm(EPI_F16_RELU, gemm_args(a.q8, m->o_pw6, m->pw6_b, a.c2p, M3, QV_SUBC, QV_SUBC / 2, QV_SUBC, own3, mm(MM_C2), nullptr), s);
+        launch_gemm(EPI_F16_RELU, gemm_args(a.q8, m->o_pw6, m->pw6_b, a.c2p, M3, QV_SUBC, QV_SUBC / 2, QV_SUBC, own3, mm(MM_C2), nullptr), s, sw);
         launch_pack_rows(a.c2p, sh.t3m, 10 * QV_SUBC, d.l3, d.row_off, a.c2k, a.row_map, B, s);
         sub_out();
     }
     // an encoder GEMM (hook class 64; a residual GEMM accumulates into x, so it is never doubled)
     void gemm(int epi, const half_t *A, int K, const WMat &W, const float *bias, void *out, int N, int ldo, float alpha) const {
         const GemmArgs g = layer_gemm_args(m, a, sh.M, sh.T, A, K, W, bias, out, N, ldo, alpha);
-        hooked(64, [&] { launch_gemm(epi, g, s); }, epi != EPI_RESID);
+        hooked(64, [&] { launch_gemm(epi, g, s, sw); }, epi != EPI_RESID);
     }
     void layernorm(const LayerW &L, int i, bool may_dup = true) const {   // x -> ln through the layer's i-th LayerNorm (hook class 1)
         hooked(1, [&] { launch_layernorm(a.x, L.ln_g[i], L.ln_b[i], a.ln, sh.M, s); }, may_dup);
@@ -837,7 +835,7 @@ struct Fwd {
         gemm(EPI_QKV, a.ln, QV_D, L.qkv_w, L.qkv_b, a.qk, 3 * QV_D, 2 * QV_D, 1.f);
         hooked(4, [&] {
             launch_attention(a.qk, a.vt, posp + (size_t)l * QV_D, N_LAYERS * QV_D, L.bias_u, L.bias_v, d.l3, d.row_off, a.att, sh.T, sh.t3min,
-                             sh.t_pad, sh.B, s, att_variant);
+                             sh.t_pad, sh.B, s, sw);
         });
         gemm(EPI_RESID, a.att, QV_D, L.out_w, L.out_b, a.x, QV_D, QV_D, 1.f);
     }
@@ -854,10 +852,10 @@ struct Fwd {
         const size_t n = (size_t)sh.M * QV_D, tap_off = l * n;
         launch_ln_minmax(a.x, L.ln_g[2], L.ln_b[2], sh.M, a.row_map, mm_ln, m->save_taps ? a.tap_lnc + tap_off : nullptr, s);
         launch_ln_quant(a.x, L.ln_g[2], L.ln_b[2], sh.M, a.row_map, mm_ln, a.q8, s);
-        launch_gemm(EPI_GLU, ort_pw1_args(m, a, sh.M, l), s);
+        launch_gemm(EPI_GLU, ort_pw1_args(m, a, sh.M, l), s, sw);
         launch_dwconv1d_ort(a.gluf, L.o_dw.wq, L.o_dw.scale, L.o_dw_b, L.bn_alpha, L.bn_beta, d.l3, d.row_off, mm_glu, mm_dw, a.dwf, sh.T, sh.B, s);
         launch_quant_rows(a.dwf, sh.M, QV_D, own, mm_dw, a.q8, s);
-        launch_gemm(EPI_RESID, gemm_args(a.q8, L.o_pw2, L.pw2_b, a.x, sh.M, QV_D, QV_D / 2, QV_D, own, mm_dw, nullptr), s);
+        launch_gemm(EPI_RESID, gemm_args(a.q8, L.o_pw2, L.pw2_b, a.x, sh.M, QV_D, QV_D / 2, QV_D, own, mm_dw, nullptr), s, sw);
         if (m->save_taps) {
             QV_HIP(hipMemcpyAsync(a.tap_glu + tap_off, a.gluf, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
             QV_HIP(hipMemcpyAsync(a.tap_dw + tap_off, a.dwf, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
@@ -884,17 +882,17 @@ struct Fwd {
             const RowOwner own = {a.row_map, nullptr, 0, 0};
             launch_rows_minmax(a.x, sh.M, a.row_map, mm(MM_HEAD), s);
             launch_quant_rows(a.x, sh.M, QV_D, own, mm(MM_HEAD), a.q8, s);
-            launch_gemm(EPI_F32, gemm_args(a.q8, m->o_head, m->head_b, a.logits, sh.M, HEAD_N, QV_D / 2, HEAD_N, own, mm(MM_HEAD), nullptr), s);
+            launch_gemm(EPI_F32, gemm_args(a.q8, m->o_head, m->head_b, a.logits, sh.M, HEAD_N, QV_D / 2, HEAD_N, own, mm(MM_HEAD), nullptr), s, sw);
         } else {
-            launch_gemm(EPI_F32, gemm_args(a.xh, WMat{m->head_w}, m->head_b, a.logits, sh.M, HEAD_N, QV_D, HEAD_N, 1.f), s);
+            launch_gemm(EPI_F32, gemm_args(a.xh, WMat{m->head_w}, m->head_b, a.logits, sh.M, HEAD_N, QV_D, HEAD_N, 1.f), s, sw);
         }
     }
 };
 
 // every launch of one forward, log-mel .. log-softmax
 int launch_all(qv_engine *eng, const QvModel *m, const QvActs &a, const FwdShape &sh, const float *audio, int64_t n_max, float *logprobs,
-               const half_t *posp, int att_variant, hipStream_t s) {
-    const Fwd f = {eng, m, a, sh, dev_lens(m, a), audio, n_max, posp, att_variant, s};
+               const half_t *posp, const QvSwitches &sw, hipStream_t s) {
+    const Fwd f = {eng, m, a, sh, dev_lens(m, a), audio, n_max, posp, sw, s};
     if (m->ort) f.frontend_ort();
     else if (!(hook_skip() & 32)) f.frontend_f16();
     else   // (front end skipped: the encoder still needs a row_map; on the packed path the c2 buffer stands in for c2p)
@@ -919,12 +917,10 @@ int launch_all(qv_engine *eng, const QvModel *m, const QvActs &a, const FwdShape
     return QV_OK;
 }
 
-// (the GEMM tile policy is host state that picks kernels: its epoch is part of the key, so a graph captured under
-// another policy is never replayed after qv_debug_gemm_tiles / QVERSE_GEMM_* changed it)
-FwdKey fwd_key(const FwdShape &sh, const float *audio, float *logprobs, const half_t *posp, int64_t n_max, int att_variant) {
-    return {audio, logprobs, posp, n_max,
-            {sh.B, sh.M, sh.T, sh.t3min, sh.tm_max, sh.t1m, sh.t2m, sh.t_max_out, sh.t_min_pad, att_variant, qv_kernel_variant(QV_KV_LOGMEL),
-             qv_kernel_variant(QV_KV_ORT_SUB) | (qv_kernel_variant(QV_KV_SUB_RUN) << 4) | (qv_kernel_variant(QV_KV_SUB35) << 8), qv_gemm_policy_epoch()}};
+// (`sw` is the snapshot the launches are issued with: setting a switch to another value and back hits the graph captured
+// under the first value again)
+FwdKey fwd_key(const FwdShape &sh, const float *audio, float *logprobs, const half_t *posp, int64_t n_max, const QvSwitches &sw) {
+    return {audio, logprobs, posp, n_max, {sh.B, sh.M, sh.T, sh.t3min, sh.tm_max, sh.t1m, sh.t2m, sh.t_max_out, sh.t_min_pad}, sw.forward_part()};
 }
 
 }  // namespace
@@ -936,8 +932,8 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
     TRY(fwd_shape(eng, m, a, len_host, batch, n_max, t_max_out, zero_pad_rows, t_out_host, s, &sh));
     const half_t *posp = nullptr;
     TRY(get_pos(eng, m, sh.T, s, &posp));
-    const int att_variant = qv_attention_variant();   // read once per forward: all 17 layers use the same kernel
-    auto plain = [&] { return launch_all(eng, m, a, sh, audio, n_max, logprobs, posp, att_variant, s); };
+    const QvSwitches sw = qv_switches_now();   // read once per forward: the graph key and every launch below see these values
+    auto plain = [&] { return launch_all(eng, m, a, sh, audio, n_max, logprobs, posp, sw, s); };
     // One graph launch for the whole forward when this context has already run a batch of exactly this shape from
     // these buffers (a serving loop over a fixed staging buffer with equal-length or equally-ragged batches): the
     // ~300 launches replay as one submission -- +1.2 % at four batches in flight, +2 % at two (profiles/r05_q_*).
@@ -946,8 +942,8 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
     // QVERSE_FWD_GRAPH=0 (or qv_debug_kernel_variant(QV_KV_FWD_GRAPH, 0)) turns it off.
     FwdGraphs &graphs = a.fwd_graphs;
     FwdGraphs::Plan plan = {graphs.PLAIN, -1, false};
-    if (qv_kernel_variant(QV_KV_FWD_GRAPH) == 1 && may_graph && !m->save_taps && !eng->profile_stages && !qv_gemm_prof_on()) {
-        const FwdKey key = fwd_key(sh, audio, logprobs, posp, n_max, att_variant);
+    if (sw[QV_KV_FWD_GRAPH] == 1 && may_graph && !m->save_taps && !eng->profile_stages && !qv_gemm_prof_on()) {
+        const FwdKey key = fwd_key(sh, audio, logprobs, posp, n_max, sw);
         plan = graphs.next(key);
         if (plan.act == graphs.CAPTURE) {
             hipGraphExec_t exec = nullptr;
@@ -1027,12 +1023,13 @@ int qv_model_replay_kernel(qv_engine *eng, QvModel *m, int k, int which, char *n
     int epi = 0;
     int rc = replay_args(eng, m, k, which, g, epi);
     if (rc != QV_OK) return rc;
-    snprintf(name_out, (size_t)cap, "%s", qv_gemm_kernel_name(epi, g));
+    snprintf(name_out, (size_t)cap, "%s", qv_gemm_kernel_name(epi, g, qv_switches_now()));
     return QV_OK;
 }
 
 int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int k, int which, int iters, double *avg_us, double *flops, hipStream_t s) {
     if (iters < 1) return QV_ERR_ARG;
+    const QvSwitches sw = qv_switches_now();
     GemmArgs g;
     int epi = 0;
     int rc = replay_args(eng, m, k, which, g, epi);
@@ -1040,9 +1037,9 @@ int qv_model_replay_gemm(qv_engine *eng, QvModel *m, int k, int which, int iters
     hipEvent_t e0, e1;
     QV_HIP(hipEventCreate(&e0));
     QV_HIP(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) launch_gemm(epi, g, s);
+    for (int i = 0; i < 3; ++i) launch_gemm(epi, g, s, sw);
     QV_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) launch_gemm(epi, g, s);
+    for (int i = 0; i < iters; ++i) launch_gemm(epi, g, s, sw);
     QV_HIP(hipEventRecord(e1, s));
     QV_HIP(hipEventSynchronize(e1));
     float ms = 0.f;

@@ -102,10 +102,11 @@ void launch_dwconv1d_ort(const float *x, const float *wq /*[9][512] integer-valu
 void launch_mel_minmax(const float *feats, const int32_t *n_samples, int tm_max, const double *stats, uint32_t *mm, int batch,
                        hipStream_t s);
 // conv.0 (+ReLU) and conv.2 as integer convolutions.  pass 0: range of ReLU(conv.0) only; pass 1: the whole thing
+// (sw[QV_KV_ORT_SUB] picks conv.0's kernel; the default snapshot is for the programs under tools/)
 void launch_sub01_ort(int pass, const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0q,
                       float w0_scale, const float *b0, const int32_t *len1, const float *w1q, float w1_scale, const float *b1,
                       const int32_t *len2, const uint32_t *mm_mel, uint32_t *mm_c0, uint32_t *mm_c1, float *out, int t2_max,
-                      int batch, hipStream_t s);
+                      int batch, hipStream_t s, const QvSwitches &sw = qv_switches_now());
 // conv.5: depthwise 3x3 / s2 on the quantised ReLU(conv.3) output -> f32, range folded
 void launch_dwconv2d_ort(const float *in, int tin_max, int fin, const int32_t *len_in, const float *wq, float w_scale,
                          const float *bias, const int32_t *len_out, const uint32_t *mm_in, uint32_t *mm_out, float *out,

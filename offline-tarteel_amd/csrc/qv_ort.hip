@@ -637,13 +637,11 @@ void launch_mel_minmax(const float *feats, const int32_t *n_samples, int tm_max,
     hipLaunchKernelGGL(k_mel_minmax, dim3(MMQ_CHUNKS, batch), dim3(320), 0, s, feats, n_samples, tm_max, stats, mm);
 }
 
-static int ort_sub_variant() { return qv_kernel_variant(QV_KV_ORT_SUB); }
-
 void launch_sub01_ort(int pass, const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0q,
                       float w0_scale, const float *b0, const int32_t *len1, const float *w1q, float w1_scale, const float *b1,
                       const int32_t *len2, const uint32_t *mm_mel, uint32_t *mm_c0, uint32_t *mm_c1, float *out, int t2_max,
-                      int batch, hipStream_t s) {
-    if (ort_sub_variant() == 1) {     // conv.0 on the f32 matrix pipe, four channel groups per block
+                      int batch, hipStream_t s, const QvSwitches &sw) {
+    if (sw[QV_KV_ORT_SUB] == 1) {     // conv.0 on the f32 matrix pipe, four channel groups per block
         const dim3 g1(1, (t2_max + SQ_TT - 1) / SQ_TT, batch);
         if (pass == 0)
             hipLaunchKernelGGL((k_sub01_ort_mx<0>), g1, dim3(256), 0, s, feats, tm_max, len_mel, stats, w0q, w0_scale, b0, len1, w1q,

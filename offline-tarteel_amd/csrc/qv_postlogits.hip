@@ -17,7 +17,7 @@
 
 #include "qv_common.h"
 #include "qv_graph.h"
-#include "qv_kernels.h"   // qv_kernel_variant
+#include "qv_kernels.h"
 
 #include <math.h>
 
@@ -2132,7 +2132,7 @@ __global__ void k_track_final(QvTables tab, QvTrack tw, int batch, int nblk) {
 
 // ====================================================================== host side =======
 
-static int launch_retrieval(qv_engine *eng, QvCtx &c, int batch, int force_ctc, hipStream_t stream) {
+static int launch_retrieval(qv_engine *eng, QvCtx &c, int batch, int force_ctc, hipStream_t stream, const QvSwitches &sw) {
     QvTables &tab = eng->tab;
     QvWork &wk = c.work;
     QvKnobs kn = eng->knobs;
@@ -2144,7 +2144,7 @@ static int launch_retrieval(qv_engine *eng, QvCtx &c, int batch, int force_ctc, 
     hipLaunchKernelGGL(k_frag, dim3(FRAG_GRID), dim3(256), 0, stream, tab, wk);
     size_t sm_p1 = (size_t)N * 8 + 128 * 8 + 128 * 4 + 272 * 4 + 128 * 4 + 128 * 8 + 64;
     hipLaunchKernelGGL(k_pass1_final, dim3(batch), dim3(256), sm_p1, stream, tab, wk, kn);
-    if (qv_kernel_variant(QV_KV_SPANS) == 1) hipLaunchKernelGGL(k_spans2, dim3(QV_SPAN_BLOCKS, batch), dim3(256), 0, stream, tab, wk, kn);
+    if (sw[QV_KV_SPANS] == 1) hipLaunchKernelGGL(k_spans2, dim3(QV_SPAN_BLOCKS, batch), dim3(256), 0, stream, tab, wk, kn);
     else hipLaunchKernelGGL(k_spans, dim3(QV_SPAN_BLOCKS, batch), dim3(256), 0, stream, tab, wk, kn);
     hipLaunchKernelGGL(k_base_final, dim3((batch + 63) / 64), dim3(64), 0, stream, tab, wk, kn, batch, force_ctc);
     // gate-failed utterances only (device-side list; blocks past n_fail exit at once)
@@ -2156,6 +2156,7 @@ static int launch_retrieval(qv_engine *eng, QvCtx &c, int batch, int force_ctc, 
 }
 
 int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int32_t *t_host, int batch, hipStream_t stream) {
+    const QvSwitches sw = qv_switches_now();   // read once per run: the graph key and the launches below see these values
     QvTables &tab = eng->tab;
     QvWork &wk = c.work;
     if (batch > wk.max_batch || t_max > wk.t_cap) {
@@ -2176,7 +2177,7 @@ int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int3
         c.t_pending[slot] = true;
     }
 #ifdef QV_DEV_HOOKS
-    static const int skip = [] { const char *e = getenv("QVERSE_SKIP"); return e ? atoi(e) : 0; }();   // dev-only, see qv_model.hip
+    const int skip = sw[QV_SW_SKIP];   // dev-only, see qv_model.hip
 #else
     constexpr int skip = 0;
 #endif
@@ -2184,7 +2185,7 @@ int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int3
         if (skip & 128) return QV_OK;   // (timing experiments only: no post-logits chain at all)
         hipLaunchKernelGGL(k_decode, dim3(batch), dim3(64 * DEC_WAVES), 0, stream, tab, wk, lp, t_max, c.t_dev);
         qv_stage_mark(eng, c, 2, stream);
-        int rc = launch_retrieval(eng, c, batch, 0, stream);
+        int rc = launch_retrieval(eng, c, batch, 0, stream, sw);
         if (rc) return rc;
         qv_stage_mark(eng, c, 3, stream);
         if (skip & 16) { }
@@ -2192,7 +2193,7 @@ int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int3
         // THIS batch has a clip of more than 384 frames -- not whenever the engine COULD hold one: an engine created for
         // 30 s clips used to run every 10 s batch through it (round 4: tools/sweep.py's 10 s row, 4.8 ms, against bench.py's
         // 3.8 ms for the same batch on an engine sized for it).  2L + 1 <= T <= t_max <= 384 holds for every candidate then.
-        else if (qv_kernel_variant(QV_KV_CTC) == 0) {
+        else if (sw[QV_KV_CTC] == 0) {
             if (t_max > 384) hipLaunchKernelGGL((k_ctc<true, 0>), dim3(batch, 64), dim3(256), 0, stream, tab, wk, eng->knobs, lp, t_max);
             else hipLaunchKernelGGL((k_ctc<false, 0>), dim3(batch, 64), dim3(256), 0, stream, tab, wk, eng->knobs, lp, t_max);
         }
@@ -2211,12 +2212,11 @@ int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int3
     // Opt-in (QVERSE_POST_GRAPH=1): measured on one MI355X with three batches in flight it changes nothing
     // (4.26 vs 4.13 ms per step, within box noise) -- kernel boundaries cost the same inside a graph, and the
     // host's ~3.5 us per launch is not what limits the step.
-    static const bool use_graph = [] { const char *e = getenv("QVERSE_POST_GRAPH"); return e && atoi(e) != 0; }();
     QvCtx::PostGraph *hit = nullptr;
-    if (use_graph && !c.post_graph_off && eng->n_ctx > 1 && stream == c.stream && lp == c.logprobs_ws && !eng->profile_stages) {
+    if (sw[QV_SW_POST_GRAPH] != 0 && !c.post_graph_off && eng->n_ctx > 1 && stream == c.stream && lp == c.logprobs_ws && !eng->profile_stages) {
         // (the kernel variants that pick launches inside the chain are part of the key: a graph captured under another span pass
         // or CTC wave program must not be replayed after qv_debug_kernel_variant changed it)
-        const int variants = qv_kernel_variant(QV_KV_SPANS) | (qv_kernel_variant(QV_KV_CTC) << 4) | ((QV_MAXW > 16) << 8);
+        const int variants = sw[QV_KV_SPANS] | (sw[QV_KV_CTC] << 4) | ((QV_MAXW > 16) << 8);
         for (int i = 0; i < c.n_post_graph; ++i)
             if (c.post_graph[i].lp == lp && c.post_graph[i].batch == batch && c.post_graph[i].t_max == t_max && c.post_graph[i].variants == variants)
                 hit = &c.post_graph[i];
@@ -2244,6 +2244,7 @@ int qv_post_run(qv_engine *eng, QvCtx &c, const float *lp, int t_max, const int3
 }
 
 int qv_post_debug_retrieve(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, hipStream_t stream) {
+    const QvSwitches sw = qv_switches_now();
     QvWork &wk = c.work;
     if (n > QV_MAXQ) { qv_set_error(eng, "transcript longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     int32_t zero = 0;
@@ -2251,7 +2252,7 @@ int qv_post_debug_retrieve(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, 
     hipLaunchKernelGGL(k_init_utts, dim3(1), dim3(64), 0, stream, wk, c.t_dev, 1);
     if (n > 0) QV_HIP(hipMemcpyAsync(wk.q, codes_host, n, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_prepare_codes, dim3(1), dim3(64), 0, stream, wk, n);
-    int rc = launch_retrieval(eng, c, 1, 1, stream);
+    int rc = launch_retrieval(eng, c, 1, 1, stream, sw);
     if (rc) return rc;
     QV_HIP(hipGetLastError());
     QV_HIP(hipStreamSynchronize(stream));
@@ -2261,6 +2262,7 @@ int qv_post_debug_retrieve(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, 
 #if QV_MAXW <= 16   // (does not depend on the window: only the default set defines it)
 int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg, const int32_t *lens, int n,
                       float *loss_host, hipStream_t stream) {
+    const QvSwitches sw = qv_switches_now();
     std::vector<int32_t> off(n + 1, 0);
     for (int i = 0; i < n; ++i) {
         if (lens[i] <= 0 || 2 * lens[i] + 1 > 768) { qv_set_error(eng, "target length unsupported"); return QV_ERR_ARG; }
@@ -2274,7 +2276,7 @@ int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg
     QV_HIP(hipMalloc(&d_l, sizeof(float) * std::max(1, n)));
     QV_HIP(hipMemcpyAsync(d_t, tg, sizeof(uint16_t) * off[n], hipMemcpyHostToDevice, stream));
     QV_HIP(hipMemcpyAsync(d_o, off.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice, stream));
-    if (qv_kernel_variant(QV_KV_CTC) == 0) hipLaunchKernelGGL(k_ctc_debug<0>, dim3(n), dim3(64), 0, stream, lp, T, d_t, d_o, n, d_l);
+    if (sw[QV_KV_CTC] == 0) hipLaunchKernelGGL(k_ctc_debug<0>, dim3(n), dim3(64), 0, stream, lp, T, d_t, d_o, n, d_l);
     else hipLaunchKernelGGL(k_ctc_debug<1>, dim3(n), dim3(64), 0, stream, lp, T, d_t, d_o, n, d_l);
     QV_HIP(hipMemcpyAsync(loss_host, d_l, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
     QV_HIP(hipStreamSynchronize(stream));
@@ -2315,6 +2317,7 @@ int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32
 // continuation bonuses, span pass; result in utt[0].base_* (SYNCHRONOUS).
 int qv_post_match_verse(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
                         const double *bonus_value, int max_span, hipStream_t stream) {
+    const QvSwitches sw = qv_switches_now();
     QvTables &tab = eng->tab;
     QvWork &wk = c.work;
     QvKnobs kn = eng->knobs;
@@ -2337,7 +2340,7 @@ int qv_post_match_verse(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int
     if (n_bonus > 0) hipLaunchKernelGGL(k_hint_sp, dim3(1), dim3(64), 0, stream, tab, wk, 0);
     size_t sm_p1 = (size_t)N * 8 + 128 * 8 + 128 * 4 + 272 * 4 + 128 * 4 + 128 * 8 + 64;
     hipLaunchKernelGGL(k_pass1_final, dim3(1), dim3(256), sm_p1, stream, tab, wk, kn);
-    if (qv_kernel_variant(QV_KV_SPANS) == 1) hipLaunchKernelGGL(k_spans2, dim3(QV_SPAN_BLOCKS, 1), dim3(256), 0, stream, tab, wk, kn);
+    if (sw[QV_KV_SPANS] == 1) hipLaunchKernelGGL(k_spans2, dim3(QV_SPAN_BLOCKS, 1), dim3(256), 0, stream, tab, wk, kn);
     else hipLaunchKernelGGL(k_spans, dim3(QV_SPAN_BLOCKS, 1), dim3(256), 0, stream, tab, wk, kn);
     hipLaunchKernelGGL(k_base_final, dim3(1), dim3(64), 0, stream, tab, wk, kn, 1, 0);
     QV_HIP(hipGetLastError());

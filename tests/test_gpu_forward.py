@@ -668,3 +668,47 @@ def test_forward_graph_replay_equals_the_plain_launches():
     finally:
         eng.kernel_variant(3, -1)
         eng.close()
+
+
+def test_switch_changes_between_runs_never_replay_a_stale_graph():
+    """A forward reads the kernel switches ONCE (qv_switches.h) and its graph is keyed on exactly what it read, by value: stepping
+    the GEMM tile policy 1 -> 0 -> 1 -> 2 -> 1 and k_sub01's run length -1 -> 1 -> -1 between runs of one ragged batch (0.5 s and
+    3 s on k_attention_short, 11 s on the key-tiled kernel; pad rows) captures at most one graph per distinct setting and context
+    -- going back to a setting hits the graph captured under it -- and every run equals the plain launches bit for bit: the
+    log-probs of forward() under each setting, and every result row predict_batch (the path that replays graphs) derives from
+    its log-probs -- greedy ids of every frame, scores, CTC losses."""
+    from offline_tarteel_amd.engine import Engine
+
+    lens = [8000, 48000, 176000]
+    audio = torch.from_numpy(synth_audio(3, lens[-1], seed=53))
+    for b, n in enumerate(lens):
+        audio[b, n:] = 0
+    dev = audio.cuda().contiguous()
+    eng = Engine(device=0, with_model=True, seed=SEED, max_batch=3, max_samples=lens[-1], contexts=2)
+    QV_KV_FWD_GRAPH, QV_KV_SUB_RUN = 3, 5
+    try:
+        eng.kernel_variant(QV_KV_FWD_GRAPH, 0)
+        lp_ref, t_ref = eng.forward(dev, lens)
+        res_ref = eng.predict_batch(dev, lens, want_text=True)
+        torch.cuda.synchronize()
+        assert min(t_ref) <= 128 < max(t_ref) and eng.forward_graph_stats() == {"replays": 0, "captures": 0}
+        eng.kernel_variant(QV_KV_FWD_GRAPH, 1)
+        settings, runs = set(), 0
+        for tiles in (1, 0, 1, 2, 1):
+            eng.gemm_tiles(tiles)
+            for sub_run in (-1, 1, -1):
+                eng.kernel_variant(QV_KV_SUB_RUN, sub_run)
+                settings.add((tiles, sub_run))
+                for _ in range(2):                                      # one run on each context
+                    assert eng.predict_batch(dev, lens, want_text=True) == res_ref, (tiles, sub_run)
+                    runs += 1
+                lp, t = eng.forward(dev, lens)
+                assert t == t_ref and torch.equal(lp, lp_ref), (tiles, sub_run)
+        st = eng.forward_graph_stats()
+        assert eng.lib.qv_debug_forward_graph_failures(eng.h) == 0
+        assert 0 < st["captures"] <= 2 * len(settings) and st["replays"] > 0, (st, runs)
+    finally:
+        eng.gemm_tiles(-1)
+        eng.kernel_variant(QV_KV_SUB_RUN, -1)
+        eng.kernel_variant(QV_KV_FWD_GRAPH, -1)
+        eng.close()

@@ -618,7 +618,7 @@ void launch_mel_minmax(const float *feats, const int32_t *n_samples, int tm_max,
 void launch_sub01_ort(int pass, const float *feats, int tm_max, const int32_t *len_mel, const double *stats, const float *w0q,
                       float w0_scale, const float *b0, const int32_t *len1, const float *w1q, float w1_scale, const float *b1,
                       const int32_t *len2, const uint32_t *mm_mel, uint32_t *mm_c0, uint32_t *mm_c1, float *out, int t2_max,
-                      int batch, hipStream_t s) {
+                      int batch, hipStream_t s, const QvSwitches &) {   // (qv_ort.h's signature; this version has one kernel)
     const dim3 grid(1, (t2_max + SQ_TT - 1) / SQ_TT, batch);   // (all four channel groups in one block)
     if (pass == 0)
         hipLaunchKernelGGL((k_sub01_ort<0>), grid, dim3(256), 0, s, feats, tm_max, len_mel, stats, w0q, w0_scale, b0, len1, w1q,
