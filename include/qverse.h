@@ -396,6 +396,60 @@ int qv_transcribe_batch(qv_engine *e, const float *audio_dev, const int64_t *len
                         float *logp_host, int16_t *first_host, int16_t *last_host,
                         int32_t pitch, void *stream);
 
+/* ---- recordings of any length ---------------------------------------------------------------------
+ * qv_create refuses max_samples above 61 s; a longer recording is transcribed through WINDOWS the engine accepts.  All
+ * quantities below are encoder frames of 1280 samples: qv_frames_for_samples(n) = n / 1280 + 1, so local frame j of a window
+ * that starts at sample 1280 * a is global frame a + j, with no remainder at the recording's end.
+ *   Kw   window_samples / 1280.  window_samples: a positive multiple of 1280, at most the engine's max_samples; 0 = the
+ *        largest such multiple.
+ *   M    margin_frames >= 0: frames not kept at a cut edge; -1 = min(50, Kw / 4) (4 s where it fits).
+ *   H    Kw - 2 M >= 1, else QV_ERR_ARG.        T = n / 1280 + 1.
+ *   one window if n <= window_samples; otherwise nw = the smallest integer with 1280 * ((nw - 1) * H + Kw) >= n.
+ *   window w starts at sample 1280 * w * H, is min(1280 * Kw, n - start) samples long and zero padded behind; the forward
+ *        is given that length (a last window of fewer than 400 samples -- M = 0 only -- as 400, the forward's minimum).
+ *   window w OWNS the global frames [lo_w, hi_w): lo_0 = 0, else lo_w = w * H + M; hi_(nw-1) = T, else hi_w = (w + 1) * H + M.
+ *        The ranges tile [0, T).  Frames a window does not own are never read after the forward.
+ * The owned frames' argmax ids and maxima form ONE sequence of T frames, which is collapsed by qv_transcribe's rule, seams
+ * included: runs, tokens, logp, n_blank_frames, min_token_logprob and the two float64 averages are defined above, on the
+ * global sequence; first / last are global frames (int32).  So the result equals, bit for bit, "qv_forward on every window,
+ * keep the owned frames, qv_transcribe's rule on the stitched sequence"; for n <= window_samples it equals qv_transcribe_batch
+ * / qv_transcribe field for field.  How close it comes to ONE forward over the whole recording depends on the weights and
+ * on M and is not measured.
+ * Output rows are `pitch` entries apart, pitch >= the largest T (else QV_ERR_ARG), padded like qv_transcribe's; logp_host,
+ * first_host and last_host may each be NULL.  rows above max_batch or T above QV_LONG_MAX_FRAMES: QV_ERR_CAPACITY, before
+ * anything is launched or written.  The long workspace (per recording fid, m, one record of 48 + 16 * T bytes, a pinned
+ * mirror; with a model the [max_batch, window_samples] batch) is allocated or grown by the first call that needs it and freed
+ * by qv_destroy. */
+#define QV_LONG_MAX_FRAMES 262144
+typedef struct {
+    int32_t n_tokens, t_frames, n_blank_frames, flags, n_windows, reserved;
+    float   min_token_logprob, reserved_f;
+    double  avg_logprob, frame_avg_logprob;
+} qv_long_info;
+
+/* the plan alone: host only, no GPU, no engine.  QV_ERR_ARG for bad window / margin values, QV_ERR_CAPACITY above
+ * QV_LONG_MAX_FRAMES.  Output pointers may be NULL. */
+int qv_long_plan(int64_t n_samples, int32_t max_samples, int32_t window_samples, int32_t margin_frames,
+                 int32_t *n_windows, int32_t *t_total, int32_t *kw, int32_t *m);
+/* audio_dev: f32[rows, audio_pitch], lengths_host[r] <= audio_pitch samples each (rows <= max_batch).  The windows of all
+ * recordings, in recording-then-window order, go through the forward in rounds of max_batch (plain launches into the current
+ * context's log-prob workspace).  Waits for batches in flight and forgets the workspace's earlier batch exactly as
+ * qv_transcribe_batch does.  SYNCHRONOUS.  An engine without a model: QV_ERR_NO_MODEL; a recording under 400 samples:
+ * QV_ERR_CAPACITY like the forward. */
+int qv_transcribe_long(qv_engine *e, const float *audio_dev, int64_t audio_pitch, const int64_t *lengths_host, int32_t rows,
+                       int32_t window_samples, int32_t margin_frames,
+                       qv_long_info *info_host, int32_t *ids_host,
+                       float *logp_host, int32_t *first_host, int32_t *last_host,
+                       int32_t pitch, void *stream);
+/* the same behind the forward: logprobs_dev f32[n_windows_total, t_max, 1025] holds the windows' log-probs in the flattened
+ * order, t_max >= Kw + 1 (else QV_ERR_ARG); n_samples_host[rows] the recordings' lengths.  Frames a window does not own and
+ * frames past a window's length may hold anything, NaN included.  Works on an engine without a model.  SYNCHRONOUS. */
+int qv_transcribe_windows(qv_engine *e, const float *logprobs_dev, int32_t t_max, const int64_t *n_samples_host, int32_t rows,
+                          int32_t window_samples, int32_t margin_frames,
+                          qv_long_info *info_host, int32_t *ids_host,
+                          float *logp_host, int32_t *first_host, int32_t *last_host,
+                          int32_t pitch, void *stream);
+
 /* Device pointer of the packed (surah, ayah, ayah_end, float-bits(score)) i32[B,4] rows of the
  * last async call -- the payload of the per-batch RCCL all-gather. */
 const int32_t *qv_packed_results_dev(qv_engine *e);
@@ -522,6 +576,9 @@ int qv_profile_inject_logprobs(qv_engine *e, const float *logprobs_dev, int32_t 
  * returns the four durations in milliseconds; a stage that did not run reports 0. */
 int qv_profile_stages(qv_engine *e, int32_t enable);
 int qv_stage_times(qv_engine *e, int32_t ctx, float *ms4_host);
+/* ... and while enabled, qv_transcribe_long / qv_transcribe_windows bracket every launch of their own three kernels: the last
+ * call's milliseconds in k_long_gather, k_long_frames and k_long_collapse (summed over the rounds).  QV_ERR_ARG without one. */
+int qv_long_kernel_times(qv_engine *e, float *ms3_host);
 
 /* Host-only: block-128 symmetric int4 quantisation of one Linear weight w[N][K] (f32 row-major,
  * N % 64 == 0, K % 128 == 0) followed by the inverse of the device packing, i.e. the f32 matrix

@@ -3,6 +3,7 @@
 #include "qv_common.h"
 #include "qv_kernels.h"
 #include "qv_layers.h"
+#include "qv_long_plan.h"
 #include "qv_tables_host.h"
 
 #include <math.h>
@@ -419,6 +420,7 @@ extern "C" void qv_destroy(qv_engine *e) {
     (void)hipDeviceSynchronize();
     if (e->model) qv_model_destroy(e->model);
     for (void *p : e->allocs) (void)hipFree(p);
+    qv_long_free(e->long_ws);
     for (QvCtx &c : e->ctx) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
         if (c.align.out_host) (void)hipHostFree(c.align.out_host);
@@ -961,6 +963,62 @@ extern "C" int qv_transcribe_batch(qv_engine *eng, const float *audio_dev, const
     if (rc) return rc;
     return qv_transcribe_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, info_host, ids_host, logp_host, first_host, last_host,
                               pitch, (hipStream_t)stream);
+}
+
+// ---- recordings of any length (qv_long.hip, qv_long_plan.h) ---------------------------------------------------------
+extern "C" int qv_long_plan(int64_t n_samples, int32_t max_samples, int32_t window_samples, int32_t margin_frames, int32_t *n_windows,
+                            int32_t *t_total, int32_t *kw, int32_t *m) {
+    QvLongPlan p;
+    const int rc = qv_long_plan_make(n_samples, max_samples, window_samples, margin_frames, &p);
+    if (rc) return rc;   // QV_ERR_ARG, or QV_ERR_CAPACITY above QV_LONG_MAX_FRAMES
+    if (n_windows) *n_windows = p.n_windows;
+    if (t_total) *t_total = p.t_total;
+    if (kw) *kw = p.kw;
+    if (m) *m = p.m;
+    return QV_OK;
+}
+
+extern "C" int qv_transcribe_long(qv_engine *eng, const float *audio_dev, int64_t audio_pitch, const int64_t *lengths_host, int32_t rows,
+                                  int32_t window_samples, int32_t margin_frames, qv_long_info *info_host, int32_t *ids_host,
+                                  float *logp_host, int32_t *first_host, int32_t *last_host, int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    if (!audio_dev || !lengths_host || !info_host || !ids_host || rows < 1 || audio_pitch < 1) {
+        qv_set_error(eng, "qv_transcribe_long: null argument, no rows or audio_pitch < 1");
+        return QV_ERR_ARG;
+    }
+    QV_ORDERED(eng, stream);
+    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
+    QV_TRY(quiesce_contexts(eng));
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    // (qv_long_run checks everything that can refuse the call before its first launch)
+    const int rc = qv_long_run(eng, c, audio_dev, audio_pitch, nullptr, 0, lengths_host, rows, window_samples, margin_frames, info_host,
+                               ids_host, logp_host, first_host, last_host, pitch, (hipStream_t)stream);
+    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
+    return rc;
+}
+
+extern "C" int qv_transcribe_windows(qv_engine *eng, const float *logprobs_dev, int32_t t_max, const int64_t *n_samples_host, int32_t rows,
+                                     int32_t window_samples, int32_t margin_frames, qv_long_info *info_host, int32_t *ids_host,
+                                     float *logp_host, int32_t *first_host, int32_t *last_host, int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!logprobs_dev || !n_samples_host || !info_host || !ids_host || rows < 1 || t_max < 1) {
+        qv_set_error(eng, "qv_transcribe_windows: null argument, no rows or t_max < 1");
+        return QV_ERR_ARG;
+    }
+    QV_ORDERED(eng, stream);
+    return qv_long_run(eng, eng->ctx[eng->cur_ctx], nullptr, 0, logprobs_dev, t_max, n_samples_host, rows, window_samples, margin_frames,
+                       info_host, ids_host, logp_host, first_host, last_host, pitch, (hipStream_t)stream);
+}
+
+extern "C" int qv_long_kernel_times(qv_engine *eng, float *ms3_host) {
+    QV_SERIALISE(eng);
+    if (!eng || !ms3_host) return QV_ERR_ARG;
+    if (!eng->profile_stages || !eng->long_ws.dev) { qv_set_error(eng, "qv_long_kernel_times: no profiled long call (qv_profile_stages first)"); return QV_ERR_ARG; }
+    memcpy(ms3_host, eng->long_ws.kernel_ms, sizeof(float) * 3);
+    return QV_OK;
 }
 
 extern "C" int qv_debug_forward_tap(qv_engine *eng, int32_t what, int32_t layer, float *out_dev, void *stream) {

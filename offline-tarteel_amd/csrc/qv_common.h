@@ -234,6 +234,22 @@ int qv_transcribe_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t 
                        qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host, int16_t *last_host,
                        int pitch, hipStream_t stream);
 
+// recordings of any length (qv_long.hip; the cutting rule: qv_long_plan.h).  One workspace per engine, allocated or grown by
+// the first call that needs it and freed by qv_destroy: `dev` holds the plan tables (tab_bytes, rec_bytes), the records
+// (out_bytes), then fid (fid_bytes) and m; `host` mirrors tables and records in pinned memory; `batch` is the
+// [max_batch, window_samples] batch the windows of a round are gathered into (engines with a model).
+struct QvLongWs {
+    unsigned char *dev, *host;
+    float *batch;
+    size_t dev_cap, host_cap, batch_cap;   // bytes, bytes, floats
+    size_t tab_bytes, rec_bytes, out_bytes, fid_bytes;
+    float kernel_ms[3];   // qv_profile_stages: the last call's time in k_long_gather, k_long_frames, k_long_collapse
+};
+void qv_long_free(QvLongWs &w);
+int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitch, const float *lp_in, int t_max_in,
+                const int64_t *n_host, int rows, int window_samples, int margin_frames, qv_long_info *info_host, int32_t *ids_host,
+                float *logp_host, int32_t *first_host, int32_t *last_host, int pitch, hipStream_t stream);
+
 // post-logits launchers (qv_postlogits.hip); `c` is the execution context whose workspace and staging slots the call uses
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,
@@ -348,6 +364,7 @@ struct qv_engine {
     unsigned char *resample_tab = nullptr;   // ring of row tables for qv_upfirdn_batch / qv_mixdown_batch
     unsigned resample_at = 0;
     QvTrack track;
+    QvLongWs long_ws = {};
     bool profile_stages;
     // measurement hook (qv_profile_inject_logprobs): caller-owned log-probs the post-logits stages of
     // qv_predict_batch_async() read INSTEAD of the forward's own output (the forward still runs in full)

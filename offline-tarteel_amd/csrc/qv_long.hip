@@ -1,0 +1,422 @@
+// qv_long.hip -- transcription with confidence of recordings longer than the engine's capacity (include/qverse.h:
+// qv_transcribe_long, qv_transcribe_windows; the cutting rule: qv_long_plan.h).
+//
+// The recording is cut into overlapping windows the engine accepts; the existing forward runs over rounds of at most max_batch
+// windows into the context's log-prob workspace; of every window only the frames it OWNS are looked at again:
+//   k_long_gather    the windows of one round out of the caller's [R, pitch] audio into a [round, window_samples] batch,
+//                    zero-filled behind a short last window (16-byte loads and stores; HBM-bound);
+//   k_long_frames    one wave per owned frame: k_transcribe's argmax loop, instruction for instruction; fid / m go to the
+//                    frame's GLOBAL index in per-recording arrays in HBM (before the next round reuses the workspace);
+//   k_long_collapse  once per call, one workgroup per recording: runs of equal fid over [0, T), seams included, one token per
+//                    non-blank run, the sums in the header's order.  Sixteen waves take a slab each; a wave first reduces
+//                    its slab to (latest run start, running maximum, token count, blank count), then scans it again with what
+//                    the slabs before it carry in.  The run operator is associative: no bit depends on the partition.
+#include "qv_common.h"
+#include "qv_long_plan.h"
+
+#include <string.h>
+
+#include <algorithm>
+
+#define QV_TRY_RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+static_assert(QV_LONG_FRAME_CAP == QV_LONG_MAX_FRAMES, "qv_long_plan.h and qverse.h disagree");
+static_assert(sizeof(qv_long_info) == 48, "record layout");
+
+namespace {
+
+// one window of the call, in the flattened recording-then-window order (device plan table)
+struct LongWin {
+    int64_t src_off;   // first sample of the window in the caller's audio (elements)
+    int64_t dst;       // index of the window's first OWNED frame in the fid / m arrays
+    int32_t len;       // samples to copy; the rest of the row is zero
+    int32_t lp_win;    // the window's row in the log-prob tensor k_long_frames reads
+    int32_t j0;        // local index of the first owned frame
+    int32_t count;     // owned frames
+};
+static_assert(sizeof(LongWin) == 32, "plan table layout");
+
+struct LongRec { int32_t t_frames, n_windows; };
+
+#define LG_THREADS 256
+// grid: (ceil(window_samples / 4 / LG_THREADS), windows of the round).  vec: every window start is 16-byte aligned.
+__global__ __launch_bounds__(LG_THREADS) void k_long_gather(const float *__restrict__ audio, const LongWin *__restrict__ tab,
+                                                           float *__restrict__ out, int window_samples, int vec) {
+    const LongWin w = tab[blockIdx.y];
+    const int i = (blockIdx.x * LG_THREADS + threadIdx.x) * 4;
+    if (i >= window_samples) return;          // (window_samples % 4 == 0: a float4 never straddles the row's end)
+    const float *src = audio + w.src_off;
+    float4 v;
+    if (vec && i + 4 <= w.len) v = *(const float4 *)(src + i);
+    else {
+        v.x = i < w.len ? src[i] : 0.f;
+        v.y = i + 1 < w.len ? src[i + 1] : 0.f;
+        v.z = i + 2 < w.len ? src[i + 2] : 0.f;
+        v.w = i + 3 < w.len ? src[i + 3] : 0.f;
+    }
+    *(float4 *)(out + (size_t)blockIdx.y * window_samples + i) = v;
+}
+
+#define LF_WAVES 4
+// grid: (ceil(most owned frames of a window / LF_WAVES), windows).  lp: f32[*, t_max, 1025].
+__global__ __launch_bounds__(64 * LF_WAVES) void k_long_frames(const float *__restrict__ lp, int t_max, const LongWin *__restrict__ tab,
+                                                              int16_t *__restrict__ fid, float *__restrict__ m) {
+    const LongWin w = tab[blockIdx.y];
+    const int lane = threadIdx.x & 63, f = blockIdx.x * LF_WAVES + (threadIdx.x >> 6);
+    if (f >= w.count) return;
+    // the 17 loads of a row are all requested before the first comparison
+    const float *row = lp + ((size_t)w.lp_win * t_max + (w.j0 + f)) * QV_VOCAB;
+    float x[17];
+#pragma unroll
+    for (int i = 0; i < 17; ++i) x[i] = lane + 64 * i < QV_VOCAB ? row[lane + 64 * i] : -INFINITY;
+    float best = x[0];
+    int bi = lane;
+#pragma unroll
+    for (int i = 1; i < 17; ++i)
+        if (x[i] > best) { best = x[i]; bi = lane + 64 * i; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        float b2 = __shfl_xor(best, o);
+        int i2 = __shfl_xor(bi, o);
+        if (b2 > best || (b2 == best && i2 < bi)) { best = b2; bi = i2; }
+    }
+    if (lane == 0) { fid[w.dst + f] = (int16_t)bi; m[w.dst + f] = best; }
+}
+
+#define LC_WAVES 16
+
+// k_transcribe's chunk loop over the frames [base0, base1) of one recording, entered with the run that reaches into the
+// slab (c_first: its first frame, -1 = none known; c_max: its maximum so far) and the tokens started before it (n_tok).
+template <bool EMIT>
+__device__ __forceinline__ void lc_scan(const int16_t *fid, const float *m, int T, int base0, int base1, int lane, int &n_tok,
+                                        int &n_blank, int &c_first, float &c_max, int32_t *o_ids, float *o_logp, int32_t *o_first,
+                                        int32_t *o_last) {
+    for (int base = base0; base < base1; base += 64) {
+        const int t = base + lane;
+        const bool valid = t < T;
+        const int id = valid ? (int)fid[t] : -2;
+        const int prev = valid && t > 0 ? (int)fid[t - 1] : -3;
+        const int next = t + 1 < T ? (int)fid[t + 1] : -1;
+        const bool start = valid && id != prev, end = valid && id != next;
+        // inclusive segmented scan over the lanes (k_transcribe): f = the latest run start at or before this frame, mx = the
+        // FIRST maximum of m over the frames of that run seen so far
+        int f = start ? t : -1;
+        float mx = valid ? m[t] : -INFINITY;
+        bool fl = start;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int f2 = __shfl_up(f, o);
+            const float m2 = __shfl_up(mx, o);
+            const int fl2 = __shfl_up((int)fl, o);
+            if (lane >= o) {
+                f = f2 > f ? f2 : f;
+                if (!fl) mx = mx > m2 ? mx : m2;
+                fl = fl || fl2 != 0;
+            }
+        }
+        if (!fl) { f = c_first; mx = mx > c_max ? mx : c_max; }
+        const bool blank = id == QV_BLANK;
+        const unsigned long long ks = __ballot(start && !blank);
+        n_blank += __popcll(__ballot(valid && blank));
+        if (EMIT && end && !blank) {
+            const int k = n_tok + __popcll(ks & (~0ull >> (63 - lane))) - 1;   // starts at or before this lane
+            o_ids[k] = id;
+            o_first[k] = f;
+            o_last[k] = t;
+            o_logp[k] = mx;
+        }
+        n_tok += __popcll(ks);
+        c_first = __shfl(f, 63);
+        c_max = __shfl(mx, 63);
+    }
+}
+
+// the header's sum of x[0 .. n): lane l adds x[l], x[l + 64], ... ascending from +0.0, then p[l] += p[l ^ o], o = 32 .. 1.
+// The additions of a lane are one dependent chain; eight loads are requested ahead of it.
+__device__ __forceinline__ double lc_sum(const float *x, int n, int lane) {
+    double p = 0.0;
+    for (int i = lane; i < n; i += 64 * 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = i + 64 * u < n ? x[i + 64 * u] : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (i + 64 * u < n) p = __dadd_rn(p, (double)v[u]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) p = __dadd_rn(p, __shfl_xor(p, o));
+    return p;
+}
+
+// record of recording r: qv_long_info, then ids i32[P], logp f32[P], first i32[P], last i32[P]
+__global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *__restrict__ fid_all, const float *__restrict__ m_all,
+                                                                const LongRec *__restrict__ recs, unsigned char *out, int P) {
+    __shared__ int s_first[LC_WAVES], s_ntok[LC_WAVES], s_nblank[LC_WAVES];
+    __shared__ float s_max[LC_WAVES];
+    __shared__ double s_sum[2];
+    __shared__ float s_min;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const LongRec rec_in = recs[r];
+    int T = rec_in.t_frames;
+    T = T < 0 ? 0 : (T > P ? P : T);
+    const int16_t *fid = fid_all + (size_t)r * P;
+    const float *m = m_all + (size_t)r * P;
+    unsigned char *rec = out + (size_t)r * (sizeof(qv_long_info) + (size_t)P * 16);
+    int32_t *o_ids = (int32_t *)(rec + sizeof(qv_long_info));
+    float *o_logp = (float *)(o_ids + P);
+    int32_t *o_first = (int32_t *)(o_logp + P), *o_last = o_first + P;
+
+    const int chunks = (T + 63) / 64, per = (chunks + LC_WAVES - 1) / LC_WAVES;
+    const int base0 = wave * per * 64 < T ? wave * per * 64 : T, base1 = (wave + 1) * per * 64 < T ? (wave + 1) * per * 64 : T;
+    {   // pass 1: the slab on its own
+        int n_tok = 0, n_blank = 0, c_first = -1;
+        float c_max = -INFINITY;
+        lc_scan<false>(fid, m, T, base0, base1, lane, n_tok, n_blank, c_first, c_max, nullptr, nullptr, nullptr, nullptr);
+        if (lane == 0) { s_first[wave] = c_first; s_max[wave] = c_max; s_ntok[wave] = n_tok; s_nblank[wave] = n_blank; }
+    }
+    __syncthreads();
+    // pass 2: what the slabs before this one carry in, then the slab again, emitting
+    int n_tok = 0, n_blank = 0, c_first = -1;
+    float c_max = -INFINITY;
+    for (int s = 0; s < wave; ++s) {
+        n_tok += s_ntok[s];
+        if (s_first[s] >= 0) { c_first = s_first[s]; c_max = s_max[s]; }
+        else c_max = s_max[s] > c_max ? s_max[s] : c_max;      // the later slab replaces only when strictly greater
+    }
+    lc_scan<true>(fid, m, T, base0, base1, lane, n_tok, n_blank, c_first, c_max, o_ids, o_logp, o_first, o_last);
+    int tok_all = 0, blank_all = 0;
+    for (int s = 0; s < LC_WAVES; ++s) { tok_all += s_ntok[s]; blank_all += s_nblank[s]; }
+    for (int i = tok_all + tid; i < P; i += 64 * LC_WAVES) { o_ids[i] = -1; o_first[i] = -1; o_last[i] = -1; o_logp[i] = 0.f; }
+    // o_logp: written to HBM by every wave, read below by waves 1 and 2 -- released to the device's L2 before the barrier,
+    // this CU's vector cache dropped behind it
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (wave == 0) {
+        const double s = lc_sum(m, T, lane);
+        if (lane == 0) s_sum[0] = s;
+    } else if (wave == 1) {
+        const double s = lc_sum(o_logp, tok_all, lane);
+        if (lane == 0) s_sum[1] = s;
+    } else if (wave == 2) {
+        // the first minimum over the tokens (value, then index: -0.0 and +0.0 compare equal, the earlier token is reported)
+        float mn = 0.f;
+        int mi = 0x7fffffff;
+        for (int i = lane; i < tok_all; i += 64) {
+            const float v = o_logp[i];
+            if (mi == 0x7fffffff || v < mn) { mn = v; mi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v2 = __shfl_xor(mn, o);
+            const int i2 = __shfl_xor(mi, o);
+            if (i2 != 0x7fffffff && (mi == 0x7fffffff || v2 < mn || (v2 == mn && i2 < mi))) { mn = v2; mi = i2; }
+        }
+        if (lane == 0) s_min = mn;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        qv_long_info inf;
+        inf.n_tokens = tok_all;
+        inf.t_frames = T;
+        inf.n_blank_frames = blank_all;
+        inf.flags = tok_all == 0 ? QV_FLAG_EMPTY_TRANSCRIPT : 0;
+        inf.n_windows = rec_in.n_windows;
+        inf.reserved = 0;
+        inf.min_token_logprob = tok_all ? s_min : 0.f;
+        inf.reserved_f = 0.f;
+        inf.avg_logprob = tok_all ? __ddiv_rn(s_sum[1], (double)tok_all) : 0.0;
+        inf.frame_avg_logprob = T ? __ddiv_rn(s_sum[0], (double)T) : 0.0;
+        *(qv_long_info *)rec = inf;
+    }
+}
+
+size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// qv_profile_stages: HIP events around every launch of the three kernels, summed per kernel after the call's synchronisation
+struct LongTimer {
+    bool on;
+    hipStream_t s;
+    std::vector<hipEvent_t> ev[3];
+    void mark(int which) {
+        if (!on) return;
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
+        (void)hipEventRecord(e, s);
+        ev[which].push_back(e);
+    }
+    void finish(float ms[3]) {   // after the stream has been synchronised
+        for (int k = 0; k < 3; ++k) {
+            ms[k] = 0.f;
+            for (size_t i = 0; i + 1 < ev[k].size(); i += 2) {
+                float t = 0.f;
+                if (hipEventElapsedTime(&t, ev[k][i], ev[k][i + 1]) == hipSuccess) ms[k] += t;
+            }
+        }
+    }
+    ~LongTimer() {
+        for (auto &v : ev)
+            for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+};
+
+}  // namespace
+
+void qv_long_free(QvLongWs &w) {
+    if (w.dev) (void)hipFree(w.dev);
+    if (w.host) (void)hipHostFree(w.host);
+    if (w.batch) (void)hipFree(w.batch);
+    w = {};
+}
+
+// The long workspace of the engine, allocated or grown by the first call that needs it: the plan tables going up (windows,
+// recordings), per recording fid / m and one record coming back, in device memory; the tables and the records once more in a
+// pinned mirror; with a model, the [max_batch, window_samples] batch the windows of a round are gathered into.
+static int long_ws(qv_engine *eng, QvLongWs &w, size_t n_win, int rows, int P, size_t batch_floats) {
+    const size_t tab = up16(n_win * sizeof(LongWin)), recs = up16((size_t)rows * sizeof(LongRec));
+    const size_t out = (size_t)rows * (sizeof(qv_long_info) + (size_t)P * 16);
+    const size_t fid = up16((size_t)rows * P * sizeof(int16_t)), m = up16((size_t)rows * P * sizeof(float));
+    const size_t dev_bytes = tab + recs + out + fid + m, host_bytes = tab + recs + out;
+    w.tab_bytes = tab; w.rec_bytes = recs; w.out_bytes = out; w.fid_bytes = fid;
+    if (dev_bytes > w.dev_cap || host_bytes > w.host_cap) {
+        if (w.dev) (void)hipFree(w.dev);
+        if (w.host) (void)hipHostFree(w.host);
+        w.dev = w.host = nullptr;
+        w.dev_cap = w.host_cap = 0;
+        void *d = nullptr, *h = nullptr;
+        if (hipMalloc(&d, dev_bytes) != hipSuccess || hipHostMalloc(&h, host_bytes, hipHostMallocDefault) != hipSuccess) {
+            if (d) (void)hipFree(d);
+            (void)hipGetLastError();
+            qv_set_error(eng, "long transcription workspace: out of memory");
+            return QV_ERR_HIP;
+        }
+        w.dev = (unsigned char *)d; w.host = (unsigned char *)h;
+        w.dev_cap = dev_bytes; w.host_cap = host_bytes;
+    }
+    if (batch_floats > w.batch_cap) {
+        if (w.batch) (void)hipFree(w.batch);
+        w.batch = nullptr;
+        w.batch_cap = 0;
+        QV_HIP(hipMalloc((void **)&w.batch, batch_floats * sizeof(float)));
+        w.batch_cap = batch_floats;
+    }
+    return QV_OK;
+}
+
+// audio != nullptr: cut, forward and collapse (qv_transcribe_long).  audio == nullptr: the caller's window log-probs
+// lp_in f32[*, t_max_in, 1025] (qv_transcribe_windows).  Everything is checked before the first launch and before an output
+// array is written.  SYNCHRONOUS on `stream`.
+int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitch, const float *lp_in, int t_max_in,
+                const int64_t *n_host, int rows, int window_samples, int margin_frames, qv_long_info *info_host, int32_t *ids_host,
+                float *logp_host, int32_t *first_host, int32_t *last_host, int pitch, hipStream_t stream) {
+    const char *who = audio ? "qv_transcribe_long" : "qv_transcribe_windows";
+    const int max_batch = c.work.max_batch;
+    if (rows > max_batch) { qv_set_error(eng, std::string(who) + ": rows exceed engine capacity"); return QV_ERR_CAPACITY; }
+    std::vector<QvLongPlan> plans(rows);
+    size_t n_win = 0;
+    int t_top = 0;
+    for (int r = 0; r < rows; ++r) {
+        const int rc = qv_long_plan_make(n_host[r], eng->cfg.max_samples, window_samples, margin_frames, &plans[r]);
+        if (rc == QV_LONG_TOO_LONG) { qv_set_error(eng, std::string(who) + ": recording longer than QV_LONG_MAX_FRAMES frames"); return QV_ERR_CAPACITY; }
+        if (rc) { qv_set_error(eng, std::string(who) + ": bad length, window_samples (a multiple of 1280, at most max_samples) or margin_frames (window - 2 margins >= 1 frame)"); return QV_ERR_ARG; }
+        if (audio && n_host[r] > audio_pitch) { qv_set_error(eng, std::string(who) + ": a recording is longer than audio_pitch"); return QV_ERR_ARG; }
+        if (audio && n_host[r] < QV_LONG_MIN_SAMPLES) { qv_set_error(eng, "utterance length out of range (need 400 <= n)"); return QV_ERR_CAPACITY; }
+        n_win += plans[r].n_windows;
+        t_top = std::max(t_top, plans[r].t_total);
+    }
+    if (pitch < t_top) { qv_set_error(eng, std::string(who) + ": pitch smaller than the longest recording's frame count"); return QV_ERR_ARG; }
+    const int kw = plans[0].kw, wn = kw * QV_LONG_HOP;
+    if (!audio && t_max_in < kw + 1) { qv_set_error(eng, std::string(who) + ": t_max smaller than a window's frame count"); return QV_ERR_ARG; }
+    if (n_win > (size_t)INT32_MAX) { qv_set_error(eng, std::string(who) + ": too many windows"); return QV_ERR_CAPACITY; }
+
+    const int P = (t_top + 3) & ~3;
+    QvLongWs &w = eng->long_ws;
+    QV_TRY_RC(long_ws(eng, w, n_win, rows, P, audio ? (size_t)max_batch * wn : 0));
+    LongWin *tab_h = (LongWin *)w.host;
+    LongRec *rec_h = (LongRec *)(w.host + w.tab_bytes);
+    const LongWin *tab_d = (const LongWin *)w.dev;
+    const LongRec *rec_d = (const LongRec *)(w.dev + w.tab_bytes);
+    unsigned char *out_d = w.dev + w.tab_bytes + w.rec_bytes, *out_h = w.host + w.tab_bytes + w.rec_bytes;
+    int16_t *fid_d = (int16_t *)(out_d + w.out_bytes);
+    float *m_d = (float *)((unsigned char *)fid_d + w.fid_bytes);
+
+    std::vector<int64_t> fwd_len(audio ? n_win : 0);
+    bool vec = audio && ((uintptr_t)audio & 15) == 0 && audio_pitch % 4 == 0;
+    size_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        const QvLongPlan &p = plans[r];
+        rec_h[r].t_frames = p.t_total;
+        rec_h[r].n_windows = p.n_windows;
+        for (int v = 0; v < p.n_windows; ++v, ++k) {
+            LongWin &t = tab_h[k];
+            const int lo = qv_long_lo(p, v), hi = qv_long_hi(p, v);
+            t.src_off = (int64_t)r * audio_pitch + qv_long_start(p, v);
+            t.dst = (int64_t)r * P + lo;
+            t.len = qv_long_len(p, v);
+            t.lp_win = audio ? (int32_t)(k % (size_t)max_batch) : (int32_t)k;
+            t.j0 = lo - v * p.h;
+            t.count = hi - lo;
+            if (audio) fwd_len[k] = qv_long_fwd_len(p, v);
+        }
+    }
+    QV_HIP(hipMemcpyAsync(w.dev, w.host, w.tab_bytes + w.rec_bytes, hipMemcpyHostToDevice, stream));
+    LongTimer tm = {eng->profile_stages, stream, {}};
+    const int most_owned = kw + 1;   // grid of k_long_frames: a wave whose frame its window does not own leaves at once
+    if (audio) {
+        std::vector<int32_t> t_out(max_batch);
+        for (size_t k0 = 0; k0 < n_win; k0 += max_batch) {
+            const int nb = (int)std::min<size_t>(max_batch, n_win - k0);
+            int64_t lmax = 0;
+            for (int b = 0; b < nb; ++b) lmax = std::max(lmax, fwd_len[k0 + b]);
+            const int t_max = qv_long_frames(lmax);
+            tm.mark(0);
+            hipLaunchKernelGGL(k_long_gather, dim3((wn / 4 + LG_THREADS - 1) / LG_THREADS, nb), dim3(LG_THREADS), 0, stream, audio, tab_d + k0,
+                               w.batch, wn, (int)vec);
+            QV_HIP(hipGetLastError());
+            tm.mark(0);
+            QV_TRY_RC(qv_model_forward(eng, eng->model, eng->cur_ctx, w.batch, fwd_len.data() + k0, nb, wn, c.logprobs_ws, t_max, t_out.data(),
+                                       stream, /*zero_pad_rows=*/false));
+            tm.mark(1);
+            hipLaunchKernelGGL(k_long_frames, dim3((most_owned + LF_WAVES - 1) / LF_WAVES, nb), dim3(64 * LF_WAVES), 0, stream,
+                               (const float *)c.logprobs_ws, t_max, tab_d + k0, fid_d, m_d);
+            QV_HIP(hipGetLastError());
+            tm.mark(1);
+        }
+    } else {
+        for (size_t k0 = 0; k0 < n_win; k0 += 32768) {
+            const int nb = (int)std::min<size_t>(32768, n_win - k0);
+            tm.mark(1);
+            hipLaunchKernelGGL(k_long_frames, dim3((most_owned + LF_WAVES - 1) / LF_WAVES, nb), dim3(64 * LF_WAVES), 0, stream, lp_in, t_max_in,
+                               tab_d + k0, fid_d, m_d);
+            QV_HIP(hipGetLastError());
+            tm.mark(1);
+        }
+    }
+    tm.mark(2);
+    hipLaunchKernelGGL(k_long_collapse, dim3(rows), dim3(64 * LC_WAVES), 0, stream, (const int16_t *)fid_d, (const float *)m_d, rec_d, out_d, P);
+    QV_HIP(hipGetLastError());
+    tm.mark(2);
+    QV_HIP(hipMemcpyAsync(out_h, out_d, w.out_bytes, hipMemcpyDeviceToHost, stream));
+    QV_HIP(hipStreamSynchronize(stream));
+    tm.finish(w.kernel_ms);
+    const size_t row = sizeof(qv_long_info) + (size_t)P * 16;
+    for (int r = 0; r < rows; ++r) {
+        const unsigned char *rec = out_h + row * r;
+        const int32_t *r_ids = (const int32_t *)(rec + sizeof(qv_long_info));
+        const float *r_logp = (const float *)(r_ids + P);
+        const int32_t *r_first = (const int32_t *)(r_logp + P), *r_last = r_first + P;
+        const size_t o = (size_t)r * pitch;
+        memcpy(&info_host[r], rec, sizeof(qv_long_info));
+        memcpy(ids_host + o, r_ids, sizeof(int32_t) * t_top);
+        if (logp_host) memcpy(logp_host + o, r_logp, sizeof(float) * t_top);
+        if (first_host) memcpy(first_host + o, r_first, sizeof(int32_t) * t_top);
+        if (last_host) memcpy(last_host + o, r_last, sizeof(int32_t) * t_top);
+        for (int i = t_top; i < pitch; ++i) {
+            ids_host[o + i] = -1;
+            if (logp_host) logp_host[o + i] = 0.f;
+            if (first_host) first_host[o + i] = -1;
+            if (last_host) last_host[o + i] = -1;
+        }
+    }
+    return QV_OK;
+}

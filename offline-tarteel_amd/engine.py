@@ -113,6 +113,21 @@ TRANSCRIPT_INFO_DTYPE = np.dtype([("n_tokens", "<i4"), ("t_frames", "<i4"), ("n_
                                   ("avg_logprob", "<f8"), ("frame_avg_logprob", "<f8")])
 assert TRANSCRIPT_INFO_DTYPE.itemsize == C.sizeof(QvTranscriptInfo) == 40
 
+class QvLongInfo(C.Structure):
+    """include/qverse.h: qv_long_info"""
+    _fields_ = [("n_tokens", C.c_int32), ("t_frames", C.c_int32), ("n_blank_frames", C.c_int32), ("flags", C.c_int32),
+                ("n_windows", C.c_int32), ("reserved", C.c_int32),
+                ("min_token_logprob", C.c_float), ("reserved_f", C.c_float),
+                ("avg_logprob", C.c_double), ("frame_avg_logprob", C.c_double)]
+
+
+LONG_INFO_DTYPE = np.dtype([("n_tokens", "<i4"), ("t_frames", "<i4"), ("n_blank_frames", "<i4"), ("flags", "<i4"),
+                            ("n_windows", "<i4"), ("reserved", "<i4"), ("min_token_logprob", "<f4"), ("reserved_f", "<f4"),
+                            ("avg_logprob", "<f8"), ("frame_avg_logprob", "<f8")])
+assert LONG_INFO_DTYPE.itemsize == C.sizeof(QvLongInfo) == 48
+QV_LONG_MAX_FRAMES = 262144
+QV_LONG_HOP = 1280   # samples per encoder frame
+
 RESULT_DTYPE = np.dtype([
     ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("source", "<i4"),
     ("score", "<f8"), ("base_score", "<f8"), ("ctc_norm_loss", "<f4"),
@@ -172,6 +187,10 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_nbest_select.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.qv_transcribe.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_transcribe_batch.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_long_plan.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp]
+    lib.qv_transcribe_long.argtypes = [vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_transcribe_windows.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_long_kernel_times.argtypes = [vp, vp]
     lib.qv_tracker_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -219,6 +238,21 @@ def env_knobs() -> dict:
         span_penalty=float(os.getenv("CTC_DIRECT_SPAN_PENALTY", "0.5")),
         stream_gate=stream_gate_default(),   # QVERSE_STREAM_GATE: not a qv_config field (Engine.__init__ takes it out)
     )
+
+
+_long_env = None
+
+
+def long_env() -> tuple[float | None, float | None]:
+    """(window seconds, margin seconds) from QVERSE_LONG_WINDOW_S / QVERSE_LONG_MARGIN_S, read once; None = the default
+    (the largest window the engine accepts; min(50, Kw / 4) frames of margin)"""
+    global _long_env
+    if _long_env is None:
+        def num(name):
+            v = os.environ.get(name, "").strip()
+            return float(v) if v else None
+        _long_env = (num("QVERSE_LONG_WINDOW_S"), num("QVERSE_LONG_MARGIN_S"))
+    return _long_env
 
 
 def stream_gate_default() -> bool:
@@ -279,6 +313,7 @@ class Engine:
         self.contexts = int(self.lib.qv_context_count(h))
         self.max_transcript = int(self.lib.qv_max_transcript(h))
         self.max_batch = max_batch
+        self.max_samples = int(max_samples)
         self.tables = Tables(self.tables_path)
 
     def close(self):
@@ -881,6 +916,97 @@ class Engine:
             keep[1:] = row[1:] != row[:-1]
             out.append(self.transcript_of(row[keep & (row != 1024)].tolist()))
         return out
+
+    # ------------------------------------------------ recordings of any length -----
+    def _long_args(self, window_s, margin_s) -> tuple[int, int]:
+        """(window_samples, margin_frames) as the C calls take them: seconds to whole frames of 1280 samples; None = the
+        environment's value (QVERSE_LONG_WINDOW_S / QVERSE_LONG_MARGIN_S), else the library's default (0 / -1)"""
+        env_w, env_m = long_env()
+        window_s = env_w if window_s is None else window_s
+        margin_s = env_m if margin_s is None else margin_s
+        window = 0 if window_s is None else int(round(float(window_s) * 16000)) // QV_LONG_HOP * QV_LONG_HOP
+        margin = -1 if margin_s is None else int(round(float(margin_s) * 16000 / QV_LONG_HOP))
+        if window_s is not None and window < QV_LONG_HOP:
+            raise QvError(f"long window of {window_s} s is shorter than one frame of {QV_LONG_HOP} samples")
+        return window, margin
+
+    def long_plan_raw(self, n_samples: int, window_samples: int = 0, margin_frames: int = -1) -> dict:
+        """qv_long_plan for this engine's max_samples (include/qverse.h, "recordings of any length"); host only"""
+        out = [C.c_int32() for _ in range(4)]
+        rc = self.lib.qv_long_plan(int(n_samples), self.max_samples, int(window_samples), int(margin_frames), *map(C.byref, out))
+        if rc != 0:
+            raise QvError(f"qv_long_plan failed ({rc}): n = {n_samples}, window_samples = {window_samples}, margin_frames = {margin_frames}")
+        nw, t, kw, m = (int(v.value) for v in out)
+        return {"n_windows": nw, "t_frames": t, "kw": kw, "margin_frames": m, "hop_frames": kw - 2 * m, "window_samples": kw * QV_LONG_HOP}
+
+    def long_plan(self, n: int, window_s: float | None = None, margin_s: float | None = None) -> dict:
+        """How a recording of n samples is cut: {"n_windows", "t_frames", "kw", "margin_frames", "hop_frames", "window_samples"}"""
+        return self.long_plan_raw(n, *self._long_args(window_s, margin_s))
+
+    def _long_call(self, fn, what, head, rows, t_top, window_samples, margin_frames, pitch):
+        pitch = t_top if pitch is None else int(pitch)
+        info = np.zeros(rows, dtype=LONG_INFO_DTYPE)
+        ids = np.zeros((rows, max(pitch, 1)), np.int32)
+        logp = np.zeros((rows, max(pitch, 1)), np.float32)
+        first, last = np.zeros((rows, max(pitch, 1)), np.int32), np.zeros((rows, max(pitch, 1)), np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = fn(self.h, *head, rows, int(window_samples), int(margin_frames), p(info), p(ids), p(logp), p(first), p(last), pitch,
+                self._stream())
+        self._check(rc, what)
+        return info, ids, logp, first, last
+
+    def transcribe_windows_raw(self, log_probs, n_samples, window_samples: int = 0, margin_frames: int = -1, pitch: int | None = None):
+        """qv_transcribe_windows as arrays: log_probs float32 cuda [windows of all recordings, t_max, 1025] in
+        recording-then-window order, n_samples the recordings' lengths.  Returns (info [R] of LONG_INFO_DTYPE, ids int32
+        [R, pitch], logp float32, first / last int32 [R, pitch])."""
+        torch = self.torch
+        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        n = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64))
+        plans = [self.long_plan_raw(int(v), window_samples, margin_frames) for v in n]
+        if log_probs.shape[0] != sum(p["n_windows"] for p in plans) or log_probs.shape[2] != 1025:
+            raise QvError(f"transcribe_windows: log_probs {tuple(log_probs.shape)} does not hold the {sum(p['n_windows'] for p in plans)} planned windows")
+        head = (C.c_void_p(log_probs.data_ptr()), int(log_probs.shape[1]), n.ctypes.data_as(C.c_void_p))
+        return self._long_call(self.lib.qv_transcribe_windows, "qv_transcribe_windows", head, len(n), max(p["t_frames"] for p in plans),
+                               window_samples, margin_frames, pitch)
+
+    def transcribe_long_raw(self, audio, lengths, window_samples: int = 0, margin_frames: int = -1, pitch: int | None = None):
+        """qv_transcribe_long as arrays (audio: float32 cuda [R, N]); see transcribe_windows_raw"""
+        torch = self.torch
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous() and audio.dim() == 2
+        R, N = audio.shape
+        n = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        assert len(n) == R and n.max() <= N
+        t_top = int(n.max()) // QV_LONG_HOP + 1
+        head = (C.c_void_p(audio.data_ptr()), int(N), n.ctypes.data_as(C.c_void_p))
+        return self._long_call(self.lib.qv_transcribe_long, "qv_transcribe_long", head, R, t_top, window_samples, margin_frames, pitch)
+
+    def _long_transcripts(self, info, ids, logp, first, last) -> list[dict]:
+        short = info[["n_tokens", "t_frames", "n_blank_frames", "flags", "min_token_logprob", "reserved_f", "avg_logprob",
+                      "frame_avg_logprob"]]
+        out = self._transcripts(short, ids, logp, first, last)
+        for d, nw in zip(out, info["n_windows"].tolist()):
+            d["n_windows"] = nw
+        return out
+
+    def transcribe_windows(self, log_probs, n_samples, window_s: float | None = None, margin_s: float | None = None) -> list[dict]:
+        """transcribe_long behind the forward: the caller's window log-probs (transcribe_windows_raw).  Works without a model."""
+        return self._long_transcripts(*self.transcribe_windows_raw(log_probs, n_samples, *self._long_args(window_s, margin_s)))
+
+    def transcribe_long(self, audio, lengths, window_s: float | None = None, margin_s: float | None = None) -> list[dict]:
+        """Greedy transcription with confidence of recordings of ANY length (float32 cuda [R, N], R <= max_batch): cut into
+        overlapping windows the engine accepts, the forward over rounds of max_batch windows, of every window only the frames
+        far enough from its cut edges, one collapse over the stitched sequence on the device (include/qverse.h, "recordings
+        of any length").  One dict per recording as transcribe_logprobs returns it, plus "n_windows"; "first" / "last" are
+        frames of the whole recording.  window_s / margin_s in seconds; None = QVERSE_LONG_WINDOW_S / QVERSE_LONG_MARGIN_S,
+        else the largest window and min(50, Kw / 4) frames."""
+        return self._long_transcripts(*self.transcribe_long_raw(audio, lengths, *self._long_args(window_s, margin_s)))
+
+    def long_kernel_times(self) -> dict:
+        """milliseconds the last transcribe_long / transcribe_windows call spent in its own three kernels (HIP events; needs
+        profile_stages(True))"""
+        ms = (C.c_float * 3)()
+        self._check(self.lib.qv_long_kernel_times(self.h, ms), "qv_long_kernel_times")
+        return {"gather": ms[0], "frames": ms[1], "collapse": ms[2]}
 
     def debug_retrieve(self, transcript: str) -> dict:
         """match_verse + candidate assembly for an already-normalised transcript."""

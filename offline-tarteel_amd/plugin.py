@@ -214,6 +214,8 @@ def transcribe(audio_path: str) -> str:
     eng = _ensure_engine()
     audio = load_audio(audio_path)
     dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
+    if len(audio) > eng.max_samples:   # longer than the engine's capacity: overlapping windows, stitched on the device
+        return eng.transcribe_long(dev, [len(audio)])[0]["text"]
     lp, T = eng.forward(dev, [len(audio)])
     ids = lp[0, : T[0]].argmax(-1).cpu().numpy().tolist()
     dedup, prev = [], -1
@@ -234,7 +236,19 @@ def transcribe_detailed(audio_path: str) -> dict:
     eng = _ensure_engine()
     audio = load_audio(audio_path)
     dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
+    if len(audio) > eng.max_samples:   # as transcribe(): the same dict plus "n_windows", token frames of the whole recording
+        return eng.transcribe_long(dev, [len(audio)])[0]
     return eng.transcribe_batch(dev, [len(audio)], confidence=True)[0]
+
+
+def predict_long(audio_path: str) -> list[dict]:
+    """The verses of a recording of ANY length: the emissions of StreamingPipeline.run_on_full_transcript ({"surah", "ayah",
+    "score"} per ayah, in order) on the engine's own transcript -- one forward for a clip the engine accepts, overlapping
+    windows stitched on the device (Engine.transcribe_long) for a longer one.  Transcripts above 1,024 normalised characters
+    need QVERSE_MAX_TRANSCRIPT=2048."""
+    from .streaming import StreamingPipeline
+
+    return StreamingPipeline(_ensure_engine()).run_on_full_transcript(audio_path)
 
 
 def model_size() -> int:

@@ -147,13 +147,18 @@ class StreamingPipeline:
         return out
 
     def run_on_full_transcript(self, audio_path, transcribe_fn=None) -> list[dict]:
-        """:58-105.  ``transcribe_fn(audio_path) -> str``; None = the engine."""
+        """:58-105.  ``transcribe_fn(audio_path) -> str``; None = the engine (a recording longer than the engine's
+        capacity through Engine.transcribe_long: overlapping windows, stitched on the device)."""
         if transcribe_fn is None:
             import torch
 
             eng = self._eng()
             audio = self._load(audio_path)
-            transcript = eng.transcribe_batch(torch.from_numpy(audio[None, :]).cuda(eng.device), [len(audio)])[0]
+            dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
+            if len(audio) > eng.max_samples:
+                transcript = eng.transcribe_long(dev, [len(audio)])[0]["text"]
+            else:
+                transcript = eng.transcribe_batch(dev, [len(audio)])[0]
         else:
             transcript = transcribe_fn(audio_path)
         match = self._match_verse_fn
