@@ -450,6 +450,69 @@ int qv_transcribe_windows(qv_engine *e, const float *logprobs_dev, int32_t t_max
                           float *logp_host, int32_t *first_host, int32_t *last_host,
                           int32_t pitch, void *stream);
 
+/* ---- verse-constrained beam search ------------------------------------------------------------------
+ * A CTC prefix beam search in which every hypothesis is a prefix of a real verse or of a run of up to max_span consecutive
+ * verses: it cannot leave the Quran, needs no text matching, and recognises a recitation that stops mid-verse as a prefix
+ * with a known set of verses still reachable.  (The reference's second route, web/frontend/src/worker/beam-decode.ts over
+ * src/lib/phoneme-trie.ts, with one deliberate difference: DESIGN.md 4.16.)
+ *   the trie    for every verse v ascending and every span sp = 1..max_span the token sequence of key v * 6 + sp - 1 of the
+ *               tables' token table (what the CTC rerank scores), empty ones skipped; (v, sp) is an END of the sequence's last
+ *               node.  Nodes are numbered breadth-first from root = 0, the children of a node in ascending token id.
+ *               tok(n) = the token on the edge into node n.  161,465 / 343,929 / 523,170 / 1,046,039 nodes for max_span
+ *               1 / 2 / 3 / 6; 8 bytes per node in HBM.  Built and uploaded by the first call that asks for a span, kept until
+ *               another span is asked for or qv_destroy.
+ *   a state     at most `beam` hypotheses (n, pb, pnb): node, log-probability (float64) of the paths that end in blank / in
+ *               non-blank.  Start: {(0, 0.0, -inf)}.  lae(a, b) = b if a == -inf; a if b == -inf; else
+ *               max + log1p(exp(min - max)).  tot = lae(pb, pnb).
+ *   frame t     row lp[t] (float32, widened exactly).  Every hypothesis stays: pb' = tot + lp[blank], s = pnb + lp[tok(n)]
+ *               (s = -inf for the root); and extends into every child c with token k:
+ *               x(c) = ((n != 0 && k == tok(n)) ? pb : tot) + lp[k].  A candidate node c gets pb'(c) from its own stay
+ *               (else -inf) and pnb'(c) = lae(s(c), x(c)), a missing term taken as -inf.
+ *   pruning     candidates whose total is -inf are dropped; the `beam` largest totals are kept, ties to the smaller node.
+ *   result      after the last frame the hypotheses by total descending, ties to the smaller node; the first k of them.
+ *               max_candidates = the largest number of distinct candidate nodes a frame produced (before the -inf ones are
+ *               dropped); no candidate is ever dropped for lack of room.
+ * Rows t >= t_host[b] are never read; valid frames hold no NaN.  A row of t_host[b] = 0 returns the start state. */
+#define QV_BEAM_MAX 64
+enum { QV_BEAM_COMPLETE = 1 };      /* qv_beam_entry.flags: the node is the end of at least one (verse, span) */
+typedef struct {
+    int32_t node;                   /* trie node of the hypothesis (of the trie for the call's max_span) */
+    int32_t n_tokens;               /* its depth */
+    int32_t n_ends;                 /* (verse, span) sequences that END here (repeated verses share a node) */
+    int32_t start_verse, span;      /* the first of them by (verse, span): global verse index, number of ayat; -1, 0 if none */
+    int32_t surah, ayah, ayah_end;  /* ... as a reference; 0, 0, 0 if none */
+    int32_t below_count;            /* ends at or under the node: what is still reachable */
+    int32_t below_verse, below_span;/* the smallest (verse, span) among them */
+    int32_t flags;                  /* QV_BEAM_* */
+    double score;                   /* lae(blank_score, nonblank_score) */
+    double blank_score, nonblank_score;
+} qv_beam_entry;
+typedef struct { int32_t n_entries, t_frames, max_candidates, reserved; } qv_beam_info;
+
+/* Statistics of the trie for max_span in 1..6 from a tables file: host only, no engine, no GPU.  Output pointers may be
+ * NULL.  QV_ERR_ARG for a bad span, QV_ERR_IO for a file the reader refuses. */
+int qv_trie_stats(const char *tables_path, int32_t max_span, int32_t *nodes, int32_t *ends, int32_t *max_depth,
+                  int32_t *max_children);
+/* The tokens from the root to `node` of the engine's trie for max_span (host-side walk of the parents; builds the trie if
+ * the engine does not hold that span).  n_out receives the count; more than `cap` tokens or no such node: QV_ERR_ARG. */
+int qv_trie_node_tokens(qv_engine *e, int32_t max_span, int32_t node, int32_t *ids_out, int32_t cap, int32_t *n_out);
+/* The search on the caller's log-probs f32[batch, t_max, 1025]; works on an engine without a model.  SYNCHRONOUS on
+ * `stream`.  info_host[batch]; entries_host[batch][k], entries past n_entries zeroed; ids_host (may be NULL): row b, `pitch`
+ * entries apart (pitch >= t_max), receives the tokens of entry 0, -1 padded.  1 <= beam <= QV_BEAM_MAX, 1 <= k <= beam.
+ * One record per row comes back in one copy; the workspace (max_batch records of 2,064 bytes plus a pinned mirror) belongs to
+ * the current execution context and is allocated by the first call that uses it.  Null pointers, batch < 1, t_max < 1, beam /
+ * k / max_span out of range, pitch < t_max, a t_host[b] outside 0..t_max: QV_ERR_ARG; batch above max_batch or t_max above
+ * the engine's frame capacity: QV_ERR_CAPACITY, before anything is launched. */
+int qv_beam_decode(qv_engine *e, const float *logprobs_dev, const int32_t *t_host, int32_t batch, int32_t t_max,
+                   int32_t max_span, int32_t beam, int32_t k, qv_beam_info *info_host, qv_beam_entry *entries_host,
+                   int32_t *ids_host, int32_t pitch, void *stream);
+/* the forward (as qv_transcribe_batch runs it, with the same contract: waits for batches in flight, forgets the workspace's
+ * earlier batch, QV_ERR_NO_MODEL without a model) into the current context's log-prob workspace, then the same kernel;
+ * t_max = qv_frames_for_samples(longest row). */
+int qv_beam_batch(qv_engine *e, const float *audio_dev, const int64_t *lengths_host, int32_t batch, int64_t n_max,
+                  int32_t max_span, int32_t beam, int32_t k, qv_beam_info *info_host, qv_beam_entry *entries_host,
+                  int32_t *ids_host, int32_t pitch, void *stream);
+
 /* Device pointer of the packed (surah, ayah, ayah_end, float-bits(score)) i32[B,4] rows of the
  * last async call -- the payload of the per-batch RCCL all-gather. */
 const int32_t *qv_packed_results_dev(qv_engine *e);

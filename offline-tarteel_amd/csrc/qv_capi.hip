@@ -5,6 +5,7 @@
 #include "qv_layers.h"
 #include "qv_long_plan.h"
 #include "qv_tables_host.h"
+#include "qv_trie_host.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -421,12 +422,14 @@ extern "C" void qv_destroy(qv_engine *e) {
     if (e->model) qv_model_destroy(e->model);
     for (void *p : e->allocs) (void)hipFree(p);
     qv_long_free(e->long_ws);
+    qv_beam_free(e);
     for (QvCtx &c : e->ctx) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
         if (c.align.out_host) (void)hipHostFree(c.align.out_host);
         if (c.align.in_host) (void)hipHostFree(c.align.in_host);
         if (c.nbest.out_host) (void)hipHostFree(c.nbest.out_host);
         if (c.transcribe.host) (void)hipHostFree(c.transcribe.host);
+        if (c.beam.host) (void)hipHostFree(c.beam.host);
         if (c.stream) (void)hipStreamDestroy(c.stream);
         if (c.in_ready) (void)hipEventDestroy(c.in_ready);
         if (c.done) (void)hipEventDestroy(c.done);
@@ -963,6 +966,88 @@ extern "C" int qv_transcribe_batch(qv_engine *eng, const float *audio_dev, const
     if (rc) return rc;
     return qv_transcribe_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, info_host, ids_host, logp_host, first_host, last_host,
                               pitch, (hipStream_t)stream);
+}
+
+// ---- verse-constrained beam search (qv_beam.hip, qv_trie_host.h) ----------------------------------------------------
+extern "C" int qv_trie_stats(const char *tables_path, int32_t max_span, int32_t *nodes, int32_t *ends, int32_t *max_depth,
+                             int32_t *max_children) {
+    if (!tables_path || max_span < 1 || max_span > QV_TRIE_MAX_SPAN) { qv_set_error(nullptr, "qv_trie_stats: null path or max_span outside 1..6"); return QV_ERR_ARG; }
+    std::ifstream f(tables_path, std::ios::binary | std::ios::ate);
+    if (!f) { qv_set_error(nullptr, std::string("cannot open tables file: ") + tables_path); return QV_ERR_IO; }
+    const std::streamsize sz = f.tellg();
+    f.seekg(0);
+    std::vector<uint8_t> file(sz > 0 ? (size_t)sz : 0);
+    if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();   // refused below: bad magic
+    HostTables h;
+    std::string err;
+    if (int rc = qv_build_host_tables(file.data(), file.size(), h, err)) { qv_set_error(nullptr, err); return rc; }
+    QvTrie t;
+    if (int rc = qv_trie_build(h.n_verses, h.tok_off.p, h.tok_off.n, h.tok.p, h.tok.n, max_span, t, err)) {
+        qv_set_error(nullptr, err);
+        return rc == QV_TRIE_BAD_ARG ? QV_ERR_ARG : QV_ERR_IO;
+    }
+    if (nodes) *nodes = (int32_t)t.n_nodes();
+    if (ends) *ends = (int32_t)t.ends.size();
+    if (max_depth) *max_depth = t.max_depth;
+    if (max_children) *max_children = t.max_children;
+    return QV_OK;
+}
+
+extern "C" int qv_trie_node_tokens(qv_engine *eng, int32_t max_span, int32_t node, int32_t *ids_out, int32_t cap, int32_t *n_out) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!ids_out || !n_out || cap < 0) { qv_set_error(eng, "qv_trie_node_tokens: null argument or cap < 0"); return QV_ERR_ARG; }
+    return qv_beam_node_tokens(eng, max_span, node, ids_out, cap, n_out);
+}
+
+// the argument rules the two beam entry points share (everything but the log-probs and their frame counts)
+static int beam_args(qv_engine *eng, const char *who, int32_t batch, int32_t max_span, int32_t beam, int32_t k, const void *info_host,
+                     const void *entries_host, const int32_t *ids_host, int32_t pitch, int32_t t_max) {
+    if (!info_host || !entries_host || batch < 1 || max_span < 1 || max_span > QV_TRIE_MAX_SPAN || beam < 1 || beam > QV_BEAM_MAX || k < 1 ||
+        k > beam || (ids_host && pitch < t_max)) {
+        qv_set_error(eng, std::string(who) + ": null argument, empty batch, max_span outside 1..6, beam outside 1..QV_BEAM_MAX, k outside 1..beam or pitch < t_max");
+        return QV_ERR_ARG;
+    }
+    return QV_OK;
+}
+
+extern "C" int qv_beam_decode(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch, int32_t t_max, int32_t max_span,
+                              int32_t beam, int32_t k, qv_beam_info *info_host, qv_beam_entry *entries_host, int32_t *ids_host,
+                              int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!lp || !t_host || t_max < 1) { qv_set_error(eng, "qv_beam_decode: null argument or t_max < 1"); return QV_ERR_ARG; }
+    QV_TRY(beam_args(eng, "qv_beam_decode", batch, max_span, beam, k, info_host, entries_host, ids_host, pitch, t_max));
+    QV_ORDERED(eng, stream);
+    return qv_beam_rows(eng, eng->ctx[eng->cur_ctx], lp, t_host, batch, t_max, max_span, beam, k, info_host, entries_host, ids_host, pitch,
+                        (hipStream_t)stream);
+}
+
+extern "C" int qv_beam_batch(qv_engine *eng, const float *audio_dev, const int64_t *lengths_host, int32_t batch, int64_t n_max,
+                             int32_t max_span, int32_t beam, int32_t k, qv_beam_info *info_host, qv_beam_entry *entries_host,
+                             int32_t *ids_host, int32_t pitch, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    if (!audio_dev || !lengths_host || batch < 1) { qv_set_error(eng, "qv_beam_batch: null argument or empty batch"); return QV_ERR_ARG; }
+    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "qv_beam_batch: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    int64_t lmax = 0;
+    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
+    const int t_max = qv_frames_for_samples(lmax);
+    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "qv_beam_batch: audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    if (t_max < 1) { qv_set_error(eng, "qv_beam_batch: no frames"); return QV_ERR_ARG; }
+    QV_TRY(beam_args(eng, "qv_beam_batch", batch, max_span, beam, k, info_host, entries_host, ids_host, pitch, t_max));
+    QV_ORDERED(eng, stream);
+    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
+    QV_TRY(quiesce_contexts(eng));
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
+    std::vector<int32_t> t_out(batch);
+    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max, t_out.data(),
+                              (hipStream_t)stream, /*zero_pad_rows=*/false);
+    if (rc) return rc;
+    return qv_beam_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, max_span, beam, k, info_host, entries_host, ids_host, pitch,
+                        (hipStream_t)stream);
 }
 
 // ---- recordings of any length (qv_long.hip, qv_long_plan.h) ---------------------------------------------------------

@@ -234,6 +234,23 @@ int qv_transcribe_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t 
                        qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host, int16_t *last_host,
                        int pitch, hipStream_t stream);
 
+// verse-constrained beam search (qv_beam.hip; the trie: qv_trie_host.h).  One record per row -- qv_beam_info, then QV_BEAM_MAX
+// (node, total, pb, pnb) entries -- so a batch comes back in ONE copy into the pinned mirror.  Per-context workspace, allocated
+// by the first beam call on that context (dev == nullptr: not yet): the rows' frame counts in the first t_bytes, the records
+// behind them.  The trie of the span last asked for belongs to the engine (QvBeamState, nullptr until a call needs it).
+struct QvBeamWs {
+    unsigned char *dev;
+    unsigned char *host;
+    size_t t_bytes;
+};
+struct QvBeamState;
+struct QvTrie;
+void qv_beam_free(qv_engine *eng);
+int qv_beam_trie(qv_engine *eng, int max_span, const QvTrie **out);
+int qv_beam_node_tokens(qv_engine *eng, int max_span, int node, int32_t *ids_out, int cap, int32_t *n_out);
+int qv_beam_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max, int max_span, int W, int k,
+                 qv_beam_info *info_host, qv_beam_entry *entries_host, int32_t *ids_host, int pitch, hipStream_t stream);
+
 // recordings of any length (qv_long.hip; the cutting rule: qv_long_plan.h).  One workspace per engine, allocated or grown by
 // the first call that needs it and freed by qv_destroy: `dev` holds the plan tables (tab_bytes, rec_bytes), the records
 // (out_bytes), then fid (fid_bytes) and m; `host` mirrors tables and records in pinned memory; `batch` is the
@@ -334,6 +351,8 @@ struct QvCtx {
     QvNbestWs nbest = {};
     // transcription with confidence (qv_transcribe, qv_transcribe_batch): independent of the batch state above
     QvTranscribeWs transcribe = {};
+    // verse-constrained beam search (qv_beam_decode, qv_beam_batch): independent of the batch state as well
+    QvBeamWs beam = {};
 };
 
 struct qv_engine {
@@ -365,6 +384,7 @@ struct qv_engine {
     unsigned resample_at = 0;
     QvTrack track;
     QvLongWs long_ws = {};
+    QvBeamState *beam = nullptr;   // the trie of the beam search (qv_beam.hip), built by the first call that asks for it
     bool profile_stages;
     // measurement hook (qv_profile_inject_logprobs): caller-owned log-probs the post-logits stages of
     // qv_predict_batch_async() read INSTEAD of the forward's own output (the forward still runs in full)

@@ -128,6 +128,40 @@ assert LONG_INFO_DTYPE.itemsize == C.sizeof(QvLongInfo) == 48
 QV_LONG_MAX_FRAMES = 262144
 QV_LONG_HOP = 1280   # samples per encoder frame
 
+BEAM_MAX = 64        # include/qverse.h: QV_BEAM_MAX
+BEAM_COMPLETE = 1    # QV_BEAM_COMPLETE
+
+
+class QvBeamEntry(C.Structure):
+    """include/qverse.h: qv_beam_entry"""
+    _fields_ = [("node", C.c_int32), ("n_tokens", C.c_int32), ("n_ends", C.c_int32), ("start_verse", C.c_int32), ("span", C.c_int32),
+                ("surah", C.c_int32), ("ayah", C.c_int32), ("ayah_end", C.c_int32), ("below_count", C.c_int32),
+                ("below_verse", C.c_int32), ("below_span", C.c_int32), ("flags", C.c_int32),
+                ("score", C.c_double), ("blank_score", C.c_double), ("nonblank_score", C.c_double)]
+
+
+BEAM_ENTRY_DTYPE = np.dtype([("node", "<i4"), ("n_tokens", "<i4"), ("n_ends", "<i4"), ("start_verse", "<i4"), ("span", "<i4"),
+                             ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("below_count", "<i4"), ("below_verse", "<i4"),
+                             ("below_span", "<i4"), ("flags", "<i4"), ("score", "<f8"), ("blank_score", "<f8"),
+                             ("nonblank_score", "<f8")])
+BEAM_INFO_DTYPE = np.dtype([("n_entries", "<i4"), ("t_frames", "<i4"), ("max_candidates", "<i4"), ("reserved", "<i4")])
+assert BEAM_ENTRY_DTYPE.itemsize == C.sizeof(QvBeamEntry) == 72 and BEAM_INFO_DTYPE.itemsize == 16
+
+
+def trie_stats(max_span: int = 3, tables_path: str | None = None) -> dict:
+    """qv_trie_stats: {"nodes", "ends", "max_depth", "max_children"} of the beam search's trie for max_span in 1..6, from the
+    tables file alone -- host only, no engine, no GPU."""
+    lib = load_library()
+    out = [C.c_int32(0) for _ in range(4)]
+    rc = lib.qv_trie_stats(str(tables_path or TABLES_PATH).encode(), int(max_span), *map(C.byref, out))
+    if rc != 0:
+        msg = lib.qv_last_error(None).decode()
+        if rc == 2:
+            raise FileNotFoundError(msg)
+        raise QvError(f"qv_trie_stats failed ({rc}): {msg}")
+    return dict(zip(("nodes", "ends", "max_depth", "max_children"), (int(v.value) for v in out)))
+
+
 RESULT_DTYPE = np.dtype([
     ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("source", "<i4"),
     ("score", "<f8"), ("base_score", "<f8"), ("ctc_norm_loss", "<f4"),
@@ -191,6 +225,10 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_transcribe_long.argtypes = [vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_transcribe_windows.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_long_kernel_times.argtypes = [vp, vp]
+    lib.qv_trie_stats.argtypes = [C.c_char_p, i32, vp, vp, vp, vp]
+    lib.qv_trie_node_tokens.argtypes = [vp, i32, i32, vp, i32, vp]
+    lib.qv_beam_decode.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
+    lib.qv_beam_batch.argtypes = [vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, i32, vp]
     lib.qv_tracker_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -916,6 +954,75 @@ class Engine:
             keep[1:] = row[1:] != row[:-1]
             out.append(self.transcript_of(row[keep & (row != 1024)].tolist()))
         return out
+
+    # ------------------------------------------------ verse-constrained beam search -----
+    def trie_node_tokens(self, node: int, max_span: int = 3) -> list[int]:
+        """the tokens from the root to `node` of the trie for max_span (qv_trie_node_tokens)"""
+        ids = np.zeros(1024, np.int32)
+        n = C.c_int32(0)
+        rc = self.lib.qv_trie_node_tokens(self.h, int(max_span), int(node), ids.ctypes.data_as(C.c_void_p), len(ids), C.byref(n))
+        self._check(rc, "qv_trie_node_tokens")
+        return ids[: n.value].tolist()
+
+    def beam_raw(self, log_probs, t_frames, beam: int = 8, k: int = 5, max_span: int = 3):
+        """qv_beam_decode as arrays: (info [B] of BEAM_INFO_DTYPE, entries [B, k] of BEAM_ENTRY_DTYPE, ids int32 [B, t_max] --
+        the tokens of entry 0, -1 padded)."""
+        torch = self.torch
+        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        B, t_max, V = log_probs.shape
+        assert V == 1025 and len(t_frames) == B
+        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        info = np.zeros(B, dtype=BEAM_INFO_DTYPE)
+        ent = np.zeros((B, max(int(k), 1)), dtype=BEAM_ENTRY_DTYPE)
+        ids = np.full((B, max(t_max, 1)), -1, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_beam_decode(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, int(max_span), int(beam), int(k), p(info),
+                                     p(ent), p(ids), t_max, self._stream())
+        self._check(rc, "qv_beam_decode")
+        return info, ent, ids
+
+    def _beam_rows(self, info, ent, ids, max_span: int) -> list[dict]:
+        tab = self.tables
+        out = []
+        for b in range(len(info)):
+            hyps = []
+            for i, e in enumerate(ent[b, : int(info[b]["n_entries"])].tolist()):
+                (node, n_tok, n_ends, start, span, surah, ayah, ayah_end, below, bv, bs, flags, score, pb, pnb) = e
+                toks = ids[b, :n_tok].tolist() if i == 0 else self.trie_node_tokens(node, max_span)
+                first = (int(tab.surah[bv]), int(tab.ayah[bv]), int(tab.ayah[bv]) + bs - 1) if below else None
+                hyps.append({"surah": surah, "ayah": ayah, "ayah_end": ayah_end if surah else None, "score": score,
+                             "complete": bool(flags & BEAM_COMPLETE), "n_tokens": n_tok, "text": tab.ids_to_text(toks),
+                             "matches": n_ends, "reachable": below, "first_reachable": first, "node": node, "start": start,
+                             "span": span, "blank_score": pb, "nonblank_score": pnb, "ids": toks})
+            out.append({"t_frames": int(info[b]["t_frames"]), "max_candidates": int(info[b]["max_candidates"]), "hypotheses": hyps})
+        return out
+
+    def beam_logprobs(self, log_probs, t_frames, beam: int = 8, k: int = 5, max_span: int = 3) -> list[dict]:
+        """Verse-constrained CTC prefix beam search (qv_beam_decode; definition in include/qverse.h) of float32 cuda log-probs
+        [B, t_max, 1025] with t_frames[b] valid frames: every hypothesis is a prefix of a verse or of up to max_span
+        consecutive verses.  Per row {"t_frames", "max_candidates", "hypotheses"}; the at most k hypotheses, best first, are
+        {"surah", "ayah", "ayah_end" (of the first verse run that ENDS at the prefix; 0, 0, None when none does), "score"
+        (log-probability of the prefix), "complete", "n_tokens", "text" (Tables.ids_to_text of the prefix), "matches" (verse
+        runs that end here), "reachable" (verse runs that start with the prefix), "first_reachable" (surah, ayah, ayah_end of
+        the first of them), and "node", "start", "span", "blank_score", "nonblank_score", "ids"}."""
+        return self._beam_rows(*self.beam_raw(log_probs, t_frames, beam, k, max_span), max_span)
+
+    def beam_batch(self, audio, lengths, beam: int = 8, k: int = 5, max_span: int = 3) -> list[dict]:
+        """beam_logprobs behind the forward (qv_beam_batch): audio float32 cuda [B, N], zero padded"""
+        torch = self.torch
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
+        B, N = audio.shape
+        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        assert len(ln) == B and ln.max() <= N
+        pitch = max(self.frames_for(int(ln.max())), 1)
+        info = np.zeros(B, dtype=BEAM_INFO_DTYPE)
+        ent = np.zeros((B, max(int(k), 1)), dtype=BEAM_ENTRY_DTYPE)
+        ids = np.full((B, pitch), -1, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_beam_batch(self.h, C.c_void_p(audio.data_ptr()), p(ln), B, N, int(max_span), int(beam), int(k), p(info), p(ent),
+                                    p(ids), pitch, self._stream())
+        self._check(rc, "qv_beam_batch")
+        return self._beam_rows(info, ent, ids, max_span)
 
     # ------------------------------------------------ recordings of any length -----
     def _long_args(self, window_s, margin_s) -> tuple[int, int]:

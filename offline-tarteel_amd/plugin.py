@@ -120,6 +120,30 @@ def _finish(eng, raw: list[dict], round_score: bool, words: bool, candidates: in
     return out
 
 
+def trie_fallback_enabled() -> bool:
+    """QVERSE_TRIE_FALLBACK=1 (off by default): a row predict() / predict_batch() would return without a prediction takes the
+    best COMPLETE hypothesis of the verse-constrained beam search (Engine.beam_batch), provided it outranks every incomplete
+    one.  Unset, every output is what it was."""
+    return os.getenv("QVERSE_TRIE_FALLBACK", "") not in ("", "0", "false", "False")
+
+
+def _trie_fallback(eng, out: list[dict], raw: list[dict], beam_rows) -> list[dict]:
+    """beam_rows(indices) -> Engine.beam_batch rows of those clips.  A row without a prediction becomes the search's first
+    hypothesis when that one is complete (so the best complete hypothesis outranks every incomplete one): "source": "trie",
+    "score" the hypothesis' log-probability, unrounded."""
+    missing = [i for i, r in enumerate(raw) if not r["surah"]]
+    if not missing:
+        return out
+    for i, row in zip(missing, beam_rows(missing)):
+        hyps = row["hypotheses"]
+        if hyps and hyps[0]["complete"]:
+            h = hyps[0]
+            extra = {k: v for k, v in out[i].items() if k in ("words", "candidates")}
+            out[i] = {"surah": h["surah"], "ayah": h["ayah"], "ayah_end": h["ayah_end"], "score": h["score"],
+                      "transcript": out[i].get("transcript", ""), "source": "trie", **extra}
+    return out
+
+
 def predict_arrays(arrays, round_score: bool = True, words: bool = False, candidates: int | None = None) -> list[dict]:
     """audio arrays (float32, 16 kHz) -> predict()-shaped dicts, one engine call per <= MAX_BATCH.
     words=True: every dict gains "words" (see predict_words); candidates=K: "candidates" (see predict_candidates)."""
@@ -136,7 +160,10 @@ def predict_arrays(arrays, round_score: bool = True, words: bool = False, candid
         dev = torch.from_numpy(buf).cuda(eng.device)
         raw = eng.predict_batch(dev, lens, align=words, nbest=candidates)
         _last_raw[:] = raw
-        out.extend(_finish(eng, raw, round_score, words, candidates))
+        part = _finish(eng, raw, round_score, words, candidates)
+        if trie_fallback_enabled():
+            part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(dev[idx].contiguous(), [lens[i] for i in idx]))
+        out.extend(part)
     return out
 
 
@@ -146,9 +173,13 @@ def predict_device(dev, lens, round_score: bool = True, words: bool = False, can
     out = []
     for s in range(0, len(lens), eng.max_batch):
         chunk = lens[s: s + eng.max_batch]
-        raw = eng.predict_batch(dev[s: s + len(chunk), : max(chunk)].contiguous(), chunk, align=words, nbest=candidates)
+        rows = dev[s: s + len(chunk), : max(chunk)].contiguous()
+        raw = eng.predict_batch(rows, chunk, align=words, nbest=candidates)
         _last_raw[:] = raw
-        out.extend(_finish(eng, raw, round_score, words, candidates))
+        part = _finish(eng, raw, round_score, words, candidates)
+        if trie_fallback_enabled():
+            part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(rows[idx].contiguous(), [chunk[i] for i in idx]))
+        out.extend(part)
     return out
 
 
@@ -171,6 +202,20 @@ def predict_candidates(audio_path: str, k: int = 5) -> dict:
     text match with its score when the gate passed, [] when nothing was recognised.  Selected on the device
     (Engine.nbest_results)."""
     return predict_arrays([load_audio(audio_path)], candidates=k)[0]
+
+
+def predict_constrained(audio_path: str, beam: int = 8, k: int = 5) -> dict:
+    """The verse-constrained route on its own (the reference's trie beam search, web/frontend/src/worker/beam-decode.ts): no
+    greedy transcript, no text matching.  {"t_frames", "max_candidates", "hypotheses"}: up to k prefixes of real verses (or of
+    up to three consecutive ones), best first, each {"surah", "ayah", "ayah_end", "score" (log-probability), "complete",
+    "n_tokens", "text", "matches", "reachable", "first_reachable", ...} as Engine.beam_logprobs documents them.  A recitation
+    that stops mid-verse comes back as an incomplete prefix with the verses still reachable."""
+    import torch
+
+    eng = _ensure_engine()
+    audio = load_audio(audio_path)
+    dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
+    return eng.beam_batch(dev, [len(audio)], beam=beam, k=k)[0]
 
 
 def predict_words(audio_path: str) -> dict:
