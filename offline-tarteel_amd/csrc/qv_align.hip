@@ -12,9 +12,7 @@
 //   * the same wave then walks t = T-1 .. 1 backwards.  Lane l only ever reads back the words lane l wrote, so no
 //     cross-lane visibility is needed; the rows are loaded BCH frames ahead of the walk (their addresses do not
 //     depend on the path) and the lane that owns the current state supplies the step through v_readlane.
-#include "qv_common.h"
-
-#include <string.h>
+#include "qv_rows.h"
 
 namespace {
 
@@ -265,33 +263,23 @@ __global__ void k_align_plan(QvTables tab, QvWork wk, int batch, int t_max, QvAl
 }  // namespace
 
 // The alignment workspace of one context, allocated on the first alignment call that uses it: an engine that never
-// aligns pays nothing.  Device bytes: max_batch * (t_cap * 256 for the back-pointers + 3,872 for the output records +
-// 792 for plan and targets); the two pinned mirrors add max_batch * 4,664 bytes of host memory.
+// aligns pays nothing.  One mirror: the output records (3,872 bytes per row of max_batch), then plan and targets (792), in
+// device memory and in the pinned buffer; behind them, on the device alone, the back-pointers (t_cap * 256).
 static int align_ws(qv_engine *eng, QvCtx &c, QvAlignWs **out) {
     QvAlignWs &w = c.align;
     *out = &w;
     if (w.bp) return QV_OK;
     const size_t B = (size_t)c.work.max_batch, tc = (size_t)c.work.t_cap;
-    const size_t n_out = B * QV_ALIGN_ROW_BYTES, n_in = B * (sizeof(QvAlignRow) + QV_ALIGN_PITCH * sizeof(uint16_t));
-    void *bp = nullptr, *o = nullptr, *in = nullptr, *oh = nullptr, *ih = nullptr;
-    if (hipMalloc(&bp, B * tc * 64 * sizeof(uint32_t)) != hipSuccess || hipMalloc(&o, n_out) != hipSuccess ||
-        hipMalloc(&in, n_in) != hipSuccess || hipHostMalloc(&oh, n_out, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&ih, n_in, hipHostMallocDefault) != hipSuccess) {
-        if (bp) (void)hipFree(bp);
-        if (o) (void)hipFree(o);
-        if (in) (void)hipFree(in);
-        if (oh) (void)hipHostFree(oh);
-        (void)hipGetLastError();
-        qv_set_error(eng, "alignment workspace: out of memory");
-        return QV_ERR_HIP;
-    }
-    for (void *q : {bp, o, in}) eng->allocs.push_back(q);   // freed by qv_destroy (the pinned mirrors: with the context)
-    w.out = (unsigned char *)o;
-    w.plan = (QvAlignRow *)in;
-    w.targets = (uint16_t *)((QvAlignRow *)in + B);
-    w.out_host = (unsigned char *)oh;
-    w.in_host = (unsigned char *)ih;
-    w.bp = (uint32_t *)bp;
+    const auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };   // every part as aligned as an allocation of its own
+    const size_t n_out = up256(B * QV_ALIGN_ROW_BYTES), n_in = up256(B * (sizeof(QvAlignRow) + QV_ALIGN_PITCH * sizeof(uint16_t)));
+    QvMirror m;
+    QV_TRY_RC(qv_ctx_mirror(eng, c, n_out + n_in + B * tc * 64 * sizeof(uint32_t), n_out + n_in, "alignment workspace", &m));
+    w.out = m.dev;
+    w.plan = (QvAlignRow *)(m.dev + n_out);
+    w.targets = (uint16_t *)(w.plan + B);
+    w.out_host = m.host;
+    w.in_host = m.host + n_out;
+    w.bp = (uint32_t *)(m.dev + n_out + n_in);
     return QV_OK;
 }
 
@@ -302,25 +290,17 @@ static int align_run(qv_engine *eng, QvAlignWs &w, int t_cap, const float *lp, i
     if (t_cap > 384) hipLaunchKernelGGL(k_align<true>, dim3(batch), dim3(64), 0, stream, lp, t_max, tok_base, w.plan, w, t_cap);
     else hipLaunchKernelGGL(k_align<false>, dim3(batch), dim3(64), 0, stream, lp, t_max, tok_base, w.plan, w, t_cap);
     QV_HIP(hipGetLastError());
-    QV_HIP(hipMemcpyAsync(w.out_host, w.out, (size_t)batch * QV_ALIGN_ROW_BYTES, hipMemcpyDeviceToHost, stream));
-    QV_HIP(hipStreamSynchronize(stream));
-    const size_t n = QV_ALIGN_MAX_TOKENS;
+    QV_TRY_RC(qv_fetch_sync(eng, w.out_host, w.out, (size_t)batch * QV_ALIGN_ROW_BYTES, stream));
+    const int n = QV_ALIGN_MAX_TOKENS;   // (entries past the longest alignable target hold the "no token" values as well)
     for (int b = 0; b < batch; ++b) {
         const unsigned char *rec = w.out_host + (size_t)b * QV_ALIGN_ROW_BYTES;
         const float *r_logp = (const float *)(rec + sizeof(qv_align_info));
         const int16_t *r_first = (const int16_t *)(r_logp + QV_ALIGN_PITCH), *r_last = r_first + QV_ALIGN_PITCH;
         memcpy(&info_host[b], rec, sizeof(qv_align_info));
-        memcpy(logp_host + (size_t)b * pitch, r_logp, sizeof(float) * n);
-        memcpy(first_host + (size_t)b * pitch, r_first, sizeof(int16_t) * n);
-        memcpy(last_host + (size_t)b * pitch, r_last, sizeof(int16_t) * n);
-        if (ids_host) memcpy(ids_host + (size_t)b * pitch, r_last + QV_ALIGN_PITCH, sizeof(uint16_t) * n);
-        // entries past the longest alignable target hold the "no token" values as well
-        for (int i = (int)n; i < pitch; ++i) {
-            first_host[(size_t)b * pitch + i] = -1;
-            last_host[(size_t)b * pitch + i] = -1;
-            logp_host[(size_t)b * pitch + i] = 0.f;
-            if (ids_host) ids_host[(size_t)b * pitch + i] = 0xFFFF;
-        }
+        scatter_column(logp_host, pitch, b, r_logp, n, 0.f);
+        scatter_column(first_host, pitch, b, r_first, n, (int16_t)-1);
+        scatter_column(last_host, pitch, b, r_last, n, (int16_t)-1);
+        scatter_column(ids_host, pitch, b, (const uint16_t *)(r_last + QV_ALIGN_PITCH), n, (uint16_t)0xFFFF);
     }
     return QV_OK;
 }
@@ -336,8 +316,7 @@ int qv_align_explicit(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *
     for (int b = 0; b < batch; ++b)
         if (lens_host[b] < 0 || t_host[b] < 0 || t_host[b] > t_max) { qv_set_error(eng, "qv_align: lens_host[b] / t_host[b] out of range"); return QV_ERR_ARG; }
     QvAlignWs *w = nullptr;
-    int rc = align_ws(eng, c, &w);
-    if (rc) return rc;
+    QV_TRY_RC(align_ws(eng, c, &w));
     // plan and targets are laid out in the pinned mirror as on the device and go up in one copy (the previous call has
     // finished with the mirror: alignment calls are synchronous and serialised by the engine's lock)
     QvAlignRow *plan = (QvAlignRow *)w->in_host;
@@ -368,12 +347,9 @@ int qv_align_results(qv_engine *eng, int k, int batch, qv_align_info *info_host,
         return QV_ERR_ARG;
     }
     QvAlignWs *w = nullptr;
-    int rc = align_ws(eng, c, &w);
-    if (rc) return rc;
-    // ordered behind the batch: on the context's own stream when the batch ran there, else after a device-wide join (the
-    // batch ran on a caller stream we were not given -- as qv_fetch_results_ctx)
-    hipStream_t stream = eng->n_ctx > 1 ? c.stream : nullptr;
-    if (eng->n_ctx == 1 || c.al_stream != c.stream) QV_HIP(hipDeviceSynchronize());
+    QV_TRY_RC(align_ws(eng, c, &w));
+    hipStream_t stream = nullptr;
+    QV_TRY_RC(qv_stream_behind_batch(eng, c, &stream));
     hipLaunchKernelGGL(k_align_plan, dim3((batch + 63) / 64), dim3(64), 0, stream, eng->tab, c.work, batch, c.al_tmax, w->plan);
     return align_run(eng, *w, c.work.t_cap, c.al_lp, c.al_tmax, eng->tab.tok, batch, info_host, ids_host, first_host, last_host,
                      logp_host, pitch, stream);

@@ -14,10 +14,8 @@
 //                 ranks below W are the new best W.  No candidate count is too large: a frame just takes more chunks.
 // The frame row (1025 floats) is staged in LDS; the next row is requested before the current one is processed and stored
 // after it.  All score arithmetic is float64 in the order the header documents; frames t >= t_host[b] are never read.
-#include "qv_common.h"
+#include "qv_rows.h"
 #include "qv_trie_host.h"
-
-#include <string.h>
 
 namespace {
 
@@ -259,28 +257,6 @@ int qv_beam_trie(qv_engine *eng, int max_span, const QvTrie **out) {
     return QV_OK;
 }
 
-// The beam workspace of one context, allocated by the first call that uses it: per row of max_batch the frame count going up
-// and one record coming back (16 + 64 * 32 bytes), in device memory and in a pinned mirror.
-static int beam_ws(qv_engine *eng, QvCtx &c, QvBeamWs **out) {
-    QvBeamWs &w = c.beam;
-    *out = &w;
-    if (w.dev) return QV_OK;
-    const size_t B = (size_t)c.work.max_batch;
-    w.t_bytes = (B * sizeof(int32_t) + 15) & ~(size_t)15;
-    const size_t bytes = w.t_bytes + B * BM_ROW_BYTES;
-    void *d = nullptr, *h = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess || hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) {
-        if (d) (void)hipFree(d);
-        (void)hipGetLastError();
-        qv_set_error(eng, "beam workspace: out of memory");
-        return QV_ERR_HIP;
-    }
-    eng->allocs.push_back(d);   // freed by qv_destroy (the pinned mirror: with the context)
-    w.dev = (unsigned char *)d;
-    w.host = (unsigned char *)h;
-    return QV_OK;
-}
-
 int qv_beam_node_tokens(qv_engine *eng, int max_span, int node, int32_t *ids_out, int cap, int32_t *n_out) {
     const QvTrie *t = nullptr;
     int rc = qv_beam_trie(eng, max_span, &t);
@@ -293,30 +269,24 @@ int qv_beam_node_tokens(qv_engine *eng, int max_span, int node, int32_t *ids_out
     return QV_OK;
 }
 
-// frame counts up, kernel, one copy back, the records completed from the host trie; SYNCHRONOUS on `stream`
+// frame counts up, kernel, one copy back, the records completed from the host trie; SYNCHRONOUS on `stream`.  The workspace
+// of the context, allocated by the first call that uses it: per row of max_batch the frame count going up and one record
+// coming back (16 + 64 * 32 bytes).
 int qv_beam_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max, int max_span, int W, int k,
                  qv_beam_info *info_host, qv_beam_entry *entries_host, int32_t *ids_host, int pitch, hipStream_t stream) {
-    if (batch > c.work.max_batch) { qv_set_error(eng, "beam search: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
-    if (t_max > c.work.t_cap) { qv_set_error(eng, "beam search: t_max exceeds the engine's frame capacity"); return QV_ERR_CAPACITY; }
-    for (int b = 0; b < batch; ++b)
-        if (t_host[b] < 0 || t_host[b] > t_max) { qv_set_error(eng, "beam search: t_host[b] outside 0..t_max"); return QV_ERR_ARG; }
+    QV_TRY_RC(qv_rows_check(eng, "beam search", c, batch, t_max, t_host));
     const QvTrie *trie = nullptr;
-    int rc = qv_beam_trie(eng, max_span, &trie);
-    if (rc) return rc;
-    QvBeamWs *w = nullptr;
-    rc = beam_ws(eng, c, &w);
-    if (rc) return rc;
-    // (the previous call has finished with the mirror: beam calls are synchronous and serialised by the engine's lock)
-    memcpy(w->host, t_host, sizeof(int32_t) * batch);
-    QV_HIP(hipMemcpyAsync(w->dev, w->host, sizeof(int32_t) * batch, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(k_trie_beam, dim3(batch), dim3(BM_THREADS), 0, stream, lp, t_max, (const int32_t *)w->dev,
-                       (const QvTrieRec *)eng->beam->rec_dev, (uint32_t)trie->n_nodes(), W, w->dev + w->t_bytes);
+    QV_TRY_RC(qv_beam_trie(eng, max_span, &trie));
+    QvRowWs &w = c.beam;
+    QV_TRY_RC(qv_row_ws(eng, c, w, BM_ROW_BYTES, "beam workspace"));
+    QV_TRY_RC(qv_rows_send_t(eng, w, t_host, batch, stream));
+    hipLaunchKernelGGL(k_trie_beam, dim3(batch), dim3(BM_THREADS), 0, stream, lp, t_max, (const int32_t *)w.m.dev,
+                       (const QvTrieRec *)eng->beam->rec_dev, (uint32_t)trie->n_nodes(), W, w.m.dev + w.t_bytes);
     QV_HIP(hipGetLastError());
-    QV_HIP(hipMemcpyAsync(w->host + w->t_bytes, w->dev + w->t_bytes, BM_ROW_BYTES * batch, hipMemcpyDeviceToHost, stream));
-    QV_HIP(hipStreamSynchronize(stream));
+    QV_TRY_RC(qv_fetch_sync(eng, w.m.host + w.t_bytes, w.m.dev + w.t_bytes, BM_ROW_BYTES * batch, stream));
     std::vector<uint16_t> ids;
     for (int b = 0; b < batch; ++b) {
-        const unsigned char *rec = w->host + w->t_bytes + BM_ROW_BYTES * b;
+        const unsigned char *rec = w.m.host + w.t_bytes + BM_ROW_BYTES * b;
         qv_beam_info inf;
         memcpy(&inf, rec, sizeof inf);
         const BeamOut *o = (const BeamOut *)(rec + sizeof(qv_beam_info));

@@ -4,6 +4,7 @@
 #include "qv_kernels.h"
 #include "qv_layers.h"
 #include "qv_long_plan.h"
+#include "qv_rows.h"
 #include "qv_tables_host.h"
 #include "qv_trie_host.h"
 
@@ -352,7 +353,7 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
     // the CTC rerank keeps a candidate's 2L+1 <= T states in one wave's registers: T <= 768 frames.  The
     // reference has no such limit (c2c-direct/run.py:332 only asks 2L+1 <= T); refuse the capacity instead
     // of silently dropping long candidates.
-    if (qv_frames_for_samples(cfg->max_samples) + 2 > 768) {
+    if (qv_frames_for_samples(cfg->max_samples) + 2 > QV_MAX_T_CAP) {
         qv_set_error(eng, "max_samples above 976,000 (61 s) is not supported: the CTC rerank handles at most 768 encoder frames");
         return fail(QV_ERR_CAPACITY);
     }
@@ -425,11 +426,7 @@ extern "C" void qv_destroy(qv_engine *e) {
     qv_beam_free(e);
     for (QvCtx &c : e->ctx) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
-        if (c.align.out_host) (void)hipHostFree(c.align.out_host);
-        if (c.align.in_host) (void)hipHostFree(c.align.in_host);
-        if (c.nbest.out_host) (void)hipHostFree(c.nbest.out_host);
-        if (c.transcribe.host) (void)hipHostFree(c.transcribe.host);
-        if (c.beam.host) (void)hipHostFree(c.beam.host);
+        for (QvMirror &m : c.mirrors) qv_mirror_free(m);
         if (c.stream) (void)hipStreamDestroy(c.stream);
         if (c.in_ready) (void)hipEventDestroy(c.in_ready);
         if (c.done) (void)hipEventDestroy(c.done);
@@ -1101,7 +1098,7 @@ extern "C" int qv_transcribe_windows(qv_engine *eng, const float *logprobs_dev, 
 extern "C" int qv_long_kernel_times(qv_engine *eng, float *ms3_host) {
     QV_SERIALISE(eng);
     if (!eng || !ms3_host) return QV_ERR_ARG;
-    if (!eng->profile_stages || !eng->long_ws.dev) { qv_set_error(eng, "qv_long_kernel_times: no profiled long call (qv_profile_stages first)"); return QV_ERR_ARG; }
+    if (!eng->profile_stages || !eng->long_ws.m.dev) { qv_set_error(eng, "qv_long_kernel_times: no profiled long call (qv_profile_stages first)"); return QV_ERR_ARG; }
     memcpy(ms3_host, eng->long_ws.kernel_ms, sizeof(float) * 3);
     return QV_OK;
 }

@@ -179,6 +179,21 @@ struct QvTrack {
     qv_track_match *out; // [CAP]
 };
 
+// A device buffer and the pinned host buffer that mirrors its first host_bytes: what the row-wise features send their inputs
+// up and fetch their records back through in ONE copy (qv_rows.h: qv_mirror_alloc / qv_mirror_free and the helpers around
+// them).  A context's mirrors belong to QvCtx::mirrors; the engine-level one of the long transcription to QvLongWs.
+struct QvMirror {
+    unsigned char *dev, *host;
+    size_t dev_bytes, host_bytes;
+};
+// Per-context workspace of a feature that sends the rows' frame counts up and gets one record per row back (transcription,
+// beam search), allocated by the first call that uses it (m.dev == nullptr: not yet): the frame counts in the first t_bytes
+// of the mirror, the records of max_batch rows behind them.
+struct QvRowWs {
+    QvMirror m;
+    size_t t_bytes;
+};
+
 // forced alignment (qv_align.hip).  One row of the launch plan: which token list (offset into the token buffer the kernel
 // is given: the table's, or the staged explicit targets), how many tokens, how many frames.
 #define QV_ALIGN_PITCH 384   // entries per row of the device-side outputs (>= QV_ALIGN_MAX_TOKENS)
@@ -186,7 +201,8 @@ struct QvAlignRow { int32_t tok_off, L, T, flags, start, span; };
 // per-context alignment workspace, allocated by the first alignment call on that context (bp == nullptr: not yet).
 // Outputs are one record per row -- qv_align_info, then logp / first / last / ids with QV_ALIGN_PITCH entries each -- so a
 // batch comes back in ONE copy into a pinned buffer, from where the host scatters it into the caller's arrays; plan and
-// explicit targets travel the same way in the other direction.
+// explicit targets travel the same way in the other direction.  One mirror holds it all: out, plan and targets at the front
+// of the device buffer and in the pinned one, the back-pointers behind them on the device alone.
 #define QV_ALIGN_ROW_BYTES (sizeof(qv_align_info) + QV_ALIGN_PITCH * (sizeof(float) + 3 * sizeof(int16_t)))
 struct QvAlignWs {
     uint32_t *bp;            // [B][t_cap][64] back-pointers: two bits per state, a lane's NS states in one word
@@ -222,27 +238,14 @@ int qv_nbest_select_rows(qv_engine *eng, QvCtx &c, const double *final_host, con
                          int pitch, int k, int32_t *index_host, int32_t *count_host, hipStream_t stream);
 
 // transcription with confidence (qv_transcribe.hip).  One record per row -- qv_transcript_info, then ids / logp / first /
-// last with P = t_max rounded up to even entries each -- so a batch comes back in ONE copy into the pinned mirror.
-// Per-context workspace, allocated by the first transcription call on that context (dev == nullptr: not yet): the rows'
-// frame counts in the first t_bytes, the records behind them; `host` mirrors it.
-struct QvTranscribeWs {
-    unsigned char *dev;
-    unsigned char *host;
-    size_t t_bytes;
-};
+// last with P = t_max rounded up to even entries each -- so a batch comes back in ONE copy into the pinned mirror (QvRowWs).
 int qv_transcribe_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max,
                        qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host, int16_t *last_host,
                        int pitch, hipStream_t stream);
 
 // verse-constrained beam search (qv_beam.hip; the trie: qv_trie_host.h).  One record per row -- qv_beam_info, then QV_BEAM_MAX
-// (node, total, pb, pnb) entries -- so a batch comes back in ONE copy into the pinned mirror.  Per-context workspace, allocated
-// by the first beam call on that context (dev == nullptr: not yet): the rows' frame counts in the first t_bytes, the records
-// behind them.  The trie of the span last asked for belongs to the engine (QvBeamState, nullptr until a call needs it).
-struct QvBeamWs {
-    unsigned char *dev;
-    unsigned char *host;
-    size_t t_bytes;
-};
+// (node, total, pb, pnb) entries -- so a batch comes back in ONE copy into the pinned mirror (QvRowWs).  The trie of the span
+// last asked for belongs to the engine (QvBeamState, nullptr until a call needs it).
 struct QvBeamState;
 struct QvTrie;
 void qv_beam_free(qv_engine *eng);
@@ -252,13 +255,13 @@ int qv_beam_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_hos
                  qv_beam_info *info_host, qv_beam_entry *entries_host, int32_t *ids_host, int pitch, hipStream_t stream);
 
 // recordings of any length (qv_long.hip; the cutting rule: qv_long_plan.h).  One workspace per engine, allocated or grown by
-// the first call that needs it and freed by qv_destroy: `dev` holds the plan tables (tab_bytes, rec_bytes), the records
-// (out_bytes), then fid (fid_bytes) and m; `host` mirrors tables and records in pinned memory; `batch` is the
-// [max_batch, window_samples] batch the windows of a round are gathered into (engines with a model).
+// the first call that needs it and freed by qv_destroy: the mirror's device buffer holds the plan tables (tab_bytes,
+// rec_bytes), the records (out_bytes), then fid (fid_bytes) and m; its pinned buffer mirrors tables and records; `batch` is
+// the [max_batch, window_samples] batch the windows of a round are gathered into (engines with a model).
 struct QvLongWs {
-    unsigned char *dev, *host;
+    QvMirror m;
     float *batch;
-    size_t dev_cap, host_cap, batch_cap;   // bytes, bytes, floats
+    size_t batch_cap;   // floats
     size_t tab_bytes, rec_bytes, out_bytes, fid_bytes;
     float kernel_ms[3];   // qv_profile_stages: the last call's time in k_long_gather, k_long_frames, k_long_collapse
 };
@@ -346,13 +349,17 @@ struct QvCtx {
     const float *al_lp = nullptr;
     int al_tmax = 0, al_batch = 0;
     hipStream_t al_stream = nullptr;
+    // The mirrors of this context's lazily allocated feature workspaces.  This list OWNS them, both halves: qv_ctx_mirror
+    // (qv_rows.h) appends, one loop in qv_destroy frees through qv_mirror_free; nothing of a mirror is in qv_engine::allocs.
+    // The pointers the workspaces below keep into them are views.
+    std::vector<QvMirror> mirrors;
     QvAlignWs align = {};
     // ranked alternatives (qv_nbest_results_ctx): the same batch, read from the candidate arrays of `work`
     QvNbestWs nbest = {};
     // transcription with confidence (qv_transcribe, qv_transcribe_batch): independent of the batch state above
-    QvTranscribeWs transcribe = {};
+    QvRowWs transcribe = {};
     // verse-constrained beam search (qv_beam_decode, qv_beam_batch): independent of the batch state as well
-    QvBeamWs beam = {};
+    QvRowWs beam = {};
 };
 
 struct qv_engine {

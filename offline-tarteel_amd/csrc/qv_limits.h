@@ -12,6 +12,12 @@
 #define QV_MAX_SPAN 6
 #define QV_MAX_VW 11        // ceil(684 / 64): words of the longest verse text
 
+// Frames of one utterance: qv_create refuses an engine whose frame capacity (t_cap: the frames of max_samples, + 2) is above
+// QV_MAX_T_CAP, and the per-frame arrays the greedy kernels keep in LDS (k_decode, k_transcribe) hold QV_FRAME_CAP entries.
+#define QV_MAX_T_CAP 768
+#define QV_FRAME_CAP 770
+static_assert(QV_FRAME_CAP >= QV_MAX_T_CAP, "the LDS frame arrays hold the frames of the largest engine");
+
 // FastConformer-CTC dimensions
 #define QV_D 512
 #define QV_H 8

@@ -5,20 +5,17 @@
 // windows into the context's log-prob workspace; of every window only the frames it OWNS are looked at again:
 //   k_long_gather    the windows of one round out of the caller's [R, pitch] audio into a [round, window_samples] batch,
 //                    zero-filled behind a short last window (16-byte loads and stores; HBM-bound);
-//   k_long_frames    one wave per owned frame: k_transcribe's argmax loop, instruction for instruction; fid / m go to the
+//   k_long_frames    one wave per owned frame: frame_argmax (qv_greedy.h), as k_transcribe; fid / m go to the
 //                    frame's GLOBAL index in per-recording arrays in HBM (before the next round reuses the workspace);
 //   k_long_collapse  once per call, one workgroup per recording: runs of equal fid over [0, T), seams included, one token per
-//                    non-blank run, the sums in the header's order.  Sixteen waves take a slab each; a wave first reduces
+//                    non-blank run (run_collapse, qv_greedy.h), the sums in the header's order.  Sixteen waves take a slab each; a wave first reduces
 //                    its slab to (latest run start, running maximum, token count, blank count), then scans it again with what
 //                    the slabs before it carry in.  The run operator is associative: no bit depends on the partition.
-#include "qv_common.h"
+#include "qv_greedy.h"
 #include "qv_long_plan.h"
-
-#include <string.h>
+#include "qv_rows.h"
 
 #include <algorithm>
-
-#define QV_TRY_RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 static_assert(QV_LONG_FRAME_CAP == QV_LONG_MAX_FRAMES, "qv_long_plan.h and qverse.h disagree");
 static_assert(sizeof(qv_long_info) == 48, "record layout");
@@ -64,89 +61,26 @@ __global__ __launch_bounds__(64 * LF_WAVES) void k_long_frames(const float *__re
     const LongWin w = tab[blockIdx.y];
     const int lane = threadIdx.x & 63, f = blockIdx.x * LF_WAVES + (threadIdx.x >> 6);
     if (f >= w.count) return;
-    // the 17 loads of a row are all requested before the first comparison
-    const float *row = lp + ((size_t)w.lp_win * t_max + (w.j0 + f)) * QV_VOCAB;
-    float x[17];
-#pragma unroll
-    for (int i = 0; i < 17; ++i) x[i] = lane + 64 * i < QV_VOCAB ? row[lane + 64 * i] : -INFINITY;
-    float best = x[0];
-    int bi = lane;
-#pragma unroll
-    for (int i = 1; i < 17; ++i)
-        if (x[i] > best) { best = x[i]; bi = lane + 64 * i; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        float b2 = __shfl_xor(best, o);
-        int i2 = __shfl_xor(bi, o);
-        if (b2 > best || (b2 == best && i2 < bi)) { best = b2; bi = i2; }
-    }
+    float best;
+    int bi;
+    frame_argmax(lp + ((size_t)w.lp_win * t_max + (w.j0 + f)) * QV_VOCAB, lane, best, bi);
     if (lane == 0) { fid[w.dst + f] = (int16_t)bi; m[w.dst + f] = best; }
 }
 
 #define LC_WAVES 16
 
-// k_transcribe's chunk loop over the frames [base0, base1) of one recording, entered with the run that reaches into the
-// slab (c_first: its first frame, -1 = none known; c_max: its maximum so far) and the tokens started before it (n_tok).
-template <bool EMIT>
-__device__ __forceinline__ void lc_scan(const int16_t *fid, const float *m, int T, int base0, int base1, int lane, int &n_tok,
-                                        int &n_blank, int &c_first, float &c_max, int32_t *o_ids, float *o_logp, int32_t *o_first,
-                                        int32_t *o_last) {
-    for (int base = base0; base < base1; base += 64) {
-        const int t = base + lane;
-        const bool valid = t < T;
-        const int id = valid ? (int)fid[t] : -2;
-        const int prev = valid && t > 0 ? (int)fid[t - 1] : -3;
-        const int next = t + 1 < T ? (int)fid[t + 1] : -1;
-        const bool start = valid && id != prev, end = valid && id != next;
-        // inclusive segmented scan over the lanes (k_transcribe): f = the latest run start at or before this frame, mx = the
-        // FIRST maximum of m over the frames of that run seen so far
-        int f = start ? t : -1;
-        float mx = valid ? m[t] : -INFINITY;
-        bool fl = start;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int f2 = __shfl_up(f, o);
-            const float m2 = __shfl_up(mx, o);
-            const int fl2 = __shfl_up((int)fl, o);
-            if (lane >= o) {
-                f = f2 > f ? f2 : f;
-                if (!fl) mx = mx > m2 ? mx : m2;
-                fl = fl || fl2 != 0;
-            }
-        }
-        if (!fl) { f = c_first; mx = mx > c_max ? mx : c_max; }
-        const bool blank = id == QV_BLANK;
-        const unsigned long long ks = __ballot(start && !blank);
-        n_blank += __popcll(__ballot(valid && blank));
-        if (EMIT && end && !blank) {
-            const int k = n_tok + __popcll(ks & (~0ull >> (63 - lane))) - 1;   // starts at or before this lane
-            o_ids[k] = id;
-            o_first[k] = f;
-            o_last[k] = t;
-            o_logp[k] = mx;
-        }
-        n_tok += __popcll(ks);
-        c_first = __shfl(f, 63);
-        c_max = __shfl(mx, 63);
+// a token of run_collapse into the recording's record in HBM (int32 positions)
+struct LongSink {
+    int32_t *ids;
+    float *logp;
+    int32_t *first, *last;
+    __device__ __forceinline__ void operator()(int k, int id, int f, int t, float mx) const {
+        ids[k] = id;
+        first[k] = f;
+        last[k] = t;
+        logp[k] = mx;
     }
-}
-
-// the header's sum of x[0 .. n): lane l adds x[l], x[l + 64], ... ascending from +0.0, then p[l] += p[l ^ o], o = 32 .. 1.
-// The additions of a lane are one dependent chain; eight loads are requested ahead of it.
-__device__ __forceinline__ double lc_sum(const float *x, int n, int lane) {
-    double p = 0.0;
-    for (int i = lane; i < n; i += 64 * 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = i + 64 * u < n ? x[i + 64 * u] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (i + 64 * u < n) p = __dadd_rn(p, (double)v[u]);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) p = __dadd_rn(p, __shfl_xor(p, o));
-    return p;
-}
+};
 
 // record of recording r: qv_long_info, then ids i32[P], logp f32[P], first i32[P], last i32[P]
 __global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *__restrict__ fid_all, const float *__restrict__ m_all,
@@ -171,7 +105,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *
     {   // pass 1: the slab on its own
         int n_tok = 0, n_blank = 0, c_first = -1;
         float c_max = -INFINITY;
-        lc_scan<false>(fid, m, T, base0, base1, lane, n_tok, n_blank, c_first, c_max, nullptr, nullptr, nullptr, nullptr);
+        run_collapse<false>(fid, m, T, base0, base1, lane, n_tok, n_blank, c_first, c_max, LongSink{});
         if (lane == 0) { s_first[wave] = c_first; s_max[wave] = c_max; s_ntok[wave] = n_tok; s_nblank[wave] = n_blank; }
     }
     __syncthreads();
@@ -183,7 +117,7 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *
         if (s_first[s] >= 0) { c_first = s_first[s]; c_max = s_max[s]; }
         else c_max = s_max[s] > c_max ? s_max[s] : c_max;      // the later slab replaces only when strictly greater
     }
-    lc_scan<true>(fid, m, T, base0, base1, lane, n_tok, n_blank, c_first, c_max, o_ids, o_logp, o_first, o_last);
+    run_collapse<true>(fid, m, T, base0, base1, lane, n_tok, n_blank, c_first, c_max, LongSink{o_ids, o_logp, o_first, o_last});
     int tok_all = 0, blank_all = 0;
     for (int s = 0; s < LC_WAVES; ++s) { tok_all += s_ntok[s]; blank_all += s_nblank[s]; }
     for (int i = tok_all + tid; i < P; i += 64 * LC_WAVES) { o_ids[i] = -1; o_first[i] = -1; o_last[i] = -1; o_logp[i] = 0.f; }
@@ -193,25 +127,13 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (wave == 0) {
-        const double s = lc_sum(m, T, lane);
+        const double s = lane_sum(m, T, lane);
         if (lane == 0) s_sum[0] = s;
     } else if (wave == 1) {
-        const double s = lc_sum(o_logp, tok_all, lane);
+        const double s = lane_sum(o_logp, tok_all, lane);
         if (lane == 0) s_sum[1] = s;
     } else if (wave == 2) {
-        // the first minimum over the tokens (value, then index: -0.0 and +0.0 compare equal, the earlier token is reported)
-        float mn = 0.f;
-        int mi = 0x7fffffff;
-        for (int i = lane; i < tok_all; i += 64) {
-            const float v = o_logp[i];
-            if (mi == 0x7fffffff || v < mn) { mn = v; mi = i; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float v2 = __shfl_xor(mn, o);
-            const int i2 = __shfl_xor(mi, o);
-            if (i2 != 0x7fffffff && (mi == 0x7fffffff || v2 < mn || (v2 == mn && i2 < mi))) { mn = v2; mi = i2; }
-        }
+        const float mn = wave_first_min(o_logp, tok_all, lane);
         if (lane == 0) s_min = mn;
     }
     __syncthreads();
@@ -230,8 +152,6 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *
         *(qv_long_info *)rec = inf;
     }
 }
-
-size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // qv_profile_stages: HIP events around every launch of the three kernels, summed per kernel after the call's synchronisation
 struct LongTimer {
@@ -263,8 +183,7 @@ struct LongTimer {
 }  // namespace
 
 void qv_long_free(QvLongWs &w) {
-    if (w.dev) (void)hipFree(w.dev);
-    if (w.host) (void)hipHostFree(w.host);
+    qv_mirror_free(w.m);
     if (w.batch) (void)hipFree(w.batch);
     w = {};
 }
@@ -273,25 +192,14 @@ void qv_long_free(QvLongWs &w) {
 // recordings), per recording fid / m and one record coming back, in device memory; the tables and the records once more in a
 // pinned mirror; with a model, the [max_batch, window_samples] batch the windows of a round are gathered into.
 static int long_ws(qv_engine *eng, QvLongWs &w, size_t n_win, int rows, int P, size_t batch_floats) {
-    const size_t tab = up16(n_win * sizeof(LongWin)), recs = up16((size_t)rows * sizeof(LongRec));
+    const size_t tab = qv_up16(n_win * sizeof(LongWin)), recs = qv_up16((size_t)rows * sizeof(LongRec));
     const size_t out = (size_t)rows * (sizeof(qv_long_info) + (size_t)P * 16);
-    const size_t fid = up16((size_t)rows * P * sizeof(int16_t)), m = up16((size_t)rows * P * sizeof(float));
+    const size_t fid = qv_up16((size_t)rows * P * sizeof(int16_t)), m = qv_up16((size_t)rows * P * sizeof(float));
     const size_t dev_bytes = tab + recs + out + fid + m, host_bytes = tab + recs + out;
     w.tab_bytes = tab; w.rec_bytes = recs; w.out_bytes = out; w.fid_bytes = fid;
-    if (dev_bytes > w.dev_cap || host_bytes > w.host_cap) {
-        if (w.dev) (void)hipFree(w.dev);
-        if (w.host) (void)hipHostFree(w.host);
-        w.dev = w.host = nullptr;
-        w.dev_cap = w.host_cap = 0;
-        void *d = nullptr, *h = nullptr;
-        if (hipMalloc(&d, dev_bytes) != hipSuccess || hipHostMalloc(&h, host_bytes, hipHostMallocDefault) != hipSuccess) {
-            if (d) (void)hipFree(d);
-            (void)hipGetLastError();
-            qv_set_error(eng, "long transcription workspace: out of memory");
-            return QV_ERR_HIP;
-        }
-        w.dev = (unsigned char *)d; w.host = (unsigned char *)h;
-        w.dev_cap = dev_bytes; w.host_cap = host_bytes;
+    if (dev_bytes > w.m.dev_bytes || host_bytes > w.m.host_bytes) {
+        qv_mirror_free(w.m);
+        QV_TRY_RC(qv_mirror_alloc(eng, w.m, dev_bytes, host_bytes, "long transcription workspace"));
     }
     if (batch_floats > w.batch_cap) {
         if (w.batch) (void)hipFree(w.batch);
@@ -332,11 +240,11 @@ int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitc
     const int P = (t_top + 3) & ~3;
     QvLongWs &w = eng->long_ws;
     QV_TRY_RC(long_ws(eng, w, n_win, rows, P, audio ? (size_t)max_batch * wn : 0));
-    LongWin *tab_h = (LongWin *)w.host;
-    LongRec *rec_h = (LongRec *)(w.host + w.tab_bytes);
-    const LongWin *tab_d = (const LongWin *)w.dev;
-    const LongRec *rec_d = (const LongRec *)(w.dev + w.tab_bytes);
-    unsigned char *out_d = w.dev + w.tab_bytes + w.rec_bytes, *out_h = w.host + w.tab_bytes + w.rec_bytes;
+    LongWin *tab_h = (LongWin *)w.m.host;
+    LongRec *rec_h = (LongRec *)(w.m.host + w.tab_bytes);
+    const LongWin *tab_d = (const LongWin *)w.m.dev;
+    const LongRec *rec_d = (const LongRec *)(w.m.dev + w.tab_bytes);
+    unsigned char *out_d = w.m.dev + w.tab_bytes + w.rec_bytes, *out_h = w.m.host + w.tab_bytes + w.rec_bytes;
     int16_t *fid_d = (int16_t *)(out_d + w.out_bytes);
     float *m_d = (float *)((unsigned char *)fid_d + w.fid_bytes);
 
@@ -359,7 +267,7 @@ int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitc
             if (audio) fwd_len[k] = qv_long_fwd_len(p, v);
         }
     }
-    QV_HIP(hipMemcpyAsync(w.dev, w.host, w.tab_bytes + w.rec_bytes, hipMemcpyHostToDevice, stream));
+    QV_HIP(hipMemcpyAsync(w.m.dev, w.m.host, w.tab_bytes + w.rec_bytes, hipMemcpyHostToDevice, stream));
     LongTimer tm = {eng->profile_stages, stream, {}};
     const int most_owned = kw + 1;   // grid of k_long_frames: a wave whose frame its window does not own leaves at once
     if (audio) {
@@ -396,8 +304,7 @@ int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitc
     hipLaunchKernelGGL(k_long_collapse, dim3(rows), dim3(64 * LC_WAVES), 0, stream, (const int16_t *)fid_d, (const float *)m_d, rec_d, out_d, P);
     QV_HIP(hipGetLastError());
     tm.mark(2);
-    QV_HIP(hipMemcpyAsync(out_h, out_d, w.out_bytes, hipMemcpyDeviceToHost, stream));
-    QV_HIP(hipStreamSynchronize(stream));
+    QV_TRY_RC(qv_fetch_sync(eng, out_h, out_d, w.out_bytes, stream));
     tm.finish(w.kernel_ms);
     const size_t row = sizeof(qv_long_info) + (size_t)P * 16;
     for (int r = 0; r < rows; ++r) {
@@ -405,18 +312,11 @@ int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitc
         const int32_t *r_ids = (const int32_t *)(rec + sizeof(qv_long_info));
         const float *r_logp = (const float *)(r_ids + P);
         const int32_t *r_first = (const int32_t *)(r_logp + P), *r_last = r_first + P;
-        const size_t o = (size_t)r * pitch;
         memcpy(&info_host[r], rec, sizeof(qv_long_info));
-        memcpy(ids_host + o, r_ids, sizeof(int32_t) * t_top);
-        if (logp_host) memcpy(logp_host + o, r_logp, sizeof(float) * t_top);
-        if (first_host) memcpy(first_host + o, r_first, sizeof(int32_t) * t_top);
-        if (last_host) memcpy(last_host + o, r_last, sizeof(int32_t) * t_top);
-        for (int i = t_top; i < pitch; ++i) {
-            ids_host[o + i] = -1;
-            if (logp_host) logp_host[o + i] = 0.f;
-            if (first_host) first_host[o + i] = -1;
-            if (last_host) last_host[o + i] = -1;
-        }
+        scatter_column(ids_host, pitch, r, r_ids, t_top, (int32_t)-1);
+        scatter_column(logp_host, pitch, r, r_logp, t_top, 0.f);
+        scatter_column(first_host, pitch, r, r_first, t_top, (int32_t)-1);
+        scatter_column(last_host, pitch, r, r_last, t_top, (int32_t)-1);
     }
     return QV_OK;
 }

@@ -2,15 +2,15 @@
 // (include/qverse.h: qv_nbest_results_ctx, qv_nbest_select).
 //
 // The rerank's ranked list is `sorted(finite-loss candidates, key=final_score, reverse=True)` (c2c-direct/run.py:378-379):
-// a stable descending sort, i.e. the order (final desc, candidate index asc) under IEEE > / == on doubles -- better() of
-// qv_postlogits.hip, which k_result takes the first maximum with.  k_nbest takes the first k of that order: one
+// a stable descending sort, i.e. the order (final desc, candidate index asc) under IEEE > / == on doubles -- better()
+// (qv_greedy.h), which k_result takes the first maximum with.  k_nbest takes the first k of that order: one
 // workgroup per utterance, candidate c = tid + 256 j held in a register of thread tid (QV_CAND_CAP / 256 = 8 doubles),
 // every thread's best cached; a round is one wave reduction + one four-entry LDS exchange, after which only the thread
 // that owned the winner rescans its eight registers (the scheme of local_best / k_topk).  k rounds, no LDS copy of the
 // candidate arrays, no bit-pattern keys (so -0.0 and +0.0 tie as they do in Python).
 #include "qv_common.h"
-
-#include <string.h>
+#include "qv_greedy.h"
+#include "qv_rows.h"
 
 namespace {
 
@@ -25,10 +25,6 @@ struct NbShared {
     int32_t cnt[4];
     int32_t idx[QV_NBEST_MAX];
 };
-
-__device__ __forceinline__ bool nb_better(double s, uint32_t k, double s2, uint32_t k2) {
-    return s > s2 || (s == s2 && k < k2);
-}
 
 // Leaves the indices of the stable top k of fin[0 .. n) among the entries with a finite loss in sh.idx and returns how
 // many there are (the same value in every thread); *n_ranked = number of finite-loss entries.  n <= QV_CAND_CAP.
@@ -55,7 +51,7 @@ __device__ int nbest_select_block(const double *__restrict__ fin, const float *_
 #pragma unroll
         for (int j = 0; j < NB_PER; ++j) {
             const uint32_t c = (uint32_t)(tid + j * NB_THREADS);
-            if ((live >> j & 1u) && nb_better(v[j], c, ls, lk)) { ls = v[j]; lk = c; }
+            if ((live >> j & 1u) && better(v[j], c, ls, lk)) { ls = v[j]; lk = c; }
         }
     };
     rescan();
@@ -67,7 +63,7 @@ __device__ int nbest_select_block(const double *__restrict__ fin, const float *_
         for (int o = 32; o > 0; o >>= 1) {
             const double s2 = __shfl_xor(s, o);
             const uint32_t k2 = __shfl_xor(key, o);
-            if (nb_better(s2, k2, s, key)) { s = s2; key = k2; }
+            if (better(s2, k2, s, key)) { s = s2; key = k2; }
         }
         double *ps = sh.s[r & 1];
         uint32_t *pk = sh.k[r & 1];
@@ -77,7 +73,7 @@ __device__ int nbest_select_block(const double *__restrict__ fin, const float *_
         key = pk[0];
 #pragma unroll
         for (int w = 1; w < 4; ++w)
-            if (nb_better(ps[w], pk[w], s, key)) { s = ps[w]; key = pk[w]; }
+            if (better(ps[w], pk[w], s, key)) { s = ps[w]; key = pk[w]; }
         if (key == NB_NONE) break;   // (the same LDS values in every thread: the exit is uniform)
         if (tid == 0) sh.idx[r] = (int32_t)key;
         if ((int)(key & (NB_THREADS - 1)) == tid) {
@@ -198,16 +194,10 @@ static int nbest_ws(qv_engine *eng, QvCtx &c, QvNbestWs **out) {
     *out = &w;
     if (w.out) return QV_OK;
     const size_t n_out = (size_t)c.work.max_batch * QV_NBEST_ROW_BYTES;
-    void *o = nullptr, *oh = nullptr;
-    if (hipMalloc(&o, n_out) != hipSuccess || hipHostMalloc(&oh, n_out, hipHostMallocDefault) != hipSuccess) {
-        if (o) (void)hipFree(o);
-        (void)hipGetLastError();
-        qv_set_error(eng, "n-best workspace: out of memory");
-        return QV_ERR_HIP;
-    }
-    eng->allocs.push_back(o);   // freed by qv_destroy (the pinned mirror: with the context)
-    w.out = (unsigned char *)o;
-    w.out_host = (unsigned char *)oh;
+    QvMirror m;
+    QV_TRY_RC(qv_ctx_mirror(eng, c, n_out, n_out, "n-best workspace", &m));
+    w.out = m.dev;
+    w.out_host = m.host;
     return QV_OK;
 }
 
@@ -218,16 +208,12 @@ int qv_nbest_results(qv_engine *eng, int k_ctx, int batch, int k, int flags, qv_
         return QV_ERR_ARG;
     }
     QvNbestWs *w = nullptr;
-    int rc = nbest_ws(eng, c, &w);
-    if (rc) return rc;
-    // ordered behind the batch as qv_align_results_ctx is: on the context's own stream when the batch ran there, else
-    // after a device-wide join (the batch ran on a caller stream we were not given)
-    hipStream_t stream = eng->n_ctx > 1 ? c.stream : nullptr;
-    if (eng->n_ctx == 1 || c.al_stream != c.stream) QV_HIP(hipDeviceSynchronize());
+    QV_TRY_RC(nbest_ws(eng, c, &w));
+    hipStream_t stream = nullptr;
+    QV_TRY_RC(qv_stream_behind_batch(eng, c, &stream));
     hipLaunchKernelGGL(k_nbest, dim3(batch), dim3(NB_THREADS), 0, stream, eng->tab, c.work, k, flags, w->out);
     QV_HIP(hipGetLastError());
-    QV_HIP(hipMemcpyAsync(w->out_host, w->out, (size_t)batch * QV_NBEST_ROW_BYTES, hipMemcpyDeviceToHost, stream));
-    QV_HIP(hipStreamSynchronize(stream));
+    QV_TRY_RC(qv_fetch_sync(eng, w->out_host, w->out, (size_t)batch * QV_NBEST_ROW_BYTES, stream));
     for (int b = 0; b < batch; ++b) {
         const unsigned char *rec = w->out_host + (size_t)b * QV_NBEST_ROW_BYTES;
         memcpy(&info_host[b], rec, sizeof(qv_nbest_info));
@@ -239,8 +225,7 @@ int qv_nbest_results(qv_engine *eng, int k_ctx, int batch, int k, int flags, qv_
 int qv_nbest_select_rows(qv_engine *eng, QvCtx &c, const double *final_host, const float *loss_host, const int32_t *n_host, int rows,
                          int pitch, int k, int32_t *index_host, int32_t *count_host, hipStream_t stream) {
     QvNbestWs *w = nullptr;
-    int rc = nbest_ws(eng, c, &w);
-    if (rc) return rc;
+    QV_TRY_RC(nbest_ws(eng, c, &w));
     const size_t B = (size_t)c.work.max_batch;
     if (!w->sel_final) {
         void *p = nullptr;
@@ -261,8 +246,7 @@ int qv_nbest_select_rows(qv_engine *eng, QvCtx &c, const double *final_host, con
     QV_HIP(hipMemcpyAsync(w->sel_n, n_host, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_nbest_select, dim3(rows), dim3(NB_THREADS), 0, stream, w->sel_final, w->sel_loss, w->sel_n, pitch, k, w->sel_idx);
     QV_HIP(hipGetLastError());
-    QV_HIP(hipMemcpyAsync(w->out_host, w->sel_idx, (size_t)rows * QV_NBEST_SEL_PITCH * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    QV_HIP(hipStreamSynchronize(stream));
+    QV_TRY_RC(qv_fetch_sync(eng, w->out_host, w->sel_idx, (size_t)rows * QV_NBEST_SEL_PITCH * sizeof(int32_t), stream));
     const int32_t *got = (const int32_t *)w->out_host;
     for (int r = 0; r < rows; ++r) {
         count_host[r] = got[(size_t)r * QV_NBEST_SEL_PITCH];

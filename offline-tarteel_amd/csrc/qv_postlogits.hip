@@ -17,6 +17,7 @@
 
 #include "qv_common.h"
 #include "qv_graph.h"
+#include "qv_greedy.h"
 #include "qv_kernels.h"
 
 #include <math.h>
@@ -58,11 +59,7 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     return v;
 }
 
-// (score desc, key asc) ordering used by every stable "sorted(..., reverse=True)" emulation
-__device__ __forceinline__ bool better(double s, unsigned long long k, double s2, unsigned long long k2) {
-    return s > s2 || (s == s2 && k < k2);
-}
-
+// (better(): the (score desc, key asc) ordering of every stable "sorted(..., reverse=True)" emulation -- qv_greedy.h)
 __device__ __forceinline__ void wave_best(double &s, unsigned long long &k) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -390,44 +387,23 @@ __device__ __forceinline__ void load_pm_lds(uint64_t *spm, const uint64_t *gpm) 
 //   wave 0 alone:   CTC collapse, piece expansion into normalised codes, whitespace collapse + strip, spaceless copy,
 //                   match masks (c2c-direct/run.py:187-204, shared/normalizer.py) -- a serial, 64-lane job.
 // Within that single wave the LDS / global hand-offs between lanes only need the wave's own memory operations to have
-// completed (QV_WSYNC: workgroup-scope release / acquire fences around a wave barrier), not a block barrier.
-#define QV_WSYNC()                                                  \
-    do {                                                            \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      \
-        __builtin_amdgcn_wave_barrier();                            \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      \
-    } while (0)
-#define QV_TCAP 770   // >= t_cap of any engine (qv_create refuses more than 768 + 2 frames)
-
+// completed (QV_WSYNC, qv_greedy.h), not a block barrier.
 #define DEC_WAVES 16
 __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode(QvTables tab, QvWork wk, const float *__restrict__ lp, int t_max,
                                                           const int32_t *__restrict__ t_dev) {
     __shared__ uint8_t raw[QV_RAW_CAP];
     __shared__ unsigned long long pm[2][QV_NSYM][QV_MAXW];
-    __shared__ int16_t s_fid[QV_TCAP];
-    __shared__ int32_t s_tok[QV_TCAP];
+    __shared__ int16_t s_fid[QV_FRAME_CAP];
+    __shared__ int32_t s_tok[QV_FRAME_CAP];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (b == 0 && tid == 0) { *wk.n_fail = 0; wk.frag_ctr[0] = 0; wk.frag_ctr[1] = 0; wk.frag_ctr[2] = 0; }
     QvUtt &u = wk.utt[b];
     const int T = t_dev[b];
-    // a wave takes every 16th frame; the 17 loads of a row are all requested before the first comparison (a frame's
-    // argmax is one memory latency, not seventeen)
+    // a wave takes every 16th frame
     for (int t = wave; t < T; t += DEC_WAVES) {
-        const float *row = lp + ((size_t)b * t_max + t) * QV_VOCAB;
-        float x[17];
-#pragma unroll
-        for (int i = 0; i < 17; ++i) x[i] = lane + 64 * i < QV_VOCAB ? row[lane + 64 * i] : -INFINITY;
-        float best = x[0];
-        int bi = lane;
-#pragma unroll
-        for (int i = 1; i < 17; ++i)
-            if (x[i] > best) { best = x[i]; bi = lane + 64 * i; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            float b2 = __shfl_xor(best, o);
-            int i2 = __shfl_xor(bi, o);
-            if (b2 > best || (b2 == best && i2 < bi)) { best = b2; bi = i2; }
-        }
+        float best;
+        int bi;
+        frame_argmax(lp + ((size_t)b * t_max + t) * QV_VOCAB, lane, best, bi);
         if (lane == 0) s_fid[t] = (int16_t)bi;
     }
     __syncthreads();
