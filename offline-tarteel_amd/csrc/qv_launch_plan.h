@@ -1,6 +1,6 @@
 // qv_launch_plan.h -- which kernel a launch gets and how long its blocks' runs are: pure integer functions of the launch
-// shape and a snapshot of the switches (qv_switches.h).  No HIP here: the launchers (qv_gemm.hip, qv_layers.hip) turn a plan
-// into launches, tools/launch_plan_check.cpp runs the plans on a CPU.
+// shape and a snapshot of the switches (qv_switches.h).  No HIP here: the launchers (qv_gemm.hip, qv_layers.hip,
+// qv_attention.hip) turn a plan into launches, tools/launch_plan_check.cpp runs the plans on a CPU.
 #pragma once
 
 #include "qv_limits.h"     // SUB_TT, SUB_RES_RUN, SUB_MAX_RUN, S35_TC, S35_MAX_RUN, ATT_SHORT_T

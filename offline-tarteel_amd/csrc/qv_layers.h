@@ -1,4 +1,4 @@
-// qv_layers.h -- launchers of the non-GEMM kernels (qv_layers.hip).
+// qv_layers.h -- launchers of the non-GEMM kernels (qv_layers.hip, qv_attention.hip).
 #pragma once
 
 #include "qv_kernels.h"

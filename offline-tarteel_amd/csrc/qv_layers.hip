@@ -1,13 +1,8 @@
 // qv_layers.hip -- non-GEMM kernels of the FastConformer forward: log-mel front-end, strided
-// conv subsampling, LayerNorm, rel-pos attention, depthwise conv, log-softmax.
-//
-// All of them are HBM/LDS-bound elementwise or small-reduction kernels except the attention,
-// which runs QK^T, the rel-pos term and PV on v_mfma_f32_32x32x16_f16 with operands read
-// straight from HBM/L2 in fragment order (K-contiguous 16-B loads; V is produced already
-// transposed by the QKV GEMM epilogue so that PV's B operand is K-contiguous too).
+// conv subsampling, LayerNorm, depthwise conv, log-softmax, resampler.  All of them are HBM/LDS-bound
+// elementwise or small-reduction kernels; the rel-pos attention is qv_attention.hip.
 
 #include "qv_layers.h"
-#include <type_traits>
 
 #include "qv_dev_util.h"
 #include "qv_launch_plan.h"
@@ -844,850 +839,6 @@ __global__ void k_to_float(const half_t *__restrict__ x, float *__restrict__ y, 
     if (i < n) y[i] = (float)x[i];
 }
 
-// ------------------------------------------------------------------ attention ----------
-// RelPositionMultiHeadAttention core for one (utterance, head): flash-style online softmax over
-// 32-key tiles, one wave per 32-query tile, everything on v_mfma_f32_32x32x16_f16.
-//   AC[i,j]  = (q_i + u) . k_j
-//   BD[i,j]  = (q_i + v) . p_{T-1-i+j}          (rel_shift of the [T, 2T-1] product)
-//   out      = softmax((AC + BD) / 8, keys < len) V
-// All products are computed TRANSPOSED (keys / positions / head-dim on the MFMA row axis, queries
-// on the column axis), so a lane owns ONE query: its 16 accumulator registers are 16 keys of that
-// query, the softmax reductions are in-register plus one cross-half shuffle, the running max / sum
-// are per-lane scalars, and exp(S^T) is already in the B-operand layout of the P.V product (the
-// contraction index is permuted identically on the V side, which only changes which 8-byte pieces
-// of V^T a lane loads).  The rel-pos term needs raw[c = 31 - i + j]: the two raw tiles go through
-// a per-wave LDS slab (row = query, odd stride) and come back skewed.
-#define ATT_LDS_LD 67  // floats per query row of the skew slab (odd: conflict-free skewed reads)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_attention(const half_t *__restrict__ qk, const half_t *__restrict__ vt,
-                                                   const half_t *__restrict__ pos, int pos_ld, const float *__restrict__ bias_u,
-                                                   const float *__restrict__ bias_v, const int32_t *__restrict__ len,
-                                                   const int32_t *__restrict__ row_off, half_t *__restrict__ out, int t_max,
-                                                   int t_pad) {
-    __shared__ float slab[4][32 * ATT_LDS_LD];
-    const int b = blockIdx.y, h = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int T = len[b];
-    const size_t row0 = (size_t)row_off[b];   // activations are packed: utterance b owns rows [row0, row0 + T)
-    const int l31 = lane & 31, hi = lane >> 5;
-    const half_t *qb = qk + row0 * (2 * QV_D) + h * QV_DK;                           // q row stride 1024
-    const half_t *kb = qb + QV_D;
-    const half_t *vb = vt + ((size_t)b * QV_D + h * QV_DK) * t_pad;                  // [64][t_pad]
-    const half_t *pb = pos + h * QV_DK;                                             // [2*t_max-1][pos_ld]
-    const int n_qt = (T + 31) >> 5, n_kt = (T + 31) >> 5;
-    float *sl = slab[wave];
-    for (int qt = wave; qt < n_qt; qt += 4) {
-        const int i0 = qt * 32;
-        half_t *orow = out + (row0 + i0) * QV_D + h * QV_DK;
-        // B fragments (queries on the column axis): (q+u) and (q+v), row i0 + l31, d = ks*16 + hi*8..
-        half8 qu[4], qv[4];
-        {
-            int qi = i0 + l31;
-            qi = qi < T ? qi : T - 1;   // never touch another utterance's rows
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                int d = ks * 16 + hi * 8;
-                half8 q8 = *(const half8 *)(qb + (size_t)qi * (2 * QV_D) + d);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float qf = (float)q8[e];
-                    qu[ks][e] = (half_t)(qf + bias_u[h * QV_DK + d + e]);
-                    qv[ks][e] = (half_t)(qf + bias_v[h * QV_DK + d + e]);
-                }
-            }
-        }
-        f32x16 o0, o1;  // O^T: rows d (0..31 / 32..63), column = this lane's query
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-        float m_run = -1e30f, l_run = 0.f;
-        // fragments of one key tile: K rows, the two position tiles, V^T pieces (in the key order of the P.V operand)
-        struct TileKP { half8 kf[4], p0[4], p1[4]; };
-        struct TileV { half4 a0[2], a1[2], c0[2], c1[2]; };
-        auto fetch_kp = [&](int kt, TileKP &f) {
-            const int j0 = kt * 32;
-            int kj = j0 + l31;
-            kj = kj < T ? kj : T - 1;
-            // relative-position rows for this tile: rr0 + c, c in [0,64)
-            const int rr0 = t_max - 1 - i0 - 31 + j0;
-            int pr0 = rr0 + l31, pr1 = rr0 + 32 + l31;
-            pr0 = pr0 < 0 ? 0 : (pr0 > 2 * t_max - 2 ? 2 * t_max - 2 : pr0);
-            pr1 = pr1 < 0 ? 0 : (pr1 > 2 * t_max - 2 ? 2 * t_max - 2 : pr1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                int d = ks * 16 + hi * 8;
-                f.kf[ks] = *(const half8 *)(kb + (size_t)kj * (2 * QV_D) + d);
-                f.p0[ks] = *(const half8 *)(pb + (size_t)pr0 * pos_ld + d);
-                f.p1[ks] = *(const half8 *)(pb + (size_t)pr1 * pos_ld + d);
-            }
-        };
-        auto fetch_v = [&](int kt, TileV &f) {
-            const int j0 = kt * 32;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                int jb = j0 + 16 * ks + 4 * hi;  // < t_pad
-                f.a0[ks] = *(const half4 *)(vb + (size_t)l31 * t_pad + jb);
-                f.a1[ks] = *(const half4 *)(vb + (size_t)l31 * t_pad + jb + 8);
-                f.c0[ks] = *(const half4 *)(vb + (size_t)(32 + l31) * t_pad + jb);
-                f.c1[ks] = *(const half4 *)(vb + (size_t)(32 + l31) * t_pad + jb + 8);
-            }
-        };
-        auto tile = [&](int kt, const TileKP &cur, const TileV &cv) {
-            const int j0 = kt * 32;
-            f32x16 st, r0, r1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { st[r] = 0.f; r0[r] = 0.f; r1[r] = 0.f; }
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.kf[ks], qu[ks], st, 0, 0, 0);   // S^T[jj][ii]
-                r0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.p0[ks], qv[ks], r0, 0, 0, 0);   // raw^T[c][ii], c < 32
-                r1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.p1[ks], qv[ks], r1, 0, 0, 0);   // raw^T[32 + c][ii]
-            }
-            // skew through LDS: slab[ii][c] <- raw^T[c][ii]; BD^T[jj][ii] = slab[ii][31 - ii + jj]
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int c = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                sl[l31 * ATT_LDS_LD + c] = r0[r];
-                sl[l31 * ATT_LDS_LD + 32 + c] = r1[r];
-            }
-            __builtin_amdgcn_wave_barrier();
-            float p[16];
-            float mx = -1e30f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                float bd = sl[l31 * ATT_LDS_LD + 31 - l31 + jj];
-                float sc = (st[r] + bd) * 0.125f;
-                p[r] = (j0 + jj < T) ? sc : -1e30f;
-                mx = fmaxf(mx, p[r]);
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            float m_new = fmaxf(m_run, mx);
-            float corr = __expf(m_run - m_new);
-            float sum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                float e = (j0 + jj < T) ? __expf(p[r] - m_new) : 0.f;
-                p[r] = e;
-                sum += e;
-            }
-            sum += __shfl_xor(sum, 32);
-            l_run = l_run * corr + sum;
-            m_run = m_new;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { o0[r] *= corr; o1[r] *= corr; }
-            // P.V: B operand = exp(S^T) registers 8ks..8ks+7 (keys 16ks + 4hi + {0..3, 8..11});
-            // A operand = V^T rows d with the same key order
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                half8 pbf;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pbf[e] = (half_t)p[8 * ks + e];
-                const half4 a0 = cv.a0[ks], a1 = cv.a1[ks], c0 = cv.c0[ks], c1 = cv.c1[ks];
-                half8 va = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                half8 vc = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pbf, o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vc, pbf, o1, 0, 0, 0);
-            }
-        };
-        for (int kt = 0; kt < n_kt; ++kt) {
-            TileKP cur;
-            TileV cv;
-            fetch_kp(kt, cur);
-            fetch_v(kt, cv);
-            tile(kt, cur, cv);
-        }
-        // O^T column (query i0 + l31): d = (r&3) + 8*(r>>2) + 4*hi (+32)
-        if (i0 + l31 < T) {
-            float inv = 1.f / l_run;
-            half_t *o = orow + (size_t)l31 * QV_D;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                int d = 8 * q + 4 * hi;
-                half4 h0, h1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { h0[e] = (half_t)(o0[4 * q + e] * inv); h1[e] = (half_t)(o1[4 * q + e] * inv); }
-                *(half4 *)(o + d) = h0;
-                *(half4 *)(o + 32 + d) = h1;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void att_glds16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g, (__attribute__((address_space(3))) void *)l,
-                                     16, 0, 0);
-}
-
-// Short utterances (T <= 128 encoder frames: every 10 s clip of the headline batch is 126).  The key-tiled kernel below
-// walks the keys tile by tile with an online softmax, which for four key tiles is four times (stage -> barrier ->
-// fragments -> MFMA -> skew through LDS -> softmax -> MFMA) in a row: 16 us of dependent chain for 0.5 us of MFMA.
-// Here a block is one (utterance, head): its four waves (one query tile each) stage ALL of K, V^T and the 256
-// relative-position rows the four query tiles can touch with coalesced direct-to-LDS loads (16 wave-loads per wave, one
-// latency, one barrier; a first version that fetched the fragments straight from global memory -- 56 scattered loads per
-// wave, every wave of the block fetching the same K and V -- ran 25 us, bound by the vector-memory pipeline), then each
-// wave issues the K / position products of the WHOLE key range back to back (<= 16 + 20 MFMAs: the five position tiles
-// of its 160-row window are each computed once, not once per key tile that touches them), skews tile after tile through
-// its LDS slab (which takes the place of K and the position rows after a second barrier), takes ONE softmax over the
-// complete row (no running maximum, no rescaling of the output accumulator) and ends with the <= 16 P.V products.
-// 64 KB of LDS and < 256 registers: two blocks per CU, the headline batch (512 blocks) in one round.  Not the same
-// summation as the key-tiled kernels (single-pass softmax), so not bit-identical to them; WHICH kernel an utterance gets
-// depends on its own length only, never on the batch around it, so an utterance alone and in any batch has the same bits.
-// (ATT_SHORT_T = 128: qv_limits.h)
-#ifdef QV_ATT_STAMPS   // tools/att_bench.hip: shader-clock stamps of one block's waves at the phase boundaries
-__device__ long long g_att_stamp[4][8];
-#define ATT_STAMP(i) do { if (blockIdx.x == 3 && blockIdx.y == 17 && lane == 0) g_att_stamp[wave][i] = clock64(); } while (0)
-#else
-#define ATT_STAMP(i) do { } while (0)
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_attention_short(
-    const half_t *__restrict__ qk, const half_t *__restrict__ vt, const half_t *__restrict__ pos, int pos_ld,
-    const float *__restrict__ bias_u, const float *__restrict__ bias_v, const int32_t *__restrict__ len,
-    const int32_t *__restrict__ row_off, half_t *__restrict__ out, int t_max, int t_pad) {
-    // [0, 16 K): K as 4 tiles [32 keys][64], 16-B chunks swizzled by (key >> 1) & 7; [16 K, 48 K): 256 position rows [64],
-    // swizzled the same way; [48 K, 64 K): V^T as 4 tiles [64 d][32 keys], chunks swizzled by (d >> 2) & 3.
-    // The four skew slabs (34,304 B) reuse [0, 48 K) once every wave has its K / position products.
-    __shared__ __attribute__((aligned(16))) char smem[64 * 1024];
-    half_t *sK = (half_t *)smem, *sP = (half_t *)(smem + 16 * 1024), *sV = (half_t *)(smem + 48 * 1024);
-    // (round 5: handing XCD k the k-th eighth of the (utterance, head) pairs -- xcd_order, as in the LayerNorms -- was
-    // measured: 16.46 -> 16.72 us; the kernel is not waiting for its K / V rows.  Kept head-major.)
-    const int b = blockIdx.y, h = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int T = len[b];
-    if (T > ATT_SHORT_T) return;                // whole block: a long utterance belongs to k_attention_ws
-    ATT_STAMP(0);
-    const size_t row0 = (size_t)row_off[b];
-    const int l31 = lane & 31, hi = lane >> 5;
-    const int i0 = wave * 32;
-    const bool active = i0 < T;
-    const half_t *qb = qk + row0 * (2 * QV_D) + h * QV_DK;
-    const half_t *kb = qb + QV_D;
-    const half_t *vb = vt + ((size_t)b * QV_D + h * QV_DK) * t_pad;
-    const half_t *pb = pos + h * QV_DK;
-    const int n_kt = (T + 31) >> 5;             // 1..4 key tiles = query tiles
-    const int Rb = t_max - 128;                 // position row of window row 0
-    // the query rows first: their latency is the longest chain in front of the first product (convert, add the biases)
-    half8 q8[4];
-    {
-        int qi = i0 + l31;
-        qi = qi < T ? qi : T - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) q8[ks] = *(const half8 *)(qb + (size_t)qi * (2 * QV_D) + ks * 16 + hi * 8);
-    }
-    // ---- stage: wave w loads keys 8 w .. 8 w + 7 of every key tile, d rows 16 w .. of every V^T tile, its share of the
-    // position rows [96 - 32 (n_kt - 1), 96 + 32 (n_kt + 1)) that the active query tiles touch
-    for (int kt = 0; kt < n_kt; ++kt) {
-        {
-            int r = wave * 8 + (lane >> 3), c = (lane & 7) ^ ((r >> 1) & 7);
-            int kj = kt * 32 + r;
-            kj = kj < T ? kj : T - 1;
-            att_glds16(kb + (size_t)kj * (2 * QV_D) + c * 8, sK + kt * 2048 + wave * 512);
-        }
-        {
-            int r = wave * 16 + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 3);
-            att_glds16(vb + (size_t)r * t_pad + kt * 32 + c * 8, sV + kt * 2048 + wave * 512);
-        }
-    }
-    for (int q = 4 * (4 - n_kt) + wave; q < 4 * (4 + n_kt); q += 4) {      // chunks of 8 window rows
-        int wr = q * 8 + (lane >> 3);
-        int c = (lane & 7) ^ ((wr >> 1) & 7);
-        int rr = Rb + wr;
-        rr = rr < 0 ? 0 : (rr > 2 * t_max - 2 ? 2 * t_max - 2 : rr);
-        att_glds16(pb + (size_t)rr * pos_ld + c * 8, sP + q * 512);
-    }
-    half8 qu[4], qv[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        int d = ks * 16 + hi * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float qf = (float)q8[ks][e];
-            qu[ks][e] = (half_t)(qf + bias_u[h * QV_DK + d + e]);
-            qv[ks][e] = (half_t)(qf + bias_v[h * QV_DK + d + e]);
-        }
-    }
-    ATT_STAMP(1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    ATT_STAMP(2);
-    // S^T[kt][jj][ii] for every key tile, raw^T[pt][c][ii] for position tiles pt = 0 .. n_kt (window rows 96 - i0 + 32 pt + c)
-    f32x16 st[4], raw[5];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[kt][r] = 0.f;
-        if (active && kt < n_kt) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int c = ks * 2 + hi;
-                half8 kf = *(const half8 *)(sK + kt * 2048 + l31 * 64 + ((c ^ ((l31 >> 1) & 7)) << 3));
-                st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qu[ks], st[kt], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int pt = 0; pt < 5; ++pt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) raw[pt][r] = 0.f;
-        if (active && pt <= n_kt) {
-            const int wr = 96 - i0 + 32 * pt + l31;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int c = ks * 2 + hi;
-                half8 pf = *(const half8 *)(sP + wr * 64 + ((c ^ ((wr >> 1) & 7)) << 3));
-                raw[pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pf, qv[ks], raw[pt], 0, 0, 0);
-            }
-        }
-    }
-    __syncthreads();                            // K and the position rows are dead: the slabs take their place
-    if (!active) return;
-    ATT_STAMP(3);
-    float *sl = (float *)smem + wave * (32 * ATT_LDS_LD);
-    // skew tile by tile: BD^T of key tile kt is slab[ii][31 - ii + jj] over the 64 columns (raw^T tile kt | tile kt + 1).
-    // Every position tile is written ONCE: tile pt lives in slab columns 32 (pt & 1) .., so key tile kt finds tile kt in
-    // one half and only tile kt + 1 has to replace tile kt - 1 in the other; the read column wraps modulo 64.
-    // st[kt] becomes the masked, scaled score
-    float mx = -1e30f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sl[l31 * ATT_LDS_LD + (r & 3) + 8 * (r >> 2) + 4 * hi] = raw[0][r];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-        if (kt < n_kt) {
-            __builtin_amdgcn_wave_barrier();    // the reads of key tile kt - 1 are issued before tile kt + 1 lands on tile kt - 1
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                sl[l31 * ATT_LDS_LD + 32 * ((kt + 1) & 1) + (r & 3) + 8 * (r >> 2) + 4 * hi] = raw[kt + 1][r];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                float bd = sl[l31 * ATT_LDS_LD + ((32 * (kt & 1) + 31 - l31 + jj) & 63)];
-                float sc = (st[kt][r] + bd) * 0.125f;
-                sc = (kt * 32 + jj < T) ? sc : -1e30f;
-                st[kt][r] = sc;
-                mx = fmaxf(mx, sc);
-            }
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    ATT_STAMP(4);
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-        if (kt < n_kt) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                float e = (kt * 32 + jj < T) ? __expf(st[kt][r] - mx) : 0.f;
-                st[kt][r] = e;
-                sum += e;
-            }
-        }
-    }
-    sum += __shfl_xor(sum, 32);
-    ATT_STAMP(5);
-    // P.V: B operand = exp(S^T) registers 8ks .. 8ks + 7 of tile kt (keys 32 kt + 16 ks + 4 hi + {0..3, 8..11});
-    // A operand = V^T rows d with the same key order: 16-B chunks 2 ks and 2 ks + 1 of the tile, 8-byte half `hi`
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-        if (kt < n_kt) {
-            const half_t *sVb = sV + kt * 2048;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                half8 pbf;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pbf[e] = (half_t)st[kt][8 * ks + e];
-                const int da = l31, dc = 32 + l31;
-                half4 a0 = *(const half4 *)(sVb + da * 32 + (((2 * ks) ^ ((da >> 2) & 3)) << 3) + 4 * hi);
-                half4 a1 = *(const half4 *)(sVb + da * 32 + (((2 * ks + 1) ^ ((da >> 2) & 3)) << 3) + 4 * hi);
-                half4 c0 = *(const half4 *)(sVb + dc * 32 + (((2 * ks) ^ ((dc >> 2) & 3)) << 3) + 4 * hi);
-                half4 c1 = *(const half4 *)(sVb + dc * 32 + (((2 * ks + 1) ^ ((dc >> 2) & 3)) << 3) + 4 * hi);
-                half8 va = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                half8 vc = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(va, pbf, o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(vc, pbf, o1, 0, 0, 0);
-            }
-        }
-    }
-    if (i0 + l31 < T) {
-        float inv = 1.f / sum;
-        half_t *o = out + (row0 + i0 + l31) * QV_D + h * QV_DK;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int d = 8 * q + 4 * hi;
-            half4 h0, h1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { h0[e] = (half_t)(o0[4 * q + e] * inv); h1[e] = (half_t)(o1[4 * q + e] * inv); }
-            *(half4 *)(o + d) = h0;
-            *(half4 *)(o + 32 + d) = h1;
-        }
-    }
-    ATT_STAMP(6);
-}
-
-// Wave-specialised version of the same computation (same arithmetic, same order).  k_attention's
-// duration is one wave's serial chain -- per key tile two exposed global-load latencies (K and
-// position fragments, then V) in front of 16 MFMAs -- and it keeps a wave busy with one query tile
-// after the other for long utterances.  Here a block is one (head, utterance, group of 4 query
-// tiles): waves 0..3 are consumers (one query tile each; fragments come from LDS), waves 4..7 are
-// loaders that stage, TWO key tiles ahead (3 buffers), the K tile (32 keys x 64), the V^T tile
-// (64 x 32 keys) and the 32 NEW relative-position rows of the tile: the position rows the four query
-// tiles need form a sliding window of 160 rows that advances by 32 per key tile, kept in a 256-row
-// ring (window of tile kt + the 64 rows prefetched for kt + 1 and kt + 2 never overlap in it).
-// HPB heads share a block (4 consumer waves each; the 4 loader waves stage for all of them): with HPB = 2 every SIMD runs
-// two consumer waves whose serial chains (MFMA -> skew through LDS -> softmax -> MFMA) overlap, and B = 64 x 10 s is one
-// round of 256 blocks instead of two rounds of 512.  LDS then only holds NST = 2 K/V stages (tile kt + 1 is requested
-// when tile kt's barrier frees the other buffer) and a 192-row position ring (160-row window + the 32 rows of the next
-// tile).  The arithmetic of a (head, query tile) is the same wave program in both shapes: outputs are bit-identical.
-
-#ifdef QV_ATT_STAMPS   // tools/att_bench.hip: per key tile, clock stamps of every wave of ONE block of the key-tiled kernel
-__device__ long long g_ws_stamp[12][16][6];
-#define WS_STAMP(kt, i) do { if (blockIdx.x == 1 && blockIdx.y == 1 && blockIdx.z == 17 && lane == 0 && (kt) < 16) g_ws_stamp[wave][kt][i] = clock64(); } while (0)
-#else
-#define WS_STAMP(kt, i) do { } while (0)
-#endif
-template <int HPB, int NST, int RING>
-__global__ __launch_bounds__(256 * HPB + 256) void k_attention_ws(const half_t *__restrict__ qk, const half_t *__restrict__ vt,
-                                                                  const half_t *__restrict__ pos, int pos_ld,
-                                                                  const float *__restrict__ bias_u, const float *__restrict__ bias_v,
-                                                                  const int32_t *__restrict__ len, const int32_t *__restrict__ row_off,
-                                                                  half_t *__restrict__ out, int t_max, int t_pad, int t_short) {
-    static_assert(RING % 8 == 0 && RING >= 160 + 32 * (NST - 1), "position ring: window + prefetched rows");
-    __shared__ __attribute__((aligned(16))) half_t sK[HPB][NST][32 * 64];    // [key][d], 16-B chunks swizzled by (key >> 1) & 7
-    __shared__ __attribute__((aligned(16))) half_t sV[HPB][NST][64 * 32];    // [d][key], 16-B chunks swizzled by (d >> 2) & 3
-    __shared__ __attribute__((aligned(16))) half_t sP[HPB][RING * 64];       // ring of position rows, swizzled like sK
-    __shared__ float slab[4 * HPB][32 * ATT_LDS_LD];
-    const int b = blockIdx.z, qg = blockIdx.y, hg = blockIdx.x;
-    const int T = len[b];
-    if (qg * 128 >= T || T <= t_short) return;       // whole block: no query of this group exists / k_attention_short's utterance
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool loader = wave >= 4 * HPB;
-    const int w4 = wave & 3, l31 = lane & 31, hi = lane >> 5;
-    const size_t row0 = (size_t)row_off[b];
-    const int n_kt = (T + 31) >> 5;
-    const int Rb = t_max - 128 * qg - 128;           // first position row of key tile 0's window
-
-    if (loader) {
-        // per head: one K, one V and one position load per loader wave and key tile (1 KB each)
-        auto stage = [&](int kt) {
-            const int j0 = kt * 32, buf = kt % NST;
-#pragma unroll
-            for (int hh = 0; hh < HPB; ++hh) {
-                const int h = hg * HPB + hh;
-                const half_t *kb = qk + row0 * (2 * QV_D) + QV_D + h * QV_DK;
-                const half_t *vb = vt + ((size_t)b * QV_D + h * QV_DK) * t_pad;
-                {   // K: 8 keys x 128 B per wave
-                    int r = w4 * 8 + (lane >> 3), c = (lane & 7) ^ ((r >> 1) & 7);
-                    int kj = j0 + r;
-                    kj = kj < T ? kj : T - 1;
-                    att_glds16(kb + (size_t)kj * (2 * QV_D) + c * 8, sK[hh][buf] + w4 * 512);
-                }
-                {   // V^T: 16 d rows x 64 B per wave (keys j0 .. j0 + 31 < t_pad)
-                    int r = w4 * 16 + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 3);
-                    att_glds16(vb + (size_t)r * t_pad + j0 + c * 8, sV[hh][buf] + w4 * 512);
-                }
-            }
-        };
-        auto pos_rows = [&](int first, int n8) {   // n8 chunks of 8 rows starting at window row `first`, this wave's share
-            for (int q = w4; q < n8; q += 4) {
-                int wr = first + q * 8 + (lane >> 3);                 // row relative to Rb
-                int ring = wr % RING;
-                int c = (lane & 7) ^ ((ring >> 1) & 7);
-                int rr = Rb + wr;
-                rr = rr < 0 ? 0 : (rr > 2 * t_max - 2 ? 2 * t_max - 2 : rr);
-#pragma unroll
-                for (int hh = 0; hh < HPB; ++hh)
-                    att_glds16(pos + (hg * HPB + hh) * QV_DK + (size_t)rr * pos_ld + c * 8,
-                               sP[hh] + (size_t)((first + q * 8) % RING) * 64);
-            }
-        };
-        // per wave: unit(0) = HPB x (5 position chunks + K + V), unit(kt >= 1) = HPB x (K + V + 1 position chunk)
-        pos_rows(0, 20);        // rows 0 .. 159: the window of tile 0
-        stage(0);
-        if (NST == 3 && n_kt > 1) {
-            stage(1);
-            pos_rows(32 + 128, 4);
-        }
-        for (int kt = 0; kt < n_kt; ++kt) {
-            WS_STAMP(kt, 0);
-            // unit(kt) has landed once only the units requested after it may still be in flight
-            if (NST == 3 && kt + 1 < n_kt) {
-                if (HPB == 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            WS_STAMP(kt, 1);
-            __builtin_amdgcn_s_barrier();           // tile kt visible; the buffers of tile kt - 1 are free
-            WS_STAMP(kt, 2);
-            if (kt + NST - 1 < n_kt) {
-                stage(kt + NST - 1);
-                pos_rows(32 * (kt + NST - 1) + 128, 4);   // the 32 new rows of that tile
-            }
-            WS_STAMP(kt, 3);
-        }
-        return;
-    }
-
-    // ---------------------------------------------------------------- consumers ----------
-    const int hh = wave >> 2, h = hg * HPB + hh;
-    const int i0 = qg * 128 + w4 * 32;
-    const bool active = i0 < T;
-    const half_t *qb = qk + row0 * (2 * QV_D) + h * QV_DK;
-    float *sl = slab[wave];
-    const half_t *sPh = sP[hh];
-    half8 qu[4], qv[4];
-    {
-        int qi = i0 + l31;
-        qi = qi < T ? qi : T - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            int d = ks * 16 + hi * 8;
-            half8 q8 = *(const half8 *)(qb + (size_t)qi * (2 * QV_D) + d);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float qf = (float)q8[e];
-                qu[ks][e] = (half_t)(qf + bias_u[h * QV_DK + d + e]);
-                qv[ks][e] = (half_t)(qf + bias_v[h * QV_DK + d + e]);
-            }
-        }
-    }
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-    // Round 6.  The loop below is bound by the instructions the two consumer waves of a SIMD issue per key tile (stamps in
-    // tools/att_bench: 4.4 k cycles per tile, the loaders land a tile ahead and wait), so the same arithmetic is issued
-    // with fewer of them -- the output bits do not change (tests compare variants 0 .. 2):
-    //  * scores stay in RAW units (8 x the scaled score) up to the exponential: exp((p - m) / 8) = exp2((p - m) * (log2 e / 8)),
-    //    and scaling by a power of two commutes with every rounding on the way -- 16 multiplies per tile gone;
-    //  * the key mask (j0 + jj < T) only exists in an utterance's LAST key tile: the other tiles run an unmasked copy of
-    //    the body (16 compares + 32 selects gone);
-    //  * the skew slab keeps alternating halves (tile kt sits where tile kt - 1 wrote it as ITS second tile), but the column
-    //    of a value is no longer computed with a wrap: an even key tile reads lane constant + immediate (31 - ii + jj <= 62
-    //    never wraps), an odd one reads the same column XOR 32, i.e. one of two lane-constant bases chosen by a compare of two
-    //    constants per value -- ~5 integer instructions per value read become 0 / 2;
-    //  * fragment addresses: lane constants computed once, XORed with the K-step.
-    constexpr float NEG = -1e30f * 8.0f, L2E8 = 0x1.715476p+0f * 0.125f;   // (__expf(x) is v_exp_f32(x * 0x1.715476p+0))
-    float m_run = NEG, l_run = 0.f;
-    const int swz = (l31 >> 1) & 7;
-    const int kf0 = l31 * 64 + ((hi ^ swz) << 3);                  // K / position fragment of K-step ks: kf0 ^ (ks << 4) (halves)
-    float *const slw = sl + l31 * ATT_LDS_LD + 4 * hi;            // slab stores: + 32 * tile + (r & 3) + 8 * (r >> 2)
-    const float *const slr = sl + l31 * ATT_LDS_LD + (31 - l31 + 4 * hi);   // slab loads: + (r & 3) + 8 * (r >> 2), never past column 62
-    // odd tiles: slab column = window column ^ 32, i.e. + 32 where the window column 31 - ii + jj is below 32 and - 32 elsewhere;
-    // bit r of `hiw` says "elsewhere" for register r, so the address is one shift-add away from a lane constant
-    unsigned hiw = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hiw |= (unsigned)((r & 3) + 8 * (r >> 2) >= 1 + l31 - 4 * hi) << r;
-    const int vda = l31 * 32 + 4 * hi, vdc = (32 + l31) * 32 + 4 * hi, vsw = (l31 >> 2) & 3;   // V^T rows d = l31 and 32 + l31 share (d >> 2) & 3
-    int ring1 = (128 - 32 * w4) % RING;                          // position tile kt + 1 of this wave starts at ring row 32 kt + 128 - 32 w4
-    auto tile = [&](int kt, auto masked_c, auto odd_c) {
-        constexpr bool MASKED = decltype(masked_c)::value, ODD = decltype(odd_c)::value;   // ODD: kt & 1 (never kt == 0)
-        const int j0 = kt * 32, buf = kt % NST;
-        // (the per-K-step fragment offsets are re-derived from three lane constants in every tile -- one XOR / shift each: hoisted
-        // out of the loop they are 14 more live registers, and the two-heads-per-block shape has 168 per wave)
-        int kfl = kf0, val = vda, vcl = vdc;
-        asm volatile("" : "+v"(kfl), "+v"(val), "+v"(vcl));
-        const half_t *sKb = sK[hh][buf], *sVb = sV[hh][buf];
-        // position tile pt = rows 32 pt .. of the wave's window: key tile kt needs tiles kt and kt + 1, and tile kt is what
-        // key tile kt - 1 computed as ITS second tile -- same operands, same products, so it is carried over instead of
-        // being computed twice
-        f32x16 st, r1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st[r] = 0.f; r1[r] = 0.f; }
-        if (!ODD && kt == 0) {
-            const int ring0 = (96 - 32 * w4) % RING;
-            f32x16 r0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) r0[r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                half8 p0 = *(const half8 *)(sPh + ring0 * 64 + (kfl ^ (ks << 4)));
-                r0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(p0, qv[ks], r0, 0, 0, 0);
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) slw[(r & 3) + 8 * (r >> 2)] = r0[r];
-        }
-        const half_t *sP1 = sPh + ring1 * 64;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            half8 kf = *(const half8 *)(sKb + (kfl ^ (ks << 4)));
-            half8 p1 = *(const half8 *)(sP1 + (kfl ^ (ks << 4)));
-            st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qu[ks], st, 0, 0, 0);
-            r1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, qv[ks], r1, 0, 0, 0);
-        }
-        ring1 += 32;
-        if (ring1 >= RING) ring1 -= RING;
-        // skew: BD^T[jj][ii] = window[ii][31 - ii + jj], window = [tile kt | tile kt + 1]; tile pt lives in slab columns
-        // 32 (pt & 1) .., so tile kt is already there and tile kt + 1 replaces tile kt - 1
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slw[(ODD ? 0 : 32) + (r & 3) + 8 * (r >> 2)] = r1[r];
-        __builtin_amdgcn_wave_barrier();
-        WS_STAMP(kt, 2);
-        float p[16];
-        float mx = NEG;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const int e = (r & 3) + 8 * (r >> 2);
-            // even tile: window column = slab column; odd tile: slab column = window column ^ 32
-            const float bd = !ODD ? slr[e] : *(const float *)((const char *)(slr + 32 + e) - (((hiw >> r) & 1u) << 8));
-            const float sc = st[r] + bd;
-            p[r] = (!MASKED || j0 + jj < T) ? sc : NEG;
-            mx = fmaxf(mx, p[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float corr = __builtin_amdgcn_exp2f((m_run - m_new) * L2E8);
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const float e = (!MASKED || j0 + jj < T) ? __builtin_amdgcn_exp2f((p[r] - m_new) * L2E8) : 0.f;
-            p[r] = e;
-            sum += e;
-        }
-        sum += __shfl_xor(sum, 32);
-        l_run = l_run * corr + sum;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] *= corr; o1[r] *= corr; }
-        WS_STAMP(kt, 3);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 pbf;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pbf[e] = (half_t)p[8 * ks + e];
-            // V^T pieces: keys 16 ks + 4 hi + {0..3} and + 8 -> 16-B chunks 2 ks and 2 ks + 1, 8-byte half `hi`
-            half4 a0 = *(const half4 *)(sVb + val + (((2 * ks) ^ vsw) << 3));
-            half4 a1 = *(const half4 *)(sVb + val + (((2 * ks + 1) ^ vsw) << 3));
-            half4 c0 = *(const half4 *)(sVb + vcl + (((2 * ks) ^ vsw) << 3));
-            half4 c1 = *(const half4 *)(sVb + vcl + (((2 * ks + 1) ^ vsw) << 3));
-            half8 v0 = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-            half8 v1 = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, pbf, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, pbf, o1, 0, 0, 0);
-        }
-        WS_STAMP(kt, 4);
-    };
-    for (int kt = 0; kt < n_kt; ++kt) {
-        WS_STAMP(kt, 0);
-        __builtin_amdgcn_s_barrier();
-        WS_STAMP(kt, 1);
-        if (!active) continue;
-        if (kt + 1 < n_kt) { if (kt & 1) tile(kt, std::false_type{}, std::true_type{}); else tile(kt, std::false_type{}, std::false_type{}); }
-        else { if (kt & 1) tile(kt, std::true_type{}, std::true_type{}); else tile(kt, std::true_type{}, std::false_type{}); }
-    }
-    if (active && i0 + l31 < T) {
-        float inv = 1.f / l_run;
-        half_t *o = out + (row0 + i0 + l31) * QV_D + h * QV_DK;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int d = 8 * q + 4 * hi;
-            half4 h0, h1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { h0[e] = (half_t)(o0[4 * q + e] * inv); h1[e] = (half_t)(o1[4 * q + e] * inv); }
-            *(half4 *)(o + d) = h0;
-            *(half4 *)(o + 32 + d) = h1;
-        }
-    }
-}
-
-// Round 6, variant 4: the key-tiled computation WITHOUT loader waves and with TWO independent blocks per CU.
-// k_attention_ws<2, 2, 192> is bound by the instruction issue of the two consumer waves of a SIMD, and those two run in lock
-// step: both heads of a block leave the same barrier, so both are in their MFMA phase, then both in their softmax phase
-// (stamps: tools/att_bench).  Here a block is ONE (head, 128-query group, utterance) with four waves that stage their own
-// tiles -- each wave issues its quarter of the K, V^T and position loads of key tile kt + 1 (three 1 KB direct-to-LDS loads)
-// right after the barrier that released tile kt -- in 74 KB of LDS and, without loader waves, 256 threads: two blocks per
-// CU, 256 registers per wave.  The two consumer waves of a SIMD then belong to DIFFERENT blocks, whose barriers are
-// independent: one wave's matrix products run under the other's softmax.  Same wave program per (head, query tile) as the
-// other key-tiled shapes => the same bits (tests/test_gpu_forward.py compares variants 0, 1, 2 and 4).
-template <int RING>
-__global__ __launch_bounds__(256, 2) void k_attention_x(const half_t *__restrict__ qk, const half_t *__restrict__ vt,
-                                                         const half_t *__restrict__ pos, int pos_ld,
-                                                         const float *__restrict__ bias_u, const float *__restrict__ bias_v,
-                                                         const int32_t *__restrict__ len, const int32_t *__restrict__ row_off,
-                                                         half_t *__restrict__ out, int t_max, int t_pad, int t_short) {
-    static_assert(RING % 32 == 0 && RING >= 160 + 32, "position ring: window + the rows of the next tile");
-    __shared__ __attribute__((aligned(16))) half_t sK[2][32 * 64];      // [key][d], 16-B chunks swizzled by (key >> 1) & 7
-    __shared__ __attribute__((aligned(16))) half_t sV[2][64 * 32];      // [d][key], 16-B chunks swizzled by (d >> 2) & 3
-    __shared__ __attribute__((aligned(16))) half_t sP[RING * 64];       // ring of position rows, swizzled like sK
-    __shared__ float slab[4][32 * ATT_LDS_LD];
-    const int b = blockIdx.z, qg = blockIdx.y, h = blockIdx.x;
-    const int T = len[b];
-    if (qg * 128 >= T || T <= t_short) return;
-    const int w4 = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
-    const size_t row0 = (size_t)row_off[b];
-    const int n_kt = (T + 31) >> 5;
-    const int Rb = t_max - 128 * qg - 128;           // first position row of key tile 0's window
-    const half_t *kb = qk + row0 * (2 * QV_D) + QV_D + h * QV_DK;
-    const half_t *vb = vt + ((size_t)b * QV_D + h * QV_DK) * t_pad;
-    const half_t *pb = pos + h * QV_DK;
-    auto stage = [&](int kt) {                        // this wave's quarter of key tile kt: 8 keys of K, 16 d rows of V^T
-        const int j0 = kt * 32, buf = kt & 1;
-        {
-            int r = w4 * 8 + (lane >> 3), c = (lane & 7) ^ ((r >> 1) & 7);
-            int kj = j0 + r;
-            kj = kj < T ? kj : T - 1;
-            att_glds16(kb + (size_t)kj * (2 * QV_D) + c * 8, sK[buf] + w4 * 512);
-        }
-        {
-            int r = w4 * 16 + (lane >> 2), c = (lane & 3) ^ ((r >> 2) & 3);
-            att_glds16(vb + (size_t)r * t_pad + j0 + c * 8, sV[buf] + w4 * 512);
-        }
-    };
-    auto pos_rows = [&](int first, int n8) {          // n8 chunks of 8 rows starting at window row `first`, this wave's share
-        for (int q = w4; q < n8; q += 4) {
-            int wr = first + q * 8 + (lane >> 3);
-            int ring = wr % RING;
-            int c = (lane & 7) ^ ((ring >> 1) & 7);
-            int rr = Rb + wr;
-            rr = rr < 0 ? 0 : (rr > 2 * t_max - 2 ? 2 * t_max - 2 : rr);
-            att_glds16(pb + (size_t)rr * pos_ld + c * 8, sP + (size_t)((first + q * 8) % RING) * 64);
-        }
-    };
-    pos_rows(0, 20);                                  // rows 0 .. 159: the window of tile 0
-    stage(0);
-
-    const int i0 = qg * 128 + w4 * 32;
-    const bool active = i0 < T;
-    const half_t *qb = qk + row0 * (2 * QV_D) + h * QV_DK;
-    float *sl = slab[w4];
-    half8 qu[4], qv[4];
-    {
-        int qi = i0 + l31;
-        qi = qi < T ? qi : T - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            int d = ks * 16 + hi * 8;
-            half8 q8 = *(const half8 *)(qb + (size_t)qi * (2 * QV_D) + d);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float qf = (float)q8[e];
-                qu[ks][e] = (half_t)(qf + bias_u[h * QV_DK + d + e]);
-                qv[ks][e] = (half_t)(qf + bias_v[h * QV_DK + d + e]);
-            }
-        }
-    }
-    f32x16 o0, o1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-    // (the wave program below is k_attention_ws's, statement for statement: raw-unit softmax, mask in the last tile only,
-    // alternating slab halves with wrap-free addressing)
-    constexpr float NEG = -1e30f * 8.0f, L2E8 = 0x1.715476p+0f * 0.125f;
-    float m_run = NEG, l_run = 0.f;
-    const int swz = (l31 >> 1) & 7;
-    const int kf0 = l31 * 64 + ((hi ^ swz) << 3);
-    float *const slw = sl + l31 * ATT_LDS_LD + 4 * hi;
-    const float *const slr = sl + l31 * ATT_LDS_LD + (31 - l31 + 4 * hi);
-    unsigned hiw = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hiw |= (unsigned)((r & 3) + 8 * (r >> 2) >= 1 + l31 - 4 * hi) << r;
-    const int vda = l31 * 32 + 4 * hi, vdc = (32 + l31) * 32 + 4 * hi, vsw = (l31 >> 2) & 3;
-    int ring1 = (128 - 32 * w4) % RING;
-    auto tile = [&](int kt, auto masked_c, auto odd_c) {
-        constexpr bool MASKED = decltype(masked_c)::value, ODD = decltype(odd_c)::value;
-        const int j0 = kt * 32, buf = kt & 1;
-        const half_t *sKb = sK[buf], *sVb = sV[buf];
-        f32x16 st, r1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st[r] = 0.f; r1[r] = 0.f; }
-        if (!ODD && kt == 0) {
-            const int ring0 = (96 - 32 * w4) % RING;
-            f32x16 r0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) r0[r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                half8 p0 = *(const half8 *)(sP + ring0 * 64 + (kf0 ^ (ks << 4)));
-                r0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(p0, qv[ks], r0, 0, 0, 0);
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) slw[(r & 3) + 8 * (r >> 2)] = r0[r];
-        }
-        const half_t *sP1 = sP + ring1 * 64;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            half8 kf = *(const half8 *)(sKb + (kf0 ^ (ks << 4)));
-            half8 p1 = *(const half8 *)(sP1 + (kf0 ^ (ks << 4)));
-            st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qu[ks], st, 0, 0, 0);
-            r1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(p1, qv[ks], r1, 0, 0, 0);
-        }
-        ring1 += 32;
-        if (ring1 >= RING) ring1 -= RING;
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slw[(ODD ? 0 : 32) + (r & 3) + 8 * (r >> 2)] = r1[r];
-        __builtin_amdgcn_wave_barrier();
-        float p[16];
-        float mx = NEG;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const int e = (r & 3) + 8 * (r >> 2);
-            const float bd = !ODD ? slr[e] : *(const float *)((const char *)(slr + 32 + e) - (((hiw >> r) & 1u) << 8));
-            const float sc = st[r] + bd;
-            p[r] = (!MASKED || j0 + jj < T) ? sc : NEG;
-            mx = fmaxf(mx, p[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float corr = __builtin_amdgcn_exp2f((m_run - m_new) * L2E8);
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jj = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const float e = (!MASKED || j0 + jj < T) ? __builtin_amdgcn_exp2f((p[r] - m_new) * L2E8) : 0.f;
-            p[r] = e;
-            sum += e;
-        }
-        sum += __shfl_xor(sum, 32);
-        l_run = l_run * corr + sum;
-        m_run = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] *= corr; o1[r] *= corr; }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 pbf;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) pbf[e] = (half_t)p[8 * ks + e];
-            half4 a0 = *(const half4 *)(sVb + vda + (((2 * ks) ^ vsw) << 3));
-            half4 a1 = *(const half4 *)(sVb + vda + (((2 * ks + 1) ^ vsw) << 3));
-            half4 c0 = *(const half4 *)(sVb + vdc + (((2 * ks) ^ vsw) << 3));
-            half4 c1 = *(const half4 *)(sVb + vdc + (((2 * ks + 1) ^ vsw) << 3));
-            half8 v0 = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-            half8 v1 = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-            o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0, pbf, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, pbf, o1, 0, 0, 0);
-        }
-    };
-    for (int kt = 0; kt < n_kt; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's quarter of tile kt (and of its position rows) has landed ...
-        __builtin_amdgcn_s_barrier();                        // ... and everybody's; everybody has left tile kt - 1's buffers
-        if (kt + 1 < n_kt) {
-            stage(kt + 1);
-            pos_rows(32 * (kt + 1) + 128, 4);               // the 32 new rows of that tile
-        }
-        if (!active) continue;
-        if (kt + 1 < n_kt) { if (kt & 1) tile(kt, std::false_type{}, std::true_type{}); else tile(kt, std::false_type{}, std::false_type{}); }
-        else { if (kt & 1) tile(kt, std::true_type{}, std::true_type{}); else tile(kt, std::true_type{}, std::false_type{}); }
-    }
-    if (active && i0 + l31 < T) {
-        float inv = 1.f / l_run;
-        half_t *o = out + (row0 + i0 + l31) * QV_D + h * QV_DK;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int d = 8 * q + 4 * hi;
-            half4 h0, h1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { h0[e] = (half_t)(o0[4 * q + e] * inv); h1[e] = (half_t)(o1[4 * q + e] * inv); }
-            *(half4 *)(o + d) = h0;
-            *(half4 *)(o + 32 + d) = h1;
-        }
-    }
-}
-
 // ------------------------------------------------------------------ conv module --------
 // depthwise Conv1d(512, k=9, pad 4) + folded BatchNorm + Swish on f16 [M][512]; input frames
 // t >= len[b] read as zero (the reference zeroes padded frames after GLU).  A lane owns 8
@@ -1882,37 +1033,6 @@ void launch_to_half(const float *x, half_t *y, size_t n, hipStream_t s) {
 
 void launch_to_float(const half_t *x, float *y, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_to_float, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, n);
-}
-
-// which kernels a batch gets: attention_plan (qv_launch_plan.h).  The caller passes the snapshot it took ONCE (a forward:
-// qv_model.hip), so a test that flips the process-wide switch while batches of other contexts are in flight cannot change
-// kernels between the layers of one forward
-void launch_attention(const half_t *qk, const half_t *vt, const half_t *pos, int pos_ld, const float *bu, const float *bv,
-                      const int32_t *len, const int32_t *row_off, half_t *out, int t_max, int t_min, int t_pad, int batch,
-                      hipStream_t s, const QvSwitches &sw) {
-    const AttentionPlan p = attention_plan(sw[QV_SW_ATT], t_min, t_max);
-    if (p.run_short)
-        hipLaunchKernelGGL(k_attention_short, dim3(QV_H, batch), dim3(256), 0, s, qk, vt, pos, pos_ld, bu, bv, len, row_off,
-                           out, t_max, t_pad);
-    switch (p.rest) {
-    case ATT_OLD:
-        hipLaunchKernelGGL(k_attention, dim3(QV_H, batch), dim3(256), 0, s, qk, vt, pos, pos_ld, bu, bv, len, row_off, out, t_max,
-                           t_pad);
-        break;
-    case ATT_X_192:
-        hipLaunchKernelGGL((k_attention_x<192>), dim3(QV_H, (t_max + 127) / 128, batch), dim3(256), 0, s, qk, vt, pos,
-                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, p.t_short);
-        break;
-    case ATT_WS_1_3_256:
-        hipLaunchKernelGGL((k_attention_ws<1, 3, 256>), dim3(QV_H, (t_max + 127) / 128, batch), dim3(512), 0, s, qk, vt, pos,
-                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, p.t_short);
-        break;
-    case ATT_WS_2_2_192:
-        hipLaunchKernelGGL((k_attention_ws<2, 2, 192>), dim3(QV_H / 2, (t_max + 127) / 128, batch), dim3(768), 0, s, qk, vt, pos,
-                           pos_ld, bu, bv, len, row_off, out, t_max, t_pad, p.t_short);
-        break;
-    default: break;   // ATT_NONE: every utterance was the short kernel's
-    }
 }
 
 void launch_dwconv1d(const half_t *x, const float *w, const float *bias, const int32_t *len, const int32_t *row_off, half_t *y,

@@ -29,7 +29,7 @@
 //   QV_KV_SUB35   (no variable)     steps of three c2 frames a block of k_sub35 walks: 0 = chosen from the launch shape (default);
 //                                   1 / 2 = one / two steps; 3 = the most a block ever walks (16)
 // The rest:
-//   QV_SW_ATT         the attention kernels (qv_debug_attention_variant; launch_attention in qv_layers.hip describes 0..5).  Its
+//   QV_SW_ATT         the attention kernels (qv_debug_attention_variant; attention_plan in qv_launch_plan.h describes 0..5).  Its
 //                     environment value comes from the four flags behind it, QVERSE_ATT_OLD > _HPB > _TILED > _X -> 2 / 1 / 0 / 5
 //   QV_SW_GEMM_*      launch_gemm's tile and pipeline policy (gemm_plan in qv_launch_plan.h); T256 and BM have setters
 //                     (qv_debug_gemm_tiles, qv_debug_gemm_tile_height)

@@ -19,7 +19,8 @@ SRC = ROOT / "tools" / "interference_probe.hip"
 DEPS = [Path(__file__).resolve(), ROOT / "offline-tarteel_amd" / "build.py", SRC, ROOT / "tools" / "logmel_variants.h", ROOT / "tools" / "withdrawn" / "qv_ort_conv0_mfma.hip",
         *sorted((ROOT / "offline-tarteel_amd" / "csrc").glob("*.h")), *sorted((ROOT / "offline-tarteel_amd" / "csrc").glob("*.inc")),
         ROOT / "offline-tarteel_amd" / "csrc" / "qv_gemm.hip", ROOT / "offline-tarteel_amd" / "csrc" / "qv_gemm256.hip",
-        ROOT / "offline-tarteel_amd" / "csrc" / "qv_layers.hip", ROOT / "offline-tarteel_amd" / "csrc" / "qv_ort.hip"]
+        ROOT / "offline-tarteel_amd" / "csrc" / "qv_layers.hip", ROOT / "offline-tarteel_amd" / "csrc" / "qv_attention.hip",
+        ROOT / "offline-tarteel_amd" / "csrc" / "qv_ort.hip"]
 
 
 def build(force: bool = False) -> list[Path]:

@@ -32,7 +32,7 @@ def kernels_of(lib: Path, tmp: Path):
             if m:
                 name = m.group(1)
                 code.setdefault(name, [])
-            elif name and ln.strip():
+            elif name and ln.strip() and ln.strip() != "...":   # "...": zero padding up to the next symbol, not code
                 code[name].append(re.sub(r"^\s*[0-9a-f]+:\s*", "", re.sub(r"\s*//.*$", "", ln)).strip())
         notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(o)], capture_output=True, text=True, check=True).stdout
         for blk in notes.split("- .agpr_count:")[1:]:
