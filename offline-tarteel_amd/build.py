@@ -64,9 +64,7 @@ def build(force: bool = False, verbose: bool = False, dev_hooks: bool = False) -
     jobs = []
     for src in sources():
         obj = OBJ / (src.stem + ".o")
-        # (qv_postlogits_wide.hip is qv_postlogits.hip compiled for the wide matching window: it includes that file)
-        extra = [CSRC / "qv_postlogits.hip"] if src.stem == "qv_postlogits_wide" else []
-        if force or _stale(obj, [src] + extra + headers):
+        if force or _stale(obj, [src] + headers):
             jobs.append((src, obj))
 
     def cc(job):

@@ -343,6 +343,7 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
         qv_set_error(eng, "max_transcript must be 0, 1024 or 2048");
         return fail(QV_ERR_ARG);
     }
+    eng->match = eng->max_q > QV_MAX_TRANSCRIPT ? &qv_match_wide : &qv_match_default;
     if (cfg->max_span < 2 || cfg->max_span > QV_MAX_SPAN) { qv_set_error(eng, "CTC_DIRECT_MAX_SPAN must be in [2,6]"); return fail(QV_ERR_ARG); }
     // c2c-direct/run.py:67 takes any float (negative weights included); only a non-finite one is refused here: inf * 0.0
     // text scores would put NaNs into the final scores and leave the winner undefined
@@ -460,7 +461,7 @@ extern "C" int qv_decode_retrieve_rerank_async(qv_engine *eng, const float *lp, 
     QvCtx &c = eng->ctx[eng->cur_ctx];
     qv_stage_mark(eng, c, 0, (hipStream_t)stream);   // no forward in this call: forward = 0
     qv_stage_mark(eng, c, 1, (hipStream_t)stream);
-    int rc = QV_POST(eng, qv_post_run)(eng, c, lp, t_max, t_host, batch, (hipStream_t)stream);
+    int rc = qv_post_run(eng, c, lp, t_max, t_host, batch, (hipStream_t)stream);
     if (rc == QV_OK) align_note(c, lp, t_max, batch, (hipStream_t)stream);
     return rc;
 }
@@ -575,10 +576,10 @@ extern "C" int qv_predict_batch_async(qv_engine *eng, const float *audio_dev, co
     qv_stage_mark(eng, c, 1, run);
     if (eng->inject_lp) {
         if (batch > eng->inject_batch) { qv_set_error(eng, "injected log-probs hold fewer utterances than the batch"); return QV_ERR_ARG; }
-        rc = QV_POST(eng, qv_post_run)(eng, c, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
+        rc = qv_post_run(eng, c, eng->inject_lp, eng->inject_tmax, eng->inject_t.data(), batch, run);
         if (rc == QV_OK) align_note(c, eng->inject_lp, eng->inject_tmax, batch, run);
     } else {
-        rc = QV_POST(eng, qv_post_run)(eng, c, c.logprobs_ws, t_max, t_out.data(), batch, run);
+        rc = qv_post_run(eng, c, c.logprobs_ws, t_max, t_out.data(), batch, run);
         if (rc == QV_OK) align_note(c, c.logprobs_ws, t_max, batch, run);
     }
     if (rc) return rc;
@@ -774,7 +775,7 @@ extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int3
     if (!eng) return QV_ERR_ARG;
     QvCtx &c = eng->ctx[eng->cur_ctx];
     c.al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
-    int rc = QV_POST(eng, qv_post_debug_retrieve)(eng, c, codes_host, n_codes, stream);
+    int rc = qv_post_debug_retrieve(eng, c, codes_host, n_codes, stream);
     if (rc) return rc;
     QvUtt u;
     QV_HIP(hipMemcpy(&u, c.work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));
@@ -812,7 +813,7 @@ extern "C" int qv_tracker_match(qv_engine *eng, const uint8_t *codes_host, const
         }
         if (n > eng->max_q) { qv_set_error(eng, "qv_tracker_match: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     }
-    return QV_POST(eng, qv_post_tracker_match)(eng, codes_host, offsets_host, n_words_host, bonus_verse_host, batch, out_host,
+    return qv_post_tracker_match(eng, codes_host, offsets_host, n_words_host, bonus_verse_host, batch, out_host,
                                  (hipStream_t)stream);
 }
 
@@ -842,7 +843,7 @@ extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t
     QV_TRY(quiesce_contexts(eng));
     QvCtx &c = eng->ctx[eng->cur_ctx];
     c.al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
-    int rc = QV_POST(eng, qv_post_match_verse)(eng, c, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
+    int rc = qv_post_match_verse(eng, c, codes_host, n_codes, n_bonus, bonus_verse, bonus_value, max_span, (hipStream_t)stream);
     if (rc) return rc;
     QvUtt u;
     QV_HIP(hipMemcpy(&u, c.work.utt, sizeof(QvUtt), hipMemcpyDeviceToHost));

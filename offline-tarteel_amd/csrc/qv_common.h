@@ -13,14 +13,6 @@
 #include "qv_limits.h"   // QV_NSYM, QV_OTHER, QV_MAX_SPAN, QV_MAX_VW, qv_tmpl_w
 #include "qv_switches.h"
 
-// The matching window is a compile-time constant of the post-logits kernels (buffer pitches, LDS arrays, the word counts the
-// LCS core is instantiated for).  qv_postlogits.hip is compiled twice: as itself with the default window, and through
-// qv_postlogits_wide.hip with QV_MAXQ = QV_MAX_TRANSCRIPT_WIDE, kernels in namespace qv_wide and launchers named qv_post_*_wide.
-// An engine picks one set at qv_create (qv_engine::max_q, QV_POST).
-#ifndef QV_MAXQ
-#define QV_MAXQ QV_MAX_TRANSCRIPT
-#endif
-#define QV_MAXW (QV_MAXQ / 64)
 #define QV_CAND_CAP 2048
 #define QV_RUNNER_CAP 128
 #define QV_RAW_CAP 4096     // raw (pre-collapse) transcript code units per utterance
@@ -126,9 +118,9 @@ struct QvWork {
     QvUtt *utt;              // [B]
     int16_t *frame_ids;      // [B][t_cap]
     int32_t *greedy;         // [B][t_cap]
-    uint8_t *q;              // [B][QV_MAXQ]   (QV_MAXQ, QV_MAXW: of the kernel set the engine runs -- eng->max_q and max_q / 64)
-    uint8_t *qs;             // [B][QV_MAXQ] spaceless
-    uint64_t *pm;            // [B][2][QV_NSYM][QV_MAXW]  (0: q, 1: spaceless q)
+    uint8_t *q;              // [B][max_q]   (max_q: the window of the kernel set the engine runs -- eng->match->max_q)
+    uint8_t *qs;             // [B][max_q] spaceless
+    uint64_t *pm;            // [B][2][QV_NSYM][max_q / 64]  (0: q, 1: spaceless q)
     int32_t *cand1;          // [B][N]
     int16_t *lcsf;           // [B][N][3] full-string LCS(transcript, text) (clean, alt, nobsm)
     double *fs;              // [B][N][3] fragment scores (clean, alt, nobsm)
@@ -172,7 +164,7 @@ struct QvKnobs {
 #define QV_RESAMPLE_ROWS 1024   // rows per qv_upfirdn_batch / qv_mixdown_batch call
 #define QV_RESAMPLE_SLOTS 16    // calls whose row tables may be in flight on a stream at once
 struct QvTrack {
-    uint8_t *q;          // [CAP * QV_MAXQ] codes of the slice's texts, back to back
+    uint8_t *q;          // [CAP * max_q] codes of the slice's texts, back to back
     int32_t *meta;       // [CAP][4] q_len, n_words, bonus verse, offset in q
     double *part_s;      // [CAP][QV_TRACK_BLOCKS]
     uint64_t *part_k;    // [CAP][QV_TRACK_BLOCKS] verse * 2 + (no_bsm variant matched)
@@ -270,6 +262,28 @@ int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitc
                 const int64_t *n_host, int rows, int window_samples, int margin_frames, qv_long_info *info_host, int32_t *ids_host,
                 float *logp_host, int32_t *first_host, int32_t *last_host, int pitch, hipStream_t stream);
 
+// The matching window is a compile-time constant of the kernels that touch the transcript (buffer pitches, LDS arrays, the
+// word counts the LCS core is instantiated for).  Those kernels -- and only those -- are compiled once per window
+// (qv_match_body.inc through qv_match.hip and qv_match_wide.hip); each compilation defines one QvMatchSet.  qv_create stores
+// a pointer to the set that matches qv_config.max_transcript, and the post-logits launchers launch through it.
+struct QvMatchSet {
+    int max_q;                // the window, 1024 or 2048
+    int decode_threads;       // k_decode's block size
+    int frag_blocks;          // k_frag's grid
+    size_t trigram_lds;       // k_trigram's dynamic LDS behind its n_verses scores
+    void (*k_decode)(QvTables, QvWork, const float *, int, const int32_t *);
+    void (*k_prepare_codes)(QvWork, int);
+    void (*k_trigram)(QvTables, QvWork), (*k_frag)(QvTables, QvWork);
+    void (*k_lcs_full)(QvTables, QvWork, int), (*k_hint_sp)(QvTables, QvWork, int);
+    void (*k_spans)(QvTables, QvWork, QvKnobs), (*k_spans2)(QvTables, QvWork, QvKnobs);
+    void (*k_track)(QvTables, QvTrack);
+    // The one window-independent kernel a set may carry: its own long-target CTC rerank, k_ctc<true, VAR> per wave program
+    // VAR, or nullptr = the one of qv_postlogits.hip.  The wide set has its own (qv_ctc_body.inc says why).
+    void (*k_ctc_long[2])(QvTables, QvWork, QvKnobs, const float *, int);
+};
+// (hidden: unmangled names that are no part of the library's exported C symbols)
+extern const QvMatchSet qv_match_default __attribute__((visibility("hidden"))), qv_match_wide __attribute__((visibility("hidden")));
+
 // post-logits launchers (qv_postlogits.hip); `c` is the execution context whose workspace and staging slots the call uses
 int qv_post_tracker_match(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
                           const int32_t *n_words_host, const int32_t *bonus_host, int batch,
@@ -281,16 +295,6 @@ int qv_post_match_verse(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int
                         const double *bonus_value, int max_span, hipStream_t stream);
 int qv_post_debug_ctc(qv_engine *eng, const float *lp, int T, const uint16_t *tg, const int32_t *lens, int n,
                       float *loss_host, hipStream_t stream);
-// the same launchers over the kernel set of the wide window (qv_postlogits_wide.hip)
-int qv_post_tracker_match_wide(qv_engine *eng, const uint8_t *codes_host, const int32_t *offsets_host,
-                               const int32_t *n_words_host, const int32_t *bonus_host, int batch,
-                               qv_track_match *out_host, hipStream_t stream);
-int qv_post_run_wide(qv_engine *eng, QvCtx &c, const float *logprobs_dev, int t_max, const int32_t *t_host, int batch,
-                     hipStream_t stream);
-int qv_post_debug_retrieve_wide(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, hipStream_t stream);
-int qv_post_match_verse_wide(qv_engine *eng, QvCtx &c, const uint8_t *codes_host, int n, int n_bonus, const int32_t *bonus_verse,
-                             const double *bonus_value, int max_span, hipStream_t stream);
-#define QV_POST(eng, fn) ((eng)->max_q > QV_MAX_TRANSCRIPT ? fn##_wide : fn)
 
 // acoustic model (qv_model.hip)
 struct QvModel;
@@ -373,7 +377,8 @@ struct qv_engine {
     hipStream_t tail_stream = nullptr;
     bool tail_valid = false;
     qv_config cfg;
-    int max_q = QV_MAX_TRANSCRIPT;   // the matching window, 1024 or 2048: which set of post-logits kernels runs (QV_POST)
+    int max_q = QV_MAX_TRANSCRIPT;   // the matching window, 1024 or 2048
+    const QvMatchSet *match = &qv_match_default;   // the matching kernels compiled for that window
     QvKnobs knobs;
     int device;
     std::string last_error;

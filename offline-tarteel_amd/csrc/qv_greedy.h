@@ -1,5 +1,5 @@
 // qv_greedy.h -- the greedy frame path, one definition for every kernel that walks it: the per-frame argmax (k_decode in
-// both compilations of qv_postlogits.hip, k_transcribe, k_long_frames), the collapse of runs of equal frame ids into tokens
+// both compilations of qv_match_body.inc, k_transcribe, k_long_frames), the collapse of runs of equal frame ids into tokens
 // (k_transcribe, k_long_collapse), the two reductions over the tokens' log-probs, and the (score desc, key asc) ordering of
 // the stable top-k selections (qv_postlogits.hip, qv_nbest.hip).  No state; every float reported is a value of the input or
 // the result of the IEEE operations spelled out here, so the kernels that share a helper report the same bits.

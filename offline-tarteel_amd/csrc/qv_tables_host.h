@@ -7,7 +7,7 @@
 //
 // What the kernels assume about the content, and where:
 //   n_verses <= QV_MAX_VERSES    k_lcs_full packs a work item as utterance << 15 | verse << 2 | variant and k_frag takes
-//                                13 bits of verse back out (qv_postlogits.hip); tri_post holds verses as uint16_t
+//                                13 bits of verse back out (qv_match_body.inc); tri_post holds verses as uint16_t
 //   n_tri < 0xFFFF               tri_map holds trigram ids as uint16_t, 0xFFFF = not in the index
 //   tri_keys < 2^18              three 6-bit codes; tri_map has 2^18 entries
 //   text length <= QV_MAX_TEXT   = 64 * QV_MAX_VW codes, all three texts of a verse (text_of hands any of them out).  A verse

@@ -178,6 +178,54 @@ def test_no_product_kernel_spills_or_uses_scratch(tmp_path):
     assert all(any(t in k for t in ("k_lcs_full", "k_frag", "k_spans", "k_track")) for k in sgpr), sgpr
 
 
+def test_only_the_matching_kernels_are_compiled_per_window(tmp_path):
+    """The kernels in namespace qv_wide (the wide matching window's set) are exactly the ones that depend on the window
+    (csrc/qv_match_body.inc), each next to a same-named kernel of the default set; nothing of the once-compiled part of the
+    post-logits chain (csrc/qv_postlogits.hip) exists a second time.  A kernel added to the per-window body without need
+    fails here.  Read from the code objects' AMDGPU notes, as the test above does; no disassembly."""
+    import re
+    import shutil
+    import subprocess
+    from pathlib import Path
+
+    llvm = Path("/opt/rocm/lib/llvm/bin")
+    lib = Path(__file__).resolve().parent.parent / "offline-tarteel_amd" / "libqverse.so"
+    shutil.copy(lib, tmp_path / "libqverse.so")
+    subprocess.run([str(llvm / "llvm-objdump"), "--offloading", "libqverse.so"], cwd=tmp_path, check=True, capture_output=True)
+    objs = sorted(tmp_path.glob("libqverse.so.*gfx950"))
+    assert objs, "no gfx950 code object found in libqverse.so"
+
+    def path_of(symbol):   # the (namespace ..., function) identifiers of an Itanium-mangled kernel symbol
+        m = re.match(r"_ZN?", symbol)
+        assert m, symbol
+        at, parts = m.end(), []
+        while (n := re.match(r"\d+", symbol[at:])):
+            at += n.end()
+            parts.append(symbol[at: at + int(n.group())])
+            at += int(n.group())
+        assert parts, symbol
+        if parts[-1] == "k_ctc" and symbol[at:].startswith("ILb1E"):   # k_ctc<true, VAR>: the long-target instantiations
+            parts[-1] = "k_ctc<true>"
+        return parts
+
+    wide, others = [], set()
+    for o in objs:
+        notes = subprocess.run([str(llvm / "llvm-readelf"), "--notes", str(o)], capture_output=True, text=True, check=True).stdout
+        for blk in notes.split("- .agpr_count:")[1:]:
+            parts = path_of(re.search(r"\.name:\s+(\S+)", blk).group(1))
+            if "qv_wide" in parts:
+                wide.append(parts[-1])
+            else:
+                others.add(parts[-1])
+    # (k_ctc<true, 0> and <true, 1>: the one exception, DESIGN.md 4.19 -- the wide set keeps its own long-target CTC kernel)
+    per_window = ["k_ctc<true>", "k_ctc<true>", "k_decode", "k_frag", "k_hint_sp", "k_lcs_full", "k_prepare_codes", "k_spans", "k_spans2",
+                  "k_track", "k_trigram"]
+    assert sorted(wide) == per_window, sorted(wide)
+    assert set(per_window) <= others, set(per_window) - others
+    once = ("k_ctc", "k_topk", "k_candidates", "k_result", "k_pass1_final", "k_base_final", "k_track_final", "k_init_utts", "k_set_hint")
+    assert not set(once) & set(wide) and set(once) <= others, (wide, set(once) - others)
+
+
 def test_library_has_no_packed_fp32_instructions(tmp_path):
     """No v_pk_add/mul/fma_f32 in any product kernel but the two k_gemm_pk instantiations: round 5 traced the cross-kernel disturbance of k_logmel (DESIGN.md
     section 4, tests/test_gpu_interference.py) to packed-FP32 instructions of the victim wave delivering wrong results in

@@ -34,6 +34,9 @@ def kernels_of(lib: Path, tmp: Path):
                 code.setdefault(name, [])
             elif name and ln.strip() and ln.strip() != "...":   # "...": zero padding up to the next symbol, not code
                 code[name].append(re.sub(r"^\s*[0-9a-f]+:\s*", "", re.sub(r"\s*//.*$", "", ln)).strip())
+        for ins in code.values():                       # s_nop after the last s_endpgm: padding up to the next symbol / the section's end
+            while ins and ins[-1] == "s_nop 0":
+                ins.pop()
         notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(o)], capture_output=True, text=True, check=True).stdout
         for blk in notes.split("- .agpr_count:")[1:]:
             kn = re.search(r"\.name:\s+(\S+)", blk).group(1)

@@ -12,6 +12,10 @@ as token paths with a blank only between equal neighbours (one frame per token: 
 passes) and with 35 % of the tokens replaced (gate fails -> search, pass 3, CTC rerank).  --max-transcript picks the
 engine's matching window (1024 / 2048): the same --chars 500 inputs on both show what the wide kernel set costs for work
 the default set can do, --chars 1400 needs the wide one (the default window withholds those: the row says so).
+
+--dump PATH writes, case after case, the raw qv_result records of the batch and its ranked alternatives at k = 5 (the
+qv_nbest_info records, then the entries, those past a row's n_entries zeroed): run it with two builds of the library
+(QVERSE_LIB) or two settings of a kernel switch and compare the files byte for byte.
 """
 from __future__ import annotations
 
@@ -34,13 +38,14 @@ def main():
     ap.add_argument("--case", type=int, default=-1, help="run only this case (0 = clean / gate passes ... 3 = noisy); default all")
     ap.add_argument("--chars", type=int, default=0, help="transcripts of about this many characters (runs of consecutive ayat) instead of single verses")
     ap.add_argument("--max-transcript", type=int, default=1024, choices=(1024, 2048), help="the engine's matching window")
+    ap.add_argument("--dump", default=None, help="write every case's raw result records and n-best entries (k = 5) to this file")
     args = ap.parse_args()
 
     import numpy as np
     import torch
 
     import offline_tarteel_amd  # noqa: F401
-    from offline_tarteel_amd.engine import Engine
+    from offline_tarteel_amd.engine import RESULT_DTYPE, Engine
     from synth import synth_logits
 
     B, T = args.batch, args.frames
@@ -51,6 +56,7 @@ def main():
     rng = np.random.default_rng(20260630)
     n_verses = len(eng.tables.s["tok_off"]) // 6
     rows = []
+    dump = open(args.dump, "wb") if args.dump else None
     cases = (("clean (gate passes)", 1.0, 8.0), ("corrupted", 2.0, 6.0), ("corrupted more", 2.4, 6.0),
              ("noisy (gate fails -> CTC rerank)", 3.5, 4.0))
     if args.chars:
@@ -90,6 +96,16 @@ def main():
             used += 1
         lp = torch.stack(lps).cuda().contiguous()
         res = eng.decode_retrieve_rerank(lp, [T] * B)
+        if dump:
+            raw = np.zeros(B, dtype=RESULT_DTYPE)
+            t = np.full(B, T, dtype=np.int32)
+            eng._check(eng.lib.qv_decode_retrieve_rerank(eng.h, lp.data_ptr(), t.ctypes.data, B, T, raw.ctypes.data, None, eng._stream()),
+                       "qv_decode_retrieve_rerank")
+            info, ent = eng.nbest_raw(batch=B, k=5)
+            for b in range(B):
+                ent[b, int(info[b]["n_entries"]):] = 0
+            for a in (raw, info, ent):
+                dump.write(a.tobytes())
         for _ in range(3):
             eng.decode_retrieve_rerank(lp, [T] * B, want_text=False)
         regions = []
@@ -109,6 +125,8 @@ def main():
                "mean_transcript_chars": round(sum(len(r["transcript"]) for r in res) / B, 1)}
         rows.append(row)
         print(json.dumps(row), flush=True)
+    if dump:
+        dump.close()
     eng.close()
 
 
