@@ -119,6 +119,7 @@ extern "C" int qv_debug_int4_roundtrip(const float *w, int32_t N, int32_t K, flo
     std::vector<half_t> sc((size_t)N * (K / 128) * 2);
     qv_pack_w4(w, N, K, q.data(), sc.data());
     // walk the device layout exactly as the kernel does (qv_kernels.h: GemmArgs::Wq / wscale)
+    // (restated here on purpose, not qv_w4_put's address function: the round-trip tests check the packer against this walk)
     const int nk = K / 64;
     for (int n = 0; n < N; ++n)
         for (int k = 0; k < K; ++k) {
@@ -140,6 +141,7 @@ extern "C" int qv_debug_int8_roundtrip(const float *w, int32_t N, int32_t K, flo
     std::vector<float> sc((size_t)N);
     qv_pack_w8(w, N, K, q.data(), sc.data());
     // walk the device layout exactly as the kernel does (qv_kernels.h: GemmArgs::W8 / w8scale)
+    // (restated here on purpose, not the packer's address function: the round-trip tests check the packer against this walk)
     const int nk = K / 64;
     for (int n = 0; n < N; ++n)
         for (int k = 0; k < K; ++k) {

@@ -10,9 +10,8 @@
 // time than the whole K loop.
 
 #include "qv_kernels.h"
-#include "qv_gemm_dequant.h"
+#include "qv_gemm_epilogue.h"
 #include "qv_launch_plan.h"
-#include "qv_ort.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,20 +28,6 @@ __device__ __forceinline__ void glds16(const void *g, void *l) {
     // direct global->LDS, 16 B per lane; LDS destination = wave-uniform base + lane * 16
     __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, 0);
 }
-
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-#ifdef QV_GEMM_TRACE
-#define QV_ABL(bit) (g.abl & (bit))
-#define QV_PHASE(slot) do { if (g.phase && tid == 0) g.phase[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (slot)] = wall_clock64(); } while (0)
-#define QV_TRACE(slot) do { if (g.trace && lane == 0 && (wave & 3) == 0) g.trace[(((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave) * 64 + kt_) * 4 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define QV_ABL(bit) false
-#define QV_PHASE(slot) do { } while (0)
-#define QV_TRACE(slot) do { } while (0)
-#endif
-
-constexpr bool epi_is_f32(int epi) { return epi == EPI_RESID || epi == EPI_F32; }
 
 }  // namespace
 
@@ -89,7 +74,7 @@ static void launch_one(const GemmArgs &g, hipStream_t s) {
     dim3 grid(g.N / BN, (g.M + 127) / 128);
     size_t lds = W4 ? NST * ((128 * 64 * 2) + (BN * 32)) + (size_t)BN * (g.K / 128) * 4
                     : W8 ? NST * ((128 * 64 * 2) + (BN * 64)) : NST * ((128 * 64 * 2) + (BN * 64 * 2));
-    size_t epi = epi_is_f32(EPI) ? (size_t)128 * (BN + 4) * 4 : (size_t)128 * (BN + 8) * 2;
+    size_t epi = qv_epi::out_is_f32(EPI) ? (size_t)128 * (BN + 4) * 4 : (size_t)128 * (BN + 8) * 2;
     if (WQ == 88) epi = (size_t)128 * ((EPI == EPI_GLU ? BN / 2 : BN) + 4) * 4 + 128 * 3 * 4;   // f32 staging + per-row range keys and owners
     if (epi > lds) lds = epi;
     // more than 64 KB of dynamic LDS is opted into, once per instantiation and only where needed
@@ -128,96 +113,6 @@ static void launch_shape(const GemmArgs &g, hipStream_t s, bool narrow, int nst)
     }
 }
 
-// Symmetric block-128 int4: per row and per 128 consecutive k, scale = v / -8 where v is the
-// element of largest magnitude (first one on ties), q = clamp(floor(w / scale + 8.5), 0, 15),
-// w' = (q - 8) * half(scale).  oracle/fastconformer_ref.py:quant_dequant_int4 mirrors this exactly.
-void qv_pack_w4(const float *w, int N, int K, uint8_t *q_out, half_t *scale_out) {
-    const int nk = K / 64, nkb = K / 128;
-    for (int n = 0; n < N; ++n) {
-        const float *row = w + (size_t)n * K;
-        for (int kb = 0; kb < nkb; ++kb) {
-            float vmax = 0.f, amax = -1.f;
-            for (int k = 0; k < 128; ++k) {
-                float a = fabsf(row[kb * 128 + k]);
-                if (a > amax) { amax = a; vmax = row[kb * 128 + k]; }
-            }
-            float scale = vmax / -8.0f;
-            float rs = scale != 0.f ? 1.0f / scale : 0.f;
-            scale_out[((size_t)kb * N + n) * 2] = (half_t)scale;
-            scale_out[((size_t)kb * N + n) * 2 + 1] = (half_t)(1024.f + 8.f);  // symmetric: zero point 8
-            for (int k = 0; k < 128; ++k) {
-                float t = row[kb * 128 + k] * rs + 8.0f;
-                int q = (int)floorf(t + 0.5f);
-                q = q < 0 ? 0 : q > 15 ? 15 : q;
-                int kk = kb * 128 + k, kt = kk >> 6, c = (kk & 63) >> 3, e = kk & 7;
-                int nib = (e >> 1) + 4 * (e & 1);  // k = 2p -> nibble p, k = 2p + 1 -> nibble p + 4
-                int pos = c ^ ((n >> 2) & 7);
-                size_t byte = ((size_t)(n >> 6) * nk + kt) * 2048 + (size_t)(n & 63) * 32 + pos * 4 + (nib >> 1);
-                if (nib & 1) q_out[byte] = (uint8_t)((q_out[byte] & 0x0F) | (q << 4));
-                else q_out[byte] = (uint8_t)((q_out[byte] & 0xF0) | q);
-            }
-        }
-    }
-}
-
-// The same device layout from a grid that is GIVEN (a weight file converted from the reference's quantised ONNX carries
-// MatMulNBits' own block scales and zero points, tools/convert_weights.py): w[n][k] = (q - zp[n][kb]) * scale[n][kb] holds
-// exactly in float32, so q = rint(w / scale + zp) returns the file's integer verbatim.  The device then multiplies by
-// half(scale) -- the file's float32 scale rounded once, 2^-11 = 4.9e-4 relative at most -- and subtracts the file's zero point
-// (asymmetric blocks included: the {scale, 1024 + zp} pair format always carried one).  Returns the number of elements
-// that cannot be represented this way (0 for a consistent file): a recovered q that is not an integer in [0, 15] to 1e-3,
-// and every element of a block whose zero point is not an integer in [0, 15] (half(1024 + zp) would round it) or whose
-// scale leaves the normal range of f16 (it would be flushed or overflow on the device).  The caller keeps the dequantised
-// f16 path for such a tensor (tools/convert_weights.py) instead of running it on a grid the file does not have.
-int64_t qv_pack_w4_given(const float *w, int N, int K, const float *scale, const float *zp, uint8_t *q_out, half_t *scale_out) {
-    const int nk = K / 64, nkb = K / 128;
-    int64_t bad = 0;
-    for (int n = 0; n < N; ++n) {
-        const float *row = w + (size_t)n * K;
-        for (int kb = 0; kb < nkb; ++kb) {
-            const float sc = scale[(size_t)n * nkb + kb], z = zp[(size_t)n * nkb + kb];
-            scale_out[((size_t)kb * N + n) * 2] = (half_t)sc;
-            scale_out[((size_t)kb * N + n) * 2 + 1] = (half_t)(1024.f + z);
-            const float asc = fabsf(sc);
-            if (z != nearbyintf(z) || z < 0.f || z > 15.f || (sc != 0.f && (asc < 6.103515625e-05f || asc > 65504.f))) bad += 128;
-            for (int k = 0; k < 128; ++k) {
-                const float t = sc != 0.f ? row[kb * 128 + k] / sc + z : z;
-                int q = (int)nearbyintf(t);
-                if (fabsf(t - (float)q) > 1e-3f || q < 0 || q > 15) ++bad;
-                q = q < 0 ? 0 : q > 15 ? 15 : q;
-                int kk = kb * 128 + k, kt = kk >> 6, c = (kk & 63) >> 3, e = kk & 7;
-                int nib = (e >> 1) + 4 * (e & 1);
-                int pos = c ^ ((n >> 2) & 7);
-                size_t byte = ((size_t)(n >> 6) * nk + kt) * 2048 + (size_t)(n & 63) * 32 + pos * 4 + (nib >> 1);
-                if (nib & 1) q_out[byte] = (uint8_t)((q_out[byte] & 0x0F) | (q << 4));
-                else q_out[byte] = (uint8_t)((q_out[byte] & 0xF0) | q);
-            }
-        }
-    }
-    return bad;
-}
-
-// Per-row symmetric int8: scale = max|w| / 127 (1 for an all-zero row), q = clamp(floor(w / scale + 0.5), -127, 127),
-// stored as q + 128.  oracle/fastconformer_ref.py:quant_dequant_int8 mirrors this exactly.
-void qv_pack_w8(const float *w, int N, int K, uint8_t *q_out, float *scale_out) {
-    const int nk = K / 64;
-    for (int n = 0; n < N; ++n) {
-        const float *row = w + (size_t)n * K;
-        float amax = 0.f;
-        for (int k = 0; k < K; ++k) amax = fmaxf(amax, fabsf(row[k]));
-        const float scale = amax > 0.f ? amax / 127.0f : 1.0f;
-        scale_out[n] = scale;
-        for (int k = 0; k < K; ++k) {
-            float t = row[k] / scale;
-            int q = (int)floorf(t + 0.5f);
-            q = q < -127 ? -127 : q > 127 ? 127 : q;
-            const int kt = k >> 6, c = (k & 63) >> 3;
-            const size_t byte = ((size_t)(n >> 6) * nk + kt) * 4096 + (size_t)(n & 63) * 64 + ((c ^ ((n >> 2) & 7)) << 3) + (k & 7);
-            q_out[byte] = (uint8_t)(q + 128);
-        }
-    }
-}
-
 // ---- measurement hook: HIP-event timing of every GEMM launch, per (epilogue, tile) class ----
 namespace {
 struct GemmProf {
@@ -251,53 +146,27 @@ void qv_gemm_prof_collect(double *ms, double *flops, int *n) {
     g_prof.flops.clear();
 }
 
-static void launch_gemm_inner(int epi, const GemmArgs &g, hipStream_t s, bool narrow, int nst) {
-    if (g.Wi8) {
-        // int8 activations x int8 weights (QV_PREC_ORT_MIXED): the GEMM-shaped convolutions; 128-wide tiles,
-        // register-staged loaders
-        if (g.N % 128 != 0 || !g.wsum || !g.mm_in) abort();
-        switch (epi) {
-            case EPI_GLU: launch_one<EPI_GLU, 128, 88, 2, 1>(g, s); break;
-            case EPI_RESID: launch_one<EPI_RESID, 128, 88, 2, 1>(g, s); break;
-            case EPI_F32: launch_one<EPI_F32, 128, 88, 2, 1>(g, s); break;
-            case EPI_F32_RELU: launch_one<EPI_F32_RELU, 128, 88, 2, 1>(g, s); break;
-            case EPI_F16_RELU: launch_one<EPI_F16_RELU, 128, 88, 2, 1>(g, s); break;
-            default: abort();
+// the 128-wide path of a (weights, epilogue) pair of the table (qv_gemm_epilogue.h): its shape rules, then launch_shape
+struct Launch128 {
+    const GemmArgs &g;
+    hipStream_t s;
+    bool narrow;
+    int nst;
+    template <int EPI, int WQ>
+    bool operator()() const {
+        if constexpr (WQ == 88) {
+            // 128-wide tiles, register-staged loaders
+            if (g.N % 128 != 0 || !g.wsum || !g.mm_in) abort();
+            launch_one<EPI, 128, 88, 2, 1>(g, s);
+        } else if constexpr (WQ == 8) {
+            if (narrow || g.N % 128 != 0) abort();
+            launch_shape<EPI, 8>(g, s, false, nst > 3 ? 3 : nst);
+        } else {
+            launch_shape<EPI, WQ>(g, s, EPI == EPI_GLU ? false : narrow, nst);
         }
-        return;
+        return true;
     }
-    if (g.Wq) {
-        // int4 weights: the Linear layers only (FFN, QKV, attention out, linear_pos)
-        switch (epi) {
-            case EPI_F16: launch_shape<EPI_F16, 4>(g, s, narrow, nst); break;
-            case EPI_F16_SWISH: launch_shape<EPI_F16_SWISH, 4>(g, s, narrow, nst); break;
-            case EPI_RESID: launch_shape<EPI_RESID, 4>(g, s, narrow, nst); break;
-            case EPI_QKV: launch_shape<EPI_QKV, 4>(g, s, narrow, nst); break;
-            default: abort();
-        }
-        return;
-    }
-    if (g.W8) {
-        // int8 weights: the pointwise convolutions of the conv module (GLU and residual epilogues)
-        if (narrow || g.N % 128 != 0) abort();
-        switch (epi) {
-            case EPI_GLU: launch_shape<EPI_GLU, 8>(g, s, false, nst > 3 ? 3 : nst); break;
-            case EPI_RESID: launch_shape<EPI_RESID, 8>(g, s, false, nst > 3 ? 3 : nst); break;
-            default: abort();
-        }
-        return;
-    }
-    switch (epi) {
-        case EPI_F16: launch_shape<EPI_F16, 0>(g, s, narrow, nst); break;
-        case EPI_F16_SWISH: launch_shape<EPI_F16_SWISH, 0>(g, s, narrow, nst); break;
-        case EPI_F16_RELU: launch_shape<EPI_F16_RELU, 0>(g, s, narrow, nst); break;
-        case EPI_RESID: launch_shape<EPI_RESID, 0>(g, s, narrow, nst); break;
-        case EPI_F32: launch_shape<EPI_F32, 0>(g, s, narrow, nst); break;
-        case EPI_QKV: launch_shape<EPI_QKV, 0>(g, s, narrow, nst); break;
-        case EPI_GLU: launch_shape<EPI_GLU, 0>(g, s, false, nst); break;
-        default: abort();
-    }
-}
+};
 
 // what the tile policy (gemm_plan, qv_launch_plan.h) reads of a call
 static GemmShape gemm_shape(int epi, const GemmArgs &g) {
@@ -306,12 +175,12 @@ static GemmShape gemm_shape(int epi, const GemmArgs &g) {
 
 // "k_gemm256<f16_swish>" / "k_gemm<resid,128>": the kernel launch_gemm picks for this call (measurement reports)
 const char *qv_gemm_kernel_name(int epi, const GemmArgs &g, const QvSwitches &sw) {
-    static const char *EPI[8] = {"f16", "f16_swish", "f16_relu", "glu", "resid", "f32", "qkv", "f32_relu"};
     static thread_local char buf[64];
+    const char *name = gemm_epi_name(epi);
     const GemmPlan p = gemm_plan(gemm_shape(epi, g), sw);
-    if (g.Wi8) snprintf(buf, sizeof buf, p.wide ? (p.bm == 192 ? "k_gemm256<%s,a8w8,192>" : "k_gemm256<%s,a8w8>") : "k_gemm<%s,128,a8w8>", EPI[epi]);
-    else if (p.wide) snprintf(buf, sizeof buf, p.bm == 192 ? "k_gemm256<%s,192>" : "k_gemm256<%s>", EPI[epi]);
-    else snprintf(buf, sizeof buf, "k_gemm<%s,%d>", EPI[epi], p.narrow ? 64 : 128);
+    if (g.Wi8) snprintf(buf, sizeof buf, p.wide ? (p.bm == 192 ? "k_gemm256<%s,a8w8,192>" : "k_gemm256<%s,a8w8>") : "k_gemm<%s,128,a8w8>", name);
+    else if (p.wide) snprintf(buf, sizeof buf, p.bm == 192 ? "k_gemm256<%s,192>" : "k_gemm256<%s>", name);
+    else snprintf(buf, sizeof buf, "k_gemm<%s,%d>", name, p.narrow ? 64 : 128);
     return buf;
 }
 
@@ -323,7 +192,7 @@ void launch_gemm(int epi, const GemmArgs &g, hipStream_t s, const QvSwitches &sw
     const GemmPlan p = gemm_plan(gemm_shape(epi, g), sw);
     auto go = [&] {
         if (p.wide && launch_gemm256(epi, g, s, p.bm)) return;
-        launch_gemm_inner(epi, g, s, p.narrow, p.nst);
+        if (!gemm_for_pair(g, epi, Launch128{g, s, p.narrow, p.nst})) abort();   // no kernel for this (weights, epilogue) pair
     };
     if (!g_prof.on) { go(); return; }
     size_t i = g_prof.cls.size();

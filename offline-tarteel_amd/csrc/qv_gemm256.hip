@@ -25,9 +25,7 @@
 // 256-byte (f32) row segment; no block barrier after the K loop's last one, waves drift apart and one wave's
 // stores overlap another's conversion VALU.
 
-#include "qv_kernels.h"
-#include "qv_gemm_dequant.h"
-#include "qv_ort.h"
+#include "qv_gemm_epilogue.h"
 #include "qv_dev_util.h"
 
 #include <stdio.h>
@@ -36,24 +34,8 @@
 #include <type_traits>
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using qv_epi::u32x4;
 typedef half2_t h2_t;
-
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-constexpr bool out_is_f32(int epi) { return epi == EPI_RESID || epi == EPI_F32; }
-
-#ifdef QV_GEMM_TRACE   // dev tool only (tools/gemm256_trace.hip)
-#define QW_ABL(bit) (g.abl & (bit))
-#define QW_PHASE(slot) do { if (g.phase && tid == 0) g.phase[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (slot)] = wall_clock64(); } while (0)
-#define QW_TRACE(kt) do { if (g.trace && lane == 0) g.trace[((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave) * 64 + (kt)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define QW_ABL(bit) false
-#define QW_PHASE(slot) do { } while (0)
-#define QW_TRACE(kt) do { } while (0)
-#endif
-
 }  // namespace
 
 // WQ: 0 = f16 weights, 4 = W4A16 (block-128 int4), 8 = W8A16 (per-channel int8), 88 = A8W8 (QV_PREC_ORT_MIXED: s8
@@ -65,6 +47,7 @@ constexpr bool out_is_f32(int epi) { return epi == EPI_RESID || epi == EPI_F32; 
 // operand bytes per flop.  Products and accumulation order per output element do not depend on MI: the bits are the same.
 template <int EPI, int WQ, int MI>
 __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
+    using namespace qv_epi;
     constexpr bool W4 = WQ == 4, W8 = WQ == 8, I8 = WQ == 88;
     constexpr int BM = 64 * MI, BN = 256, BK = 64;
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = W4 ? BN * BK / 2 : W8 ? BN * BK : BN * BK * 2;
@@ -74,19 +57,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
-    QW_PHASE(0);
-    // XCD-aware tile order (bijective for any tile count): consecutive workgroup ids land on different XCDs;
-    // each XCD gets a contiguous run of tiles, which share A row panels in its private L2
+    QV_PHASE(0);
     const int gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-    int wg = blockIdx.y * gx + blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int wg = xcd_tile(blockIdx.y * gx + blockIdx.x, nwg);
     const int m0 = (wg / gx) * BM, n0 = (wg % gx) * BN;
 
     typedef int i32x16 __attribute__((ext_vector_type(16)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     typedef typename std::conditional<I8, i32x16, f32x16>::type acc_t;
     acc_t acc[MI][2];
 #pragma unroll
@@ -111,7 +87,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
     for (int q = 0; q < MI; ++q) {
         const int row = wave * (8 * MI) + q * 8 + (lane >> 3), c = lane & 7;
-        int grow = (QW_ABL(64) ? 0 : m0) + row;   // (ablation 64: every block loads tile (0, 0) -- all loads hit L2)
+        int grow = (QV_ABL(64) ? 0 : m0) + row;   // (ablation 64: every block loads tile (0, 0) -- all loads hit L2)
         grow = grow < g.M ? grow : g.M - 1;   // rows past M repeat the last one; their outputs are never stored
         offA[q] = (unsigned)(((size_t)grow * g.lda + c * 8) * 2);
         dst[q] = row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
@@ -120,7 +96,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
         for (int q = 0; q < (W4 || W8 ? 0 : 4); ++q) {
             const int row = wave * 32 + q * 8 + (lane >> 3), c = lane & 7;
-            offB[q] = (unsigned)(((size_t)((QW_ABL(64) ? 0 : n0) + row) * g.ldw + c * 8) * 2);
+            offB[q] = (unsigned)(((size_t)((QV_ABL(64) ? 0 : n0) + row) * g.ldw + c * 8) * 2);
             dstB[q] = A_BYTES + row * 128 + ((c ^ ((row >> 1) & 7)) << 4);
         }
     }
@@ -140,27 +116,27 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
     }
     u32x4 ra[MI], rb[NBP];
     auto fetchA = [&](int kt) {
-        if (QW_ABL(8)) return;
+        if (QV_ABL(8)) return;
         const int so = kt * (BK * 2);
 #pragma unroll
         for (int q = 0; q < MI; ++q)
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ra[q]) : "v"(offA[q]), "s"(rsA), "s"(so) : "memory");
     };
     auto fetchB = [&](int kt) {
-        if (QW_ABL(8)) return;
+        if (QV_ABL(8)) return;
         const int so = kt * stepB;
 #pragma unroll
         for (int q = 0; q < NBP; ++q)
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(rb[q]) : "v"(offB[q]), "s"(rsB), "s"(so) : "memory");
     };
     auto putA = [&](int stage) {
-        if (QW_ABL(4)) return;
+        if (QV_ABL(4)) return;
         unsigned char *st = smem + stage * STAGE_BYTES;
 #pragma unroll
         for (int q = 0; q < MI; ++q) *(u32x4 *)(st + dst[q]) = ra[q];
     };
     auto putB = [&](int stage) {
-        if (QW_ABL(4)) return;
+        if (QV_ABL(4)) return;
         unsigned char *st = smem + stage * STAGE_BYTES;
 #pragma unroll
         for (int q = 0; q < NBP; ++q) *(u32x4 *)(st + dstB[q]) = rb[q];
@@ -173,8 +149,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
         const int so = kt * (BK * 2);
 #pragma unroll
         for (int q = 0; q < MI; ++q) {
-            if (!QW_ABL(4)) *(u32x4 *)(st + dst[q]) = ra[q];
-            if (!QW_ABL(8)) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ra[q]) : "v"(offA[q]), "s"(rsA), "s"(so) : "memory");
+            if (!QV_ABL(4)) *(u32x4 *)(st + dst[q]) = ra[q];
+            if (!QV_ABL(8)) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(ra[q]) : "v"(offA[q]), "s"(rsA), "s"(so) : "memory");
         }
     };
     auto swapB = [&](int stage, int kt) {
@@ -182,8 +158,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
         const int so = kt * stepB;
 #pragma unroll
         for (int q = 0; q < NBP; ++q) {
-            if (!QW_ABL(4)) *(u32x4 *)(st + dstB[q]) = rb[q];
-            if (!QW_ABL(8)) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(rb[q]) : "v"(offB[q]), "s"(rsB), "s"(so) : "memory");
+            if (!QV_ABL(4)) *(u32x4 *)(st + dstB[q]) = rb[q];
+            if (!QV_ABL(8)) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(rb[q]) : "v"(offB[q]), "s"(rsB), "s"(so) : "memory");
         }
     };
 
@@ -210,7 +186,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
     __builtin_amdgcn_s_barrier();
 
     struct Frag { half8 a[MI]; half8 b[2]; uint32_t q4[2]; uint2 q8[2]; };
-    QW_PHASE(1);
+    QV_PHASE(1);
     // All eight waves run the same phase.  Fragment reads are software-pipelined under the wave's own MFMAs (two
     // register sets, pinned with sched_barrier); the A pieces of tile kt + 1 are written (and the A pieces of tile
     // kt + 2 requested) behind the first 8 MFMAs of K-tile kt, the W pieces behind the second 8; one barrier per
@@ -218,7 +194,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
     // block running one phase apart (ping-pong: memory phase of waves 0..3 beside the MFMA phase of waves 4..7) and
     // the 8 loads spread two per MFMA group -- neither was faster.
     auto rd = [&](int stage, int ks, Frag &f) {
-        if (QW_ABL(2)) return;
+        if (QV_ABL(2)) return;
         const half_t *sA = (const half_t *)(smem + stage * STAGE_BYTES);
         const half_t *sB = (const half_t *)((const unsigned char *)sA + A_BYTES);
         const int c = ks * 2 + (lane >> 5);
@@ -244,7 +220,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) b[j] = W4 ? dequant8(f.q4[j], sc[j], zo[j]) : W8 ? dequant8_i8(f.q8[j]) : f.b[j];
 #if defined(QV_GEMM_TRACE) && defined(__HIP_DEVICE_COMPILE__)
-        if (QW_ABL(1)) {
+        if (QV_ABL(1)) {
 #pragma unroll
             for (int i = 0; i < MI; ++i) asm volatile("" ::"v"(f.a[i]));
 #pragma unroll
@@ -280,7 +256,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
     // that and are not in: neutral at M = 8064, -4 % on FFN-up / GLU at M = 32,256.
     auto ktile = [&](int kt, auto last_c) {
         constexpr bool LAST = decltype(last_c)::value;
-        QW_TRACE(kt);
+        QV_TRACE_AT(true, (QV_BLOCK * 8 + wave) * 64 + kt);
         const int cur = kt & 1;
         const bool has2 = kt + 2 < nk;
         Frag f0 = {}, f1 = {};
@@ -334,10 +310,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
             bia[j][q] = ldf4(rs_bias, nb + j * 32 + 8 * q + 4 * hi);
             if (W8) scl[j][q] = ldf4(rs_scl, nb + j * 32 + 8 * q + 4 * hi);
         }
-    QW_TRACE(nk);
-    QW_PHASE(2);
+    QV_TRACE_AT(true, (QV_BLOCK * 8 + wave) * 64 + nk);
+    QV_PHASE(2);
 #if defined(QV_GEMM_TRACE) && defined(__HIP_DEVICE_COMPILE__)
-    if (QW_ABL(32)) {   // no epilogue at all (accumulators kept live)
+    if (QV_ABL(32)) {   // no epilogue at all (accumulators kept live)
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -349,12 +325,9 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
     unsigned char *sW = smem + wave * 16384;   // this wave's private staging slice
 
     if constexpr (I8) {
-        // ---- A8W8 epilogue (qv_ort.h; same arithmetic as k_gemm<.., 88, ..>, bit for bit):
-        //   v = float(acc + (128 - zp_x[u]) * wsum[n]) * (s_x[u] * s_w) + bias[n],  u = the row's utterance
-        // wave-private like the f16 epilogues: 32 rows at a time through the wave's own LDS slice.
-        constexpr bool GLU = EPI == EPI_GLU, OUT16 = EPI == EPI_F16_RELU;
-        constexpr bool RELU = EPI == EPI_F16_RELU || EPI == EPI_F32_RELU;
-        constexpr bool FOLD = EPI == EPI_GLU || EPI == EPI_F32_RELU;   // the output feeds another quantiser: track its range
+        // ---- A8W8 epilogue (val_a8w8), wave-private like the f16 epilogues: 32 rows at a time through the
+        // wave's own LDS slice, ranges folded with wave ballots
+        constexpr bool GLU = A8W8<EPI>::GLU, OUT16 = A8W8<EPI>::OUT16, RELU = A8W8<EPI>::RELU, FOLD = A8W8<EPI>::FOLD;
         constexpr int WO = GLU ? 32 : 64;                               // output columns of this wave
         constexpr int LDT = WO + 4;
         float *sO = (float *)sW;
@@ -365,13 +338,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 wsm[j][q] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_ws, (nb + j * 32 + 8 * q + 4 * hi) * 4, 0, 0));
-        auto row_owner = [&](int grow, bool &valid) {
-            valid = true;
-            if (g.row_map) return g.row_map[grow] >> 16;
-            const int u = grow / g.rows_per_utt;
-            valid = (grow - u * g.rows_per_utt) / g.f_per_t < g.len[u];
-            return u;
-        };
         const int nbo = GLU ? n0 / 2 + wn * 32 : nb;
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -382,10 +348,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
             int grow = r0 + l31;
             grow = grow < g.M ? grow : g.M - 1;
             bool valid;
-            const int utt = row_owner(grow, valid);
-            const QParam p = dql_param(g.mm_in + QV_MM_STRIDE * utt);
-            const float srow = p.scale * g.w_scale;
-            const int zc = 128 - (int)p.zp;
+            const int utt = row_owner(g, grow, valid);
+            float srow;
+            int zc;
+            a8w8_row_param(g, utt, srow, zc);
             float mn = INFINITY, mx = -INFINITY;
             f32x4 old[8];
             const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
@@ -405,12 +371,12 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
                     f32x4 av, gv, o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        av[e] = (float)(acc[i][0][q * 4 + e] + zc * wsm[0][q][e]) * srow + bia[0][q][e];
-                        gv[e] = (float)(acc[i][1][q * 4 + e] + zc * wsm[1][q][e]) * srow + bia[1][q][e];
+                        av[e] = val_a8w8<false>(acc[i][0][q * 4 + e], zc, wsm[0][q][e], srow, bia[0][q][e]);
+                        gv[e] = val_a8w8<false>(acc[i][1][q * 4 + e], zc, wsm[1][q][e], srow, bia[1][q][e]);
                     }
                     const f32x4 sg = sigmoid4(gv);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { o[e] = av[e] * sg[e]; mn = fminf(mn, o[e]); mx = fmaxf(mx, o[e]); }
+                    for (int e = 0; e < 4; ++e) { o[e] = av[e] * sg[e]; track(o[e], mn, mx); }
                     *(f32x4 *)(sO + l31 * LDT + 8 * q + 4 * hi) = o;
                 }
             } else {
@@ -421,11 +387,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
                         f32x4 o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float v = (float)(acc[i][j][q * 4 + e] + zc * wsm[j][q][e]) * srow + bia[j][q][e];
-                            if (RELU) v = v > 0.f ? v : 0.f;
-                            o[e] = v;
-                            mn = fminf(mn, v);
-                            mx = fmaxf(mx, v);
+                            o[e] = val_a8w8<RELU>(acc[i][j][q * 4 + e], zc, wsm[j][q][e], srow, bia[j][q][e]);
+                            track(o[e], mn, mx);
                         }
                         *(f32x4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = o;
                     }
@@ -470,7 +433,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
                     f32x4 v = *(const f32x4 *)(sO + r * LDT + cc);
                     if (EPI == EPI_RESID) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = old[k][e] + g.alpha * v[e];
+                        for (int e = 0; e < 4; ++e) v[e] = a8w8_resid(old[k][e], g.alpha, v[e]);
                     }
                     if (r < rows_here) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, (r * g.ldo + nbo + cc) * 4, 0, 0);
                 }
@@ -497,7 +460,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
                         for (int q = 0; q < 4; ++q)
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                sT[(j * 32 + 8 * q + 4 * hi + e) * LDV + ii * 32 + l31] = (half_t)(acc[hh * 2 + ii][j][q * 4 + e] + bia[j][q][e]);
+                                sT[(j * 32 + 8 * q + 4 * hi + e) * LDV + ii * 32 + l31] = val_v(acc[hh * 2 + ii][j][q * 4 + e], bia[j][q][e]);
                 }
             // (MI = 3: the second 64-frame group holds one 32-row fragment -- frames 32 .. 63 of it belong to the next wave)
             const bool mine = hh * 64 + 2 * fp + 1 < 32 * MI;
@@ -510,10 +473,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
                 const half_t v0 = sT[d * LDV + 2 * fp], v1 = sT[d * LDV + 2 * fp + 1];
                 if (pair) {
                     h2_t v = {v0, v1};
-                    *(h2_t *)(vt + ((size_t)(bt0 >> 16) * QV_D + drow) * g.t_pad + (bt0 & 0xFFFF)) = v;
+                    *(h2_t *)(vt + vt_index(g, bt0, drow)) = v;
                 } else {
-                    if (bt0 >= 0) vt[((size_t)(bt0 >> 16) * QV_D + drow) * g.t_pad + (bt0 & 0xFFFF)] = v0;
-                    if (bt1 >= 0) vt[((size_t)(bt1 >> 16) * QV_D + drow) * g.t_pad + (bt1 & 0xFFFF)] = v1;
+                    if (bt0 >= 0) vt[vt_index(g, bt0, drow)] = v0;
+                    if (bt1 >= 0) vt[vt_index(g, bt1, drow)] = v1;
                 }
             }
         }
@@ -534,7 +497,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int r = mb + i * 32 + k * 4 + rr;
-                    if (r < g.M && !QW_ABL(16)) old[k] = ldf4(rs_out, r * g.ldo + nb + cc);
+                    if (r < g.M && !QV_ABL(16)) old[k] = ldf4(rs_out, r * g.ldo + nb + cc);
                 }
             }
 #pragma unroll
@@ -543,22 +506,15 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
                 for (int q = 0; q < 4; ++q) {
                     f32x4 v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = acc[i][j][q * 4 + e];
-                        if (W8) x *= scl[j][q][e];
-                        v[e] = g.alpha * (x + bia[j][q][e]);
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] = val_f32<W8>(acc[i][j][q * 4 + e], W8 ? scl[j][q][e] : 1.f, g.alpha, bia[j][q][e]);
                     *(f32x4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = v;
                 }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int r = mb + i * 32 + k * 4 + rr;
                 f32x4 v = *(const f32x4 *)(sO + (k * 4 + rr) * LDT + cc);
-                if (r >= g.M || QW_ABL(16)) { asm volatile("" ::"v"(v)); continue; }
-                if (EPI == EPI_RESID) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += old[k][e];
-                }
+                if (r >= g.M || QV_ABL(16)) { asm volatile("" ::"v"(v)); continue; }
+                if (EPI == EPI_RESID) add_resid(v, old[k]);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, (r * g.ldo + nb + cc) * 4, 0, 0);
             }
         }
@@ -576,27 +532,14 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                half4 o;
-                f32x4 av, gv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    av[e] = acc[i][0][q * 4 + e];
-                    gv[e] = acc[i][1][q * 4 + e];
-                    if (W8) { av[e] *= scl[0][q][e]; gv[e] *= scl[1][q][e]; }
-                    av[e] += bia[0][q][e];
-                    gv[e] += bia[1][q][e];
-                }
-                const f32x4 sg = sigmoid4(gv);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (half_t)(av[e] * sg[e]);
-                *(half4 *)(sO + l31 * LDT + 8 * q + 4 * hi) = o;
-            }
+            for (int q = 0; q < 4; ++q)
+                *(half4 *)(sO + l31 * LDT + 8 * q + 4 * hi) =
+                    val_glu<W8>(acc[i][0], acc[i][1], q, scl[0][q], scl[1][q], bia[0][q], bia[1][q]);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int r = mb + i * 32 + k * 16 + rr;
                 const u32x4 v = *(const u32x4 *)(sO + (k * 16 + rr) * LDT + cc);
-                if (r < g.M && !QW_ABL(16)) __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (r * g.ldo + nbo + cc) * 2, 0, 0);
+                if (r < g.M && !QV_ABL(16)) __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (r * g.ldo + nbo + cc) * 2, 0, 0);
             }
         }
         return;
@@ -612,25 +555,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm256(GemmArgs g) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    half4 o;
-                    f32x4 xv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xv[e] = acc[i][j][q * 4 + e] + bia[j][q][e];
-                    if (EPI == EPI_F16_SWISH) xv = swish4(xv);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = xv[e];
-                        if (EPI == EPI_F16_RELU) x = x > 0.f ? x : 0.f;
-                        o[e] = (half_t)x;
-                    }
-                    *(half4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = o;
-                }
+                for (int q = 0; q < 4; ++q)
+                    *(half4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = val_f16<EPI>(acc[i][j], q, bia[j][q]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int r = mb + i * 32 + k * 8 + rr;
                 const u32x4 v = *(const u32x4 *)(sO + (k * 8 + rr) * LDT + cc);
-                if (r < g.M && !QW_ABL(16)) __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (r * g.ldo + nb + cc) * 2, 0, 0);
+                if (r < g.M && !QV_ABL(16)) __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (r * g.ldo + nb + cc) * 2, 0, 0);
             }
         }
     }
@@ -665,59 +596,22 @@ static void launch256m(const GemmArgs &g, hipStream_t s) {
     hipLaunchKernelGGL((k_gemm256<EPI, WQ, MI>), dim3(g.N / 256, (g.M + 64 * MI - 1) / (64 * MI)), dim3(512), LDS, s, g);
 }
 
-static thread_local int t_bm = 256;   // tile height of the launch in progress (launch_gemm256's argument)
-template <int EPI, int WQ>
-static void launch256(const GemmArgs &g, hipStream_t s) {
-    if (t_bm == 192) launch256m<EPI, WQ, 3>(g, s);
-    else launch256m<EPI, WQ, 4>(g, s);
-}
+// the wide path of a (weights, epilogue) pair of the table (qv_gemm_epilogue.h); int4: K % 128 == 0, K <= 4096 (scale table in LDS)
+struct Launch256 {
+    const GemmArgs &g;
+    hipStream_t s;
+    int bm;
+    template <int EPI, int WQ>
+    bool operator()() const {
+        if (WQ == 4 && (g.K % 128 != 0 || g.K > 4096)) return false;
+        if (bm == 192) launch256m<EPI, WQ, 3>(g, s);
+        else launch256m<EPI, WQ, 4>(g, s);
+        return true;
+    }
+};
 
-// N % 256 == 0, K % 64 == 0 (int4: K % 128 == 0, K <= 4096 for the scale table in LDS); false = nothing launched
+// N % 256 == 0, K % 64 == 0, a bias, bm = 256 or 192; false = nothing launched
 bool launch_gemm256(int epi, const GemmArgs &g, hipStream_t s, int bm) {
     if (g.N % 256 != 0 || g.K % 64 != 0 || !g.bias || (bm != 256 && bm != 192)) return false;
-    t_bm = bm;
-    if (g.Wi8) {
-        // int8 activations x int8 weights (QV_PREC_ORT_MIXED): the GEMM-shaped convolutions
-        switch (epi) {
-            case EPI_GLU: launch256<EPI_GLU, 88>(g, s); break;
-            case EPI_RESID: launch256<EPI_RESID, 88>(g, s); break;
-            case EPI_F32: launch256<EPI_F32, 88>(g, s); break;
-            case EPI_F32_RELU: launch256<EPI_F32_RELU, 88>(g, s); break;
-            case EPI_F16_RELU: launch256<EPI_F16_RELU, 88>(g, s); break;
-            default: return false;
-        }
-        return true;
-    }
-    if (g.Wq) {
-        // int4 weights: the Linear layers (FFN, QKV, attention out, linear_pos)
-        if (g.K % 128 != 0 || g.K > 4096) return false;
-        switch (epi) {
-            case EPI_F16: launch256<EPI_F16, 4>(g, s); break;
-            case EPI_F16_SWISH: launch256<EPI_F16_SWISH, 4>(g, s); break;
-            case EPI_RESID: launch256<EPI_RESID, 4>(g, s); break;
-            case EPI_QKV: launch256<EPI_QKV, 4>(g, s); break;
-            default: return false;
-        }
-        return true;
-    }
-    if (g.W8) {
-        // int8 weights: the pointwise convolutions of the conv module
-        switch (epi) {
-            case EPI_GLU: launch256<EPI_GLU, 8>(g, s); break;
-            case EPI_RESID: launch256<EPI_RESID, 8>(g, s); break;
-            default: return false;
-        }
-        return true;
-    }
-    switch (epi) {
-        case EPI_F16: launch256<EPI_F16, 0>(g, s); break;
-        case EPI_F16_SWISH: launch256<EPI_F16_SWISH, 0>(g, s); break;
-        case EPI_F16_RELU: launch256<EPI_F16_RELU, 0>(g, s); break;
-        case EPI_RESID: launch256<EPI_RESID, 0>(g, s); break;
-        case EPI_F32: launch256<EPI_F32, 0>(g, s); break;
-        case EPI_QKV: launch256<EPI_QKV, 0>(g, s); break;
-        case EPI_GLU: launch256<EPI_GLU, 0>(g, s); break;
-        default: return false;
-    }
-    return true;
+    return gemm_for_pair(g, epi, Launch256{g, s, bm});
 }

@@ -1,5 +1,8 @@
 // The body of k_gemm / k_gemm_pk (qv_gemm.hip includes this file once per kernel symbol: the two differ only in the target
 // features they are compiled with).  Template parameters EPI, BN, WQ, NST, LD and the argument `GemmArgs g` are in scope.
+// The epilogue's values come from qv_gemm_epilogue.h (shared with k_gemm256); the block-wide LDS staging is this kernel's own.
+#define QV_TRACE(slot) QV_TRACE_AT((wave & 3) == 0, ((QV_BLOCK * 8 + wave) * 64 + kt_) * 4 + (slot))
+    using namespace qv_epi;
     constexpr bool W4 = WQ == 4, W8 = WQ == 8;
     // A8W8 (QV_PREC_ORT_MIXED): both operands are bytes and K counts byte PAIRS, so loaders, LDS image and fragment
     // reads are the f16 kernel's unchanged -- a 16-byte fragment chunk is 16 k values for v_mfma_i32_32x32x32_i8
@@ -21,18 +24,11 @@
     const bool loader = wave >= 4;
     const int w4 = wave & 3;                     // index inside the consumer / loader group
     const int wm = w4 >> 1, wn = w4 & 1;
-    // XCD-aware tile order: consecutive workgroup ids land on different XCDs (id % 8); give each XCD
-    // a contiguous run of tiles that share the A row panel so its private L2 sees the reuse.
     const int gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-    int wg = blockIdx.y * gx + blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int wg = xcd_tile(blockIdx.y * gx + blockIdx.x, nwg);
     const int m0 = (wg / gx) * BM, n0 = (wg % gx) * BN;
 
     typedef int i32x16 __attribute__((ext_vector_type(16)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     typedef typename std::conditional<I8, i32x16, f32x16>::type acc_t;
     acc_t acc[2][NF];
 #pragma unroll
@@ -340,24 +336,12 @@
     };
 
     if constexpr (I8) {
-        // ---- A8W8 epilogue (qv_ort.h): int32 accumulator -> float32, per-utterance activation scale, bias, activation.
-        //   v = float(acc + (128 - zp_x[u]) * wsum[n]) * (s_x[u] * s_w) + bias[n]
-        // The int32 sum is < 2^24 in magnitude (K <= 512 products of |255| x |127|), so the conversion is exact and v
-        // carries exactly the two roundings the reference's Cast -> Mul -> Add chain has.
-        constexpr bool GLU = EPI == EPI_GLU, OUT16 = EPI == EPI_F16_RELU;
-        constexpr bool RELU = EPI == EPI_F16_RELU || EPI == EPI_F32_RELU;
-        constexpr bool FOLD = EPI == EPI_GLU || EPI == EPI_F32_RELU;   // the output feeds another quantiser: track its range
+        // ---- A8W8 epilogue (val_a8w8): the whole tile is staged as float32, ranges folded block-wide
+        constexpr bool GLU = A8W8<EPI>::GLU, OUT16 = A8W8<EPI>::OUT16, RELU = A8W8<EPI>::RELU, FOLD = A8W8<EPI>::FOLD;
         constexpr int BNO = GLU ? BN / 2 : BN;
         constexpr int LDT = BNO + 4;                                   // floats per staged row
         float *sO = (float *)smem;
         uint32_t *sMM = (uint32_t *)(smem + BM * LDT * 4);             // [BM][2] range keys of the tile's rows
-        auto row_owner = [&](int grow, bool &valid) {
-            valid = true;
-            if (g.row_map) return g.row_map[grow] >> 16;
-            const int u = grow / g.rows_per_utt;
-            valid = (grow - u * g.rows_per_utt) / g.f_per_t < g.len[u];
-            return u;
-        };
         if (FOLD) {
             for (int k = tid; k < BM * 2; k += NT) sMM[k] = (k & 1) ? 0u : 0xFFFFFFFFu;   // empty range
             __syncthreads();
@@ -371,9 +355,7 @@
                 int grow = m0 + wm * 64 + i * 32 + l31;
                 grow = grow < g.M ? grow : g.M - 1;
                 bool valid;
-                const QParam p = dql_param(g.mm_in + QV_MM_STRIDE * row_owner(grow, valid));
-                srow[i] = p.scale * g.w_scale;
-                zc[i] = 128 - (int)p.zp;
+                a8w8_row_param(g, row_owner(g, grow, valid), srow[i], zc[i]);
             }
             float mn[2] = {INFINITY, INFINITY}, mx[2] = {-INFINITY, -INFINITY};
             if (GLU) {
@@ -391,16 +373,12 @@
                         f32x4 o, av, gv;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            av[e] = (float)(acc[i][0][q * 4 + e] + zc[i] * wa[e]) * srow[i] + ba[e];
-                            gv[e] = (float)(acc[i][NF - 1][q * 4 + e] + zc[i] * wg[e]) * srow[i] + bg[e];
+                            av[e] = val_a8w8<false>(acc[i][0][q * 4 + e], zc[i], wa[e], srow[i], ba[e]);
+                            gv[e] = val_a8w8<false>(acc[i][NF - 1][q * 4 + e], zc[i], wg[e], srow[i], bg[e]);
                         }
-                        const f32x4 sg = sigmoid4(gv);   // (v_exp_f32 / v_rcp_f32: a few 1e-7 relative, like any libm's expf)
+                        const f32x4 sg = sigmoid4(gv);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            o[e] = av[e] * sg[e];
-                            mn[i] = fminf(mn[i], o[e]);
-                            mx[i] = fmaxf(mx[i], o[e]);
-                        }
+                        for (int e = 0; e < 4; ++e) { o[e] = av[e] * sg[e]; track(o[e], mn[i], mx[i]); }
                         *(f32x4 *)(sO + rl * LDT + wn * (WN / 2) + nl) = o;
                     }
                 }
@@ -418,11 +396,8 @@
                             f32x4 o;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                float v = (float)(acc[i][j][q * 4 + e] + zc[i] * ws[e]) * srow[i] + bb[e];
-                                if (RELU) v = v > 0.f ? v : 0.f;
-                                o[e] = v;
-                                mn[i] = fminf(mn[i], v);
-                                mx[i] = fmaxf(mx[i], v);
+                                o[e] = val_a8w8<RELU>(acc[i][j][q * 4 + e], zc[i], ws[e], srow[i], bb[e]);
+                                track(o[e], mn[i], mx[i]);
                             }
                             *(f32x4 *)(sO + rl * LDT + cl) = o;
                         }
@@ -446,7 +421,7 @@
             if (tid < BM) {
                 bool valid = false;
                 int u = -1;
-                if (m0 + tid < g.M) u = row_owner(m0 + tid, valid);
+                if (m0 + tid < g.M) u = row_owner(g, m0 + tid, valid);
                 sU[tid] = valid && sMM[2 * tid] <= sMM[2 * tid + 1] ? u : -1;
             }
             __syncthreads();
@@ -491,7 +466,7 @@
                 f32x4 v = *(const f32x4 *)(sO + r * LDT + c);
                 if (EPI == EPI_RESID) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = old[k][e] + g.alpha * v[e];
+                    for (int e = 0; e < 4; ++e) v[e] = a8w8_resid(old[k][e], g.alpha, v[e]);
                 }
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs_out, (r * g.ldo + n0o + c) * 4, 0, 0);
             }
@@ -517,7 +492,7 @@
                     for (int i = 0; i < 2; ++i) {
                         const int rl = wm * 64 + i * 32 + l31;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) sT[(cl + e) * LDV + rl] = (half_t)(acc[i][j][q * 4 + e] + bb[e]);
+                        for (int e = 0; e < 4; ++e) sT[(cl + e) * LDV + rl] = val_v(acc[i][j][q * 4 + e], bb[e]);
                     }
                 }
         }
@@ -532,10 +507,10 @@
             const half_t v0 = sT[d * LDV + 2 * lane], v1 = sT[d * LDV + 2 * lane + 1];
             if (pair) {
                 half2_t v = {v0, v1};
-                *(half2_t *)(vt + ((size_t)(bt0 >> 16) * QV_D + drow) * g.t_pad + (bt0 & 0xFFFF)) = v;
+                *(half2_t *)(vt + vt_index(g, bt0, drow)) = v;
             } else {
-                if (bt0 >= 0) vt[((size_t)(bt0 >> 16) * QV_D + drow) * g.t_pad + (bt0 & 0xFFFF)] = v0;
-                if (bt1 >= 0) vt[((size_t)(bt1 >> 16) * QV_D + drow) * g.t_pad + (bt1 & 0xFFFF)] = v1;
+                if (bt0 >= 0) vt[vt_index(g, bt0, drow)] = v0;
+                if (bt1 >= 0) vt[vt_index(g, bt1, drow)] = v1;
             }
         }
         QV_PHASE(3);
@@ -555,7 +530,7 @@
             }
     }
 
-    if (epi_is_f32(EPI)) {
+    if (out_is_f32(EPI)) {
         constexpr int LDT = BN + 4;  // floats per staged row (pad keeps 16-B alignment)
         float *sO = (float *)smem;
 #pragma unroll
@@ -570,11 +545,7 @@
                     f32x4 v;
                     const f32x4 bb = bia[j][q];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = acc[i][j][q * 4 + e];
-                        if (W8) x *= scl[j][q][e];
-                        v[e] = g.alpha * (x + bb[e]);
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] = val_f32<W8>(acc[i][j][q * 4 + e], W8 ? scl[j][q][e] : 1.f, g.alpha, bb[e]);
                     *(f32x4 *)(sO + rl * LDT + cl) = v;
                 }
         }
@@ -598,10 +569,7 @@
             int idx = tid + k * NT, r = idx / CPR, c = (idx % CPR) * 4;
             if (m0 + r >= g.M) continue;
             f32x4 v = *(const f32x4 *)(sO + r * LDT + c);
-            if (EPI == EPI_RESID) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += old[k][e];
-            }
+            if (EPI == EPI_RESID) add_resid(v, old[k]);
             if (QV_ABL(16)) { asm volatile("" ::"v"(v)); continue; }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs_out, ((m0 + r) * g.ldo + n0 + c) * 4, 0, 0);
         }
@@ -627,20 +595,7 @@
                     f32x4 ba = ldf4(rs_bias, nb + nl), bg = ldf4(rs_bias, nb + 32 + nl);
                     f32x4 sa = {1.f, 1.f, 1.f, 1.f}, sg = sa;
                     if (W8) { sa = ldf4(rs_scl, nb + nl); sg = ldf4(rs_scl, nb + 32 + nl); }
-                    half4 o;
-                    f32x4 av, gv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        av[e] = acc[i][0][q * 4 + e];
-                        gv[e] = acc[i][NF - 1][q * 4 + e];
-                        if (W8) { av[e] *= sa[e]; gv[e] *= sg[e]; }
-                        av[e] += ba[e];
-                        gv[e] += bg[e];
-                    }
-                    const f32x4 sgm = sigmoid4(gv);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (half_t)(av[e] * sgm[e]);
-                    *(half4 *)(sO + rl * LDT + wn * (WN / 2) + nl) = o;
+                    *(half4 *)(sO + rl * LDT + wn * (WN / 2) + nl) = val_glu<W8>(acc[i][0], acc[i][NF - 1], q, sa, sg, ba, bg);
                 }
                 continue;
             }
@@ -650,18 +605,7 @@
                 for (int q = 0; q < 4; ++q) {
                     const int cl = wn * WN + j * 32 + 8 * q + 4 * hi;
                     const f32x4 bb = bia[j][q];
-                    half4 o;
-                    f32x4 xv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xv[e] = acc[i][j][q * 4 + e] + bb[e];
-                    if (EPI == EPI_F16_SWISH) xv = swish4(xv);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = xv[e];
-                        if (EPI == EPI_F16_RELU) x = x > 0.f ? x : 0.f;
-                        o[e] = (half_t)x;
-                    }
-                    *(half4 *)(sO + rl * LDT + cl) = o;
+                    *(half4 *)(sO + rl * LDT + cl) = val_f16<EPI>(acc[i][j], q, bb);
                 }
         }
         __syncthreads();
@@ -675,3 +619,4 @@
         }
         QV_PHASE(3);
     }
+#undef QV_TRACE

@@ -208,7 +208,7 @@ def damped_weights(seed: int = 20260630, branch: float = 0.25, head: float = 0.1
 # the rule below (block 128, scale = extreme value / -8, zero point 8) restates MLAS's symmetric
 # Q4 blockwise quantiser and is UNPINNED like the rest of this file.  The device format carries a
 # per-block zero point, so an asymmetric file maps onto it unchanged.]
-# qv_pack_w4 (offline-tarteel_amd/csrc/qv_gemm.hip) performs the identical f32 arithmetic.
+# qv_pack_w4 (offline-tarteel_amd/csrc/qv_wpack_host.h) performs the identical f32 arithmetic.
 def quant_dequant_int4(w2d: np.ndarray, block: int = 128) -> np.ndarray:
     """[N][K] f32 -> the f32 matrix the W4A16 GEMM effectively multiplies by."""
     w2d = np.ascontiguousarray(w2d, dtype=np.float32)
@@ -229,7 +229,7 @@ def quant_dequant_int4(w2d: np.ndarray, block: int = 128) -> np.ndarray:
 def quant_dequant_int8(w2d: np.ndarray) -> np.ndarray:
     """[N][K] f32 -> the f32 matrix the W8A16 GEMM effectively multiplies by: per-row symmetric int8,
     scale = max|w| / 127 (1 for an all-zero row), q = clip(floor(w / scale + 0.5), -127, 127)
-    (csrc/qv_gemm.hip::qv_pack_w8)."""
+    (csrc/qv_wpack_host.h::qv_pack_w8)."""
     w2d = np.ascontiguousarray(w2d, dtype=np.float32)
     amax = np.abs(w2d).max(axis=1, keepdims=True).astype(np.float32)
     scale = np.where(amax > 0, amax / np.float32(127.0), np.float32(1.0)).astype(np.float32)

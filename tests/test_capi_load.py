@@ -226,6 +226,40 @@ def test_only_the_matching_kernels_are_compiled_per_window(tmp_path):
     assert not set(once) & set(wide) and set(once) <= others, (wide, set(once) - others)
 
 
+def test_both_gemm_tile_kernels_exist_for_the_same_pairs(tmp_path):
+    """The 128-wide and the 256-wide GEMM launchers instantiate from one table of (weights, epilogue) pairs
+    (csrc/qv_gemm_epilogue.h::gemm_for_pair): k_gemm256<EPI, WQ, 4>, k_gemm256<EPI, WQ, 3> and k_gemm / k_gemm_pk<EPI, 128, WQ,
+    2, 1> (the register-staged 128-wide kernel every pair has) exist for the same 18 pairs.  Kernel names only, read from the
+    code objects' AMDGPU notes as the tests above do."""
+    import re
+    import shutil
+    import subprocess
+    from pathlib import Path
+
+    llvm = Path("/opt/rocm/lib/llvm/bin")
+    lib = Path(__file__).resolve().parent.parent / "offline-tarteel_amd" / "libqverse.so"
+    shutil.copy(lib, tmp_path / "libqverse.so")
+    subprocess.run([str(llvm / "llvm-objdump"), "--offloading", "libqverse.so"], cwd=tmp_path, check=True, capture_output=True)
+    objs = sorted(tmp_path.glob("libqverse.so.*gfx950"))
+    assert objs, "no gfx950 code object found in libqverse.so"
+    wide = {3: set(), 4: set()}
+    narrow = set()
+    for o in objs:
+        notes = subprocess.run([str(llvm / "llvm-readelf"), "--notes", str(o)], capture_output=True, text=True, check=True).stdout
+        for name in re.findall(r"\.name:\s+(\S+)", notes):
+            if (m := re.fullmatch(r"_Z9k_gemm256ILi(\d+)ELi(\d+)ELi(\d+)EEv8GemmArgs", name)):
+                wide[int(m.group(3))].add((int(m.group(1)), int(m.group(2))))
+            elif (m := re.fullmatch(r"_Z(?:6k_gemm|9k_gemm_pk)ILi(\d+)ELi128ELi(\d+)ELi2ELi1EEv8GemmArgs", name)):
+                narrow.add((int(m.group(1)), int(m.group(2))))
+    F16, SWISH, RELU, GLU, RESID, F32, QKV, F32_RELU = range(8)   # the EPI_ enum of csrc/qv_kernels.h
+    pairs = ({(e, 88) for e in (GLU, RESID, F32, F32_RELU, RELU)} | {(e, 4) for e in (F16, SWISH, RESID, QKV)}
+             | {(e, 8) for e in (GLU, RESID)} | {(e, 0) for e in (F16, SWISH, RELU, RESID, F32, QKV, GLU)})
+    assert len(pairs) == 18
+    assert wide[4] == pairs, sorted(wide[4] ^ pairs)
+    assert wide[3] == pairs, sorted(wide[3] ^ pairs)
+    assert narrow == pairs, sorted(narrow ^ pairs)
+
+
 def test_library_has_no_packed_fp32_instructions(tmp_path):
     """No v_pk_add/mul/fma_f32 in any product kernel but the two k_gemm_pk instantiations: round 5 traced the cross-kernel disturbance of k_logmel (DESIGN.md
     section 4, tests/test_gpu_interference.py) to packed-FP32 instructions of the victim wave delivering wrong results in

@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev: the log-probs of a ragged seeded batch from two library builds, compared bitwise (tools/ab_forward.py)
-#   bash tools/dev_lib_bitwise.sh A/libqverse.so B/libqverse.so [--variant N] [--frames T ...]
+#   bash tools/dev_lib_bitwise.sh A/libqverse.so B/libqverse.so [--variant N] [--precision P] [--gemm-tiles T] [--gemm-tile-height H] [--frames T ...]
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"

@@ -32,6 +32,7 @@ template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { st
 template <int EPI, int WQ>
 __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
     static_assert(WQ == 0 || WQ == 4 || WQ == 8, "f16 activations only");
+    using namespace qv_epi;   // the epilogue arithmetic is the library kernels' (csrc/qv_gemm_epilogue.h)
     constexpr bool W4 = WQ == 4, W8 = WQ == 8;
     constexpr int BM = 256, BN = 256, BK = 64;
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = W4 ? BN * BK / 2 : W8 ? BN * BK : BN * BK * 2;
@@ -45,11 +46,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-    int wg = blockIdx.y * gx + blockIdx.x;
-    {   // XCD-aware tile order, as in k_gemm256
-        int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int wg = xcd_tile(blockIdx.y * gx + blockIdx.x, nwg);
     const int m0 = (wg / gx) * BM, n0 = (wg % gx) * BN;
 
     f32x16 acc[4][4];
@@ -257,7 +254,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
                         for (int q = 0; q < 4; ++q)
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                sT[(j * 32 + 8 * q + 4 * hi + e) * LDV + ii * 32 + l31] = (half_t)(acc[hh * 2 + ii][2 * jh + j][q * 4 + e] + b4[q][e]);
+                                sT[(j * 32 + 8 * q + 4 * hi + e) * LDV + ii * 32 + l31] = val_v(acc[hh * 2 + ii][2 * jh + j][q * 4 + e], b4[q][e]);
                 }
                 const int r0 = mb + hh * 64 + 2 * fp, r1 = r0 + 1;
                 const int bt0 = r0 < g.M ? g.row_map[r0] : -1, bt1 = r1 < g.M ? g.row_map[r1] : -1;
@@ -268,10 +265,10 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
                     const half_t v0 = sT[d * LDV + 2 * fp], v1 = sT[d * LDV + 2 * fp + 1];
                     if (pair) {
                         h2_t v = {v0, v1};
-                        *(h2_t *)(vt + ((size_t)(bt0 >> 16) * QV_D + drow) * g.t_pad + (bt0 & 0xFFFF)) = v;
+                        *(h2_t *)(vt + vt_index(g, bt0, drow)) = v;
                     } else {
-                        if (bt0 >= 0) vt[((size_t)(bt0 >> 16) * QV_D + drow) * g.t_pad + (bt0 & 0xFFFF)] = v0;
-                        if (bt1 >= 0) vt[((size_t)(bt1 >> 16) * QV_D + drow) * g.t_pad + (bt1 & 0xFFFF)] = v1;
+                        if (bt0 >= 0) vt[vt_index(g, bt0, drow)] = v0;
+                        if (bt1 >= 0) vt[vt_index(g, bt1, drow)] = v1;
                     }
                 }
             }
@@ -302,11 +299,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
                 for (int q = 0; q < 4; ++q) {
                     f32x4 v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = acc[i][j][q * 4 + e];
-                        if (W8) x *= s4[q][e];
-                        v[e] = g.alpha * (x + b4[q][e]);
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] = val_f32<W8>(acc[i][j][q * 4 + e], W8 ? s4[q][e] : 1.f, g.alpha, b4[q][e]);
                     *(f32x4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = v;
                 }
             }
@@ -315,10 +308,7 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
                 const int r = mb + i * 32 + k * 2 + rr;
                 f32x4 v = *(const f32x4 *)(sO + (k * 2 + rr) * LDT + cc);
                 if (r >= g.M) { asm volatile("" ::"v"(v)); continue; }
-                if (EPI == EPI_RESID) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += old[k][e];
-                }
+                if (EPI == EPI_RESID) add_resid(v, old[k]);
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_out, (r * g.ldo + nb + cc) * 4, 0, 0);
             }
         }
@@ -341,22 +331,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
                 col_tab(2 * pr, ba, sa);
                 col_tab(2 * pr + 1, bg, sg4);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    half4 o;
-                    f32x4 av, gv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        av[e] = acc[i][2 * pr][q * 4 + e];
-                        gv[e] = acc[i][2 * pr + 1][q * 4 + e];
-                        if (W8) { av[e] *= sa[q][e]; gv[e] *= sg4[q][e]; }
-                        av[e] += ba[q][e];
-                        gv[e] += bg[q][e];
-                    }
-                    const f32x4 sg = sigmoid4(gv);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = (half_t)(av[e] * sg[e]);
-                    *(half4 *)(sO + l31 * LDT + pr * 32 + 8 * q + 4 * hi) = o;
-                }
+                for (int q = 0; q < 4; ++q)
+                    *(half4 *)(sO + l31 * LDT + pr * 32 + 8 * q + 4 * hi) = val_glu<W8>(acc[i][2 * pr], acc[i][2 * pr + 1], q, sa[q], sg4[q], ba[q], bg[q]);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -380,20 +356,8 @@ __global__ __launch_bounds__(256, 1) void k_gemm256q(GemmArgs g) {
                 f32x4 b4[4], s4[4];
                 col_tab(j, b4, s4);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    half4 o;
-                    f32x4 xv;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xv[e] = acc[i][j][q * 4 + e] + b4[q][e];
-                    if (EPI == EPI_F16_SWISH) xv = swish4(xv);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = xv[e];
-                        if (EPI == EPI_F16_RELU) x = x > 0.f ? x : 0.f;
-                        o[e] = (half_t)x;
-                    }
-                    *(half4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = o;
-                }
+                for (int q = 0; q < 4; ++q)
+                    *(half4 *)(sO + l31 * LDT + j * 32 + 8 * q + 4 * hi) = val_f16<EPI>(acc[i][j], q, b4[q]);
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {

@@ -31,10 +31,8 @@
 #include "logmel_variants.h"
 // victims 20-23: the GEMM kernels (their two translation units keep packed-FP32 instructions in the product build; only the
 // `_pk` flavour of the probe compiles them as shipped)
-#define sigmoidf_ sigmoidf_gemm_tu_
 #include "../offline-tarteel_amd/csrc/qv_gemm.hip"
 #include "../offline-tarteel_amd/csrc/qv_gemm256.hip"
-#undef sigmoidf_
 
 #include <cstdio>
 #include <cstdlib>
