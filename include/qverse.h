@@ -347,6 +347,80 @@ int qv_nbest_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, int32_t k, in
 int qv_nbest_select(qv_engine *e, const double *final_host, const float *loss_host, const int32_t *n_host,
                     int32_t rows, int32_t pitch, int32_t k, int32_t *index_host, int32_t *count_host, void *stream);
 
+/* ---- recitation correction: word-level errors against the verse ------------------------------------
+ * Which words did the reciter get wrong?  The reference answers with a Levenshtein alignment under a fixed tie rule
+ * (shared/phoneme_aligner.py: align_phonemes) folded into words (web/frontend/src/lib/correction.ts: computeCorrection);
+ * there it runs on phonemes, here on alphabet codes.  Every output is an integer.
+ *   symbols     code 0 (space) is never a symbol, it only separates words.  pred / ref = the predicted / reference text with
+ *               its spaces removed, m = |pred|, n = |ref|; word(r) = number of spaces in front of reference symbol r in the
+ *               reference text; n_words = 1 + number of spaces in the reference text (runs of spaces in an explicit text make
+ *               words without symbols).  Codes compare by plain equality: 63 is an ordinary symbol.
+ *   DP          dp[i][0] = i, dp[0][j] = j;  sub = dp[i-1][j-1] + (ref[i-1] != pred[j-1]), del = dp[i-1][j] + 1,
+ *               ins = dp[i][j-1] + 1, dp[i][j] = min of the three; the move is S if dp[i][j] == sub, else D if == del, else I
+ *               (phoneme_aligner.py:75-89, ties in that order).
+ *   backtrace   from (n, m) to (0, 0): at i == 0 the move is I, at j == 0 it is D; the list is then reversed.  One op code per
+ *               alignment column: 0 match (S, equal), 1 substitution (S, unequal), 2 deletion (D), 3 insertion (I).  The
+ *               position of a column = reference symbols consumed before it (phoneme_aligner.py:116-148).
+ *   words       a column at position p belongs to word(p) if p < n, else to word(n - 1): trailing insertions go to the last
+ *               word (correction.ts:60-78).  Per word: n_match, n_sub, n_del, n_ins, n_symbols = n_match + n_sub + n_del (the
+ *               word's aligned symbols) and type = 0 without an error, 1 with any substitution, else the op code of its first
+ *               error in alignment order (2 or 3).
+ *   prefix      QV_CORRECT_PREFIX, for a recitation in progress (what computeCorrection's maxWordIndex approximates by hand):
+ *               the backtrace starts at (i*, m), i* = the smallest i in 0..n that minimises dp[i][m]; reference symbols >= i*
+ *               are not part of the alignment and words that own none of the aligned symbols report zeros (the word of symbol
+ *               i* still receives the trailing insertions: position i* follows the rule above).  n_ref_used = i* (n without
+ *               the flag), words_touched = words that own a symbol < i*, QV_CORRECT_LAST_WORD_OPEN = symbols i*-1 and i* belong
+ *               to one word.
+ *   per row     qv_correct_info; distance = dp[i*][m] = n_sub + n_del + n_ins, n_ops = alignment columns.  The reference's per
+ *               and correct_rate are distance / n_ref_used and n_match / n_ref_used: left to the caller.
+ *   row flags   QV_CORRECT_NO_TARGET: n == 0 or the row has no prediction; QV_CORRECT_NO_TRANSCRIPT: m == 0 (computeCorrection's
+ *               empty return); QV_CORRECT_TOO_LONG: n > QV_CORRECT_MAX_REF, m > qv_max_transcript(e) or n_words >
+ *               QV_CORRECT_MAX_WORDS.  A row that carries one of the three returns no ops and no words and every other info
+ *               field 0.
+ * The longest spaceless text of a (verse, span <= 6) in the shipped tables has 1,223 symbols and the wordiest 280 words
+ * (tests/test_correct_host.py walks the tables); the longest single verse has 551 symbols.
+ * Outputs: ops_host[row * ops_pitch + c] = op code of column c, 0xFF past n_ops, ops_pitch >= QV_CORRECT_MAX_REF +
+ * qv_max_transcript(e); words_host[row * words_pitch + w], zeroed past n_words, words_pitch >= QV_CORRECT_MAX_WORDS.  Either
+ * may be NULL.  Both calls are SYNCHRONOUS.  The workspace belongs to the execution context and is allocated by the first
+ * call that uses it: per row of max_batch a record of 64 + (1280 + window) + 12 * 288 bytes in device memory and pinned,
+ * 4,096 bytes of staged codes (explicit entry), and for min(max_batch, 64) rows the back-pointers -- 2 bits per DP cell,
+ * (1280 + window + 1) diagonals of 81 words: 746,820 bytes per row with the default window, 1,078,596 with the wide one.
+ * More than 64 rows run in rounds of 64 inside one call; one device-to-host copy per call. */
+#define QV_CORRECT_MAX_REF 1280
+#define QV_CORRECT_MAX_WORDS 288
+#define QV_CORRECT_MAX_RAW 2048          /* codes of one explicit text, spaces included */
+enum { QV_CORRECT_PREFIX = 1 };          /* call flag */
+enum { QV_CORRECT_NO_TARGET = 1, QV_CORRECT_NO_TRANSCRIPT = 2, QV_CORRECT_TOO_LONG = 4, QV_CORRECT_LAST_WORD_OPEN = 8 };   /* row flags */
+typedef struct {
+    int32_t n_ref, n_pred, n_words, n_ref_used, words_touched, distance;
+    int32_t n_match, n_sub, n_del, n_ins, n_ops, flags;
+    int32_t start_verse, span;            /* the winner's text (results entry); -1, 0 for explicit texts */
+    int32_t reserved[2];
+} qv_correct_info;
+typedef struct { uint16_t n_symbols, n_match, n_sub, n_del, n_ins, type; } qv_correct_word;
+
+/* explicit texts as alphabet codes WITH their spaces, concatenated: row r compares pred_codes_host[pred_off_host[r] ..
+ * pred_off_host[r+1]) with ref_codes_host[ref_off_host[r] .. ref_off_host[r+1]) (offsets as in qv_tracker_match).  Works on
+ * an engine without a model; uses the current context's workspace and leaves its batch alone.  Null pointer (the outputs
+ * ops_host / words_host excepted), rows < 1, unknown flags, decreasing offsets, a text of more than QV_CORRECT_MAX_RAW codes
+ * or a pitch below its cap: QV_ERR_ARG, before anything is launched; rows above max_batch: QV_ERR_CAPACITY. */
+int qv_correct(qv_engine *e, const uint8_t *pred_codes_host, const int32_t *pred_off_host,
+               const uint8_t *ref_codes_host, const int32_t *ref_off_host, int32_t rows, int32_t flags,
+               qv_correct_info *info_host, uint8_t *ops_host, int32_t ops_pitch,
+               qv_correct_word *words_host, int32_t words_pitch, void *stream);
+/* the rows of context ctx's last batch: pred = the normalised transcript the decode stage left on the device (what
+ * qv_debug_transcript_codes returns), ref = the text the winner's token list was tokenised from -- a single verse's clean
+ * text; in a span the first ayah without its bismillah where it has one, the rest behind it, single spaces between -- so
+ * word k is word k of the word timings.  The winner is chosen as qv_align_results_ctx chooses it (QV_SOURCE_TEXT and
+ * QV_SOURCE_CTC alike); a row without a prediction carries QV_CORRECT_NO_TARGET.  Never reads the log-probs.  Lifetime and
+ * waiting as qv_nbest_results_ctx: call it before the context is reused, it waits for the batch itself; works after
+ * qv_predict_batch[_async[_ctx]] and qv_decode_retrieve_rerank[_async], with either window.  Bad context, null info_host,
+ * batch < 1, a batch the context does not hold, unknown flags or a pitch below its cap: QV_ERR_ARG; batch above max_batch:
+ * QV_ERR_CAPACITY. */
+int qv_correct_results_ctx(qv_engine *e, int32_t ctx, int32_t batch, int32_t flags,
+                           qv_correct_info *info_host, uint8_t *ops_host, int32_t ops_pitch,
+                           qv_correct_word *words_host, int32_t words_pitch);
+
 /* ---- transcription with confidence --------------------------------------------------------------
  * The greedy transcript of every row together with how sure the model was of it: what a streaming front end gates its
  * chunks by (the reference's transcribers return {"text", "avg_logprob"}, shared/streaming.py:158-181).  One kernel on

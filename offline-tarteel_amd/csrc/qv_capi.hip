@@ -924,6 +924,49 @@ extern "C" int qv_nbest_select(qv_engine *eng, const double *final_host, const f
     return qv_nbest_select_rows(eng, c, final_host, loss_host, n_host, rows, pitch, k, index_host, count_host, (hipStream_t)stream);
 }
 
+// ---- recitation correction (qv_correct.hip) --------------------------------------------------------------------------
+static bool correct_args_ok(const qv_engine *eng, int rows, int flags, const qv_correct_info *info_host, const uint8_t *ops_host,
+                            int ops_pitch, const qv_correct_word *words_host, int words_pitch) {
+    return rows >= 1 && !(flags & ~QV_CORRECT_PREFIX) && info_host && (!ops_host || ops_pitch >= QV_CORRECT_MAX_REF + eng->max_q) &&
+           (!words_host || words_pitch >= QV_CORRECT_MAX_WORDS);
+}
+
+extern "C" int qv_correct(qv_engine *eng, const uint8_t *pred_codes_host, const int32_t *pred_off_host, const uint8_t *ref_codes_host,
+                          const int32_t *ref_off_host, int32_t rows, int32_t flags, qv_correct_info *info_host, uint8_t *ops_host,
+                          int32_t ops_pitch, qv_correct_word *words_host, int32_t words_pitch, void *stream) {
+    QV_SERIALISE(eng);
+    QV_ORDERED(eng, stream);
+    if (!eng) return QV_ERR_ARG;
+    if (!pred_codes_host || !pred_off_host || !ref_codes_host || !ref_off_host ||
+        !correct_args_ok(eng, rows, flags, info_host, ops_host, ops_pitch, words_host, words_pitch)) {
+        qv_set_error(eng, "qv_correct: null argument, no rows, unknown flags or a pitch below its cap");
+        return QV_ERR_ARG;
+    }
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    if (rows > c.work.max_batch) { qv_set_error(eng, "qv_correct: rows exceed engine capacity"); return QV_ERR_CAPACITY; }
+    for (int r = 0; r < rows; ++r) {
+        const int64_t np = (int64_t)pred_off_host[r + 1] - pred_off_host[r], nr = (int64_t)ref_off_host[r + 1] - ref_off_host[r];
+        if (pred_off_host[r] < 0 || ref_off_host[r] < 0 || np < 0 || nr < 0 || np > QV_CORRECT_MAX_RAW || nr > QV_CORRECT_MAX_RAW) {
+            qv_set_error(eng, "qv_correct: bad offsets or a text of more than QV_CORRECT_MAX_RAW codes");
+            return QV_ERR_ARG;
+        }
+    }
+    return qv_correct_rows(eng, c, pred_codes_host, pred_off_host, ref_codes_host, ref_off_host, rows, flags, info_host, ops_host,
+                           ops_pitch, words_host, words_pitch, (hipStream_t)stream);
+}
+
+extern "C" int qv_correct_results_ctx(qv_engine *eng, int32_t k_ctx, int32_t batch, int32_t flags, qv_correct_info *info_host,
+                                      uint8_t *ops_host, int32_t ops_pitch, qv_correct_word *words_host, int32_t words_pitch) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (k_ctx < 0 || k_ctx >= eng->n_ctx || !correct_args_ok(eng, batch, flags, info_host, ops_host, ops_pitch, words_host, words_pitch)) {
+        qv_set_error(eng, "qv_correct_results_ctx: bad context, null argument, empty batch, unknown flags or a pitch below its cap");
+        return QV_ERR_ARG;
+    }
+    if (batch > eng->ctx[k_ctx].work.max_batch) { qv_set_error(eng, "qv_correct_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    return qv_correct_results(eng, k_ctx, batch, flags, info_host, ops_host, ops_pitch, words_host, words_pitch);
+}
+
 // ---- transcription with confidence (qv_transcribe.hip) ---------------------------------------------------------------
 extern "C" int qv_transcribe(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch, int32_t t_max,
                              qv_transcript_info *info_host, int32_t *ids_host, float *logp_host, int16_t *first_host,

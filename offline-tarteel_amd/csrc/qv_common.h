@@ -229,6 +229,23 @@ int qv_nbest_results(qv_engine *eng, int k_ctx, int batch, int k, int flags, qv_
 int qv_nbest_select_rows(qv_engine *eng, QvCtx &c, const double *final_host, const float *loss_host, const int32_t *n_host, int rows,
                          int pitch, int k, int32_t *index_host, int32_t *count_host, hipStream_t stream);
 
+// recitation correction (qv_correct.hip).  One record per row -- qv_correct_info, the op codes, the words -- so a batch comes
+// back in ONE copy into the pinned mirror; the explicit entry's codes and offsets go up through the same mirror.  Allocated
+// by the first correction call on the context (m.dev == nullptr: not yet); the back-pointers sit behind the mirrored part,
+// on the device alone, for min(max_batch, QV_CORRECT_ROUND) rows.
+#define QV_CORRECT_ROUND 64
+struct QvCorrectWs {
+    QvMirror m;
+    size_t row_bytes, ops_cap;   // one record; op codes it holds (QV_CORRECT_MAX_REF + the engine's window)
+    size_t in_off, bp_off;       // staged input (offsets, then codes) and back-pointers within the device buffer
+    size_t bp_row_words;         // uint32 words of back-pointers per row
+};
+int qv_correct_rows(qv_engine *eng, QvCtx &c, const uint8_t *pred_codes, const int32_t *pred_off, const uint8_t *ref_codes,
+                    const int32_t *ref_off, int rows, int flags, qv_correct_info *info_host, uint8_t *ops_host, int ops_pitch,
+                    qv_correct_word *words_host, int words_pitch, hipStream_t stream);
+int qv_correct_results(qv_engine *eng, int k_ctx, int batch, int flags, qv_correct_info *info_host, uint8_t *ops_host, int ops_pitch,
+                       qv_correct_word *words_host, int words_pitch);
+
 // transcription with confidence (qv_transcribe.hip).  One record per row -- qv_transcript_info, then ids / logp / first /
 // last with P = t_max rounded up to even entries each -- so a batch comes back in ONE copy into the pinned mirror (QvRowWs).
 int qv_transcribe_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max,
@@ -360,6 +377,8 @@ struct QvCtx {
     QvAlignWs align = {};
     // ranked alternatives (qv_nbest_results_ctx): the same batch, read from the candidate arrays of `work`
     QvNbestWs nbest = {};
+    // recitation correction (qv_correct_results_ctx: the same batch, its transcript in `work`; qv_correct: explicit texts)
+    QvCorrectWs correct = {};
     // transcription with confidence (qv_transcribe, qv_transcribe_batch): independent of the batch state above
     QvRowWs transcribe = {};
     // verse-constrained beam search (qv_beam_decode, qv_beam_batch): independent of the batch state as well

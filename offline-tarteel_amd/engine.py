@@ -101,6 +101,29 @@ NBEST_ENTRY_DTYPE = np.dtype([("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<
 NBEST_INFO_DTYPE = np.dtype([("n_entries", "<i4"), ("n_ranked", "<i4"), ("source", "<i4"), ("flags", "<i4")])
 assert NBEST_ENTRY_DTYPE.itemsize == C.sizeof(QvNbestEntry) == 56 and NBEST_INFO_DTYPE.itemsize == C.sizeof(QvNbestInfo) == 16
 
+CORRECT_MAX_REF, CORRECT_MAX_WORDS, CORRECT_MAX_RAW = 1280, 288, 2048   # include/qverse.h: QV_CORRECT_MAX_*
+CORRECT_PREFIX = 1                                                       # QV_CORRECT_PREFIX (call flag)
+CORRECT_NO_TARGET, CORRECT_NO_TRANSCRIPT, CORRECT_TOO_LONG, CORRECT_LAST_WORD_OPEN = 1, 2, 4, 8   # row flags
+CORRECT_INFO_FIELDS = ("n_ref", "n_pred", "n_words", "n_ref_used", "words_touched", "distance", "n_match", "n_sub", "n_del",
+                       "n_ins", "n_ops", "flags", "start_verse", "span")
+CORRECT_WORD_FIELDS = ("n_symbols", "n_match", "n_sub", "n_del", "n_ins", "type")
+
+
+class QvCorrectInfo(C.Structure):
+    """include/qverse.h: qv_correct_info"""
+    _fields_ = [(k, C.c_int32) for k in CORRECT_INFO_FIELDS] + [("reserved", C.c_int32 * 2)]
+
+
+class QvCorrectWord(C.Structure):
+    """include/qverse.h: qv_correct_word"""
+    _fields_ = [(k, C.c_uint16) for k in CORRECT_WORD_FIELDS]
+
+
+CORRECT_INFO_DTYPE = np.dtype([(k, "<i4") for k in CORRECT_INFO_FIELDS] + [("reserved", "<i4", (2,))])
+CORRECT_WORD_DTYPE = np.dtype([(k, "<u2") for k in CORRECT_WORD_FIELDS])
+assert CORRECT_INFO_DTYPE.itemsize == C.sizeof(QvCorrectInfo) == 64 and CORRECT_WORD_DTYPE.itemsize == C.sizeof(QvCorrectWord) == 12
+
+
 class QvTranscriptInfo(C.Structure):
     """include/qverse.h: qv_transcript_info"""
     _fields_ = [("n_tokens", C.c_int32), ("t_frames", C.c_int32), ("n_blank_frames", C.c_int32), ("flags", C.c_int32),
@@ -219,6 +242,8 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_align_results_ctx.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32]
     lib.qv_nbest_results_ctx.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.qv_nbest_select.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.qv_correct.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp]
+    lib.qv_correct_results_ctx.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32]
     lib.qv_transcribe.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_transcribe_batch.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_long_plan.argtypes = [i64, i32, i32, i32, vp, vp, vp, vp]
@@ -422,10 +447,11 @@ class Engine:
         return lp, t_out.tolist()
 
     def decode_retrieve_rerank(self, log_probs, t_frames, want_text: bool = True, align: bool = False,
-                               nbest: int | None = None) -> list[dict]:
+                               nbest: int | None = None, correct: bool = False, correct_prefix: bool = False) -> list[dict]:
         """align=True: every result dict gains an "alignment" entry (align_results) -- the winner's token ids and the
         frames each of them occupies in `log_probs`.  nbest=K: every dict gains "nbest", the row's list of up to K ranked
-        alternatives (nbest_results)."""
+        alternatives (nbest_results).  correct=True: every dict gains "correction", the row's word-level comparison of
+        the transcript with the winner's text (correct_results with the two texts; correct_prefix=True: in prefix mode)."""
         torch = self.torch
         assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous()
         B, t_max, V = log_probs.shape
@@ -438,9 +464,10 @@ class Engine:
             res.ctypes.data_as(C.c_void_p),
             greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
         self._check(rc, "qv_decode_retrieve_rerank")
-        return self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest)
+        return self._with_correction(self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest), correct, correct_prefix)
 
-    def predict_batch(self, audio, lengths, want_text: bool = True, align: bool = False, nbest: int | None = None) -> list[dict]:
+    def predict_batch(self, audio, lengths, want_text: bool = True, align: bool = False, nbest: int | None = None,
+                      correct: bool = False, correct_prefix: bool = False) -> list[dict]:
         torch = self.torch
         assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
         B, N = audio.shape
@@ -453,7 +480,83 @@ class Engine:
             res.ctypes.data_as(C.c_void_p),
             greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
         self._check(rc, "qv_predict_batch")
-        return self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest)
+        return self._with_correction(self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest), correct, correct_prefix)
+
+    # ---------------------------------------------------------------- recitation correction
+    def _with_correction(self, results: list[dict], correct: bool, prefix: bool = False) -> list[dict]:
+        if correct:
+            for d, c in zip(results, self.correct_results(batch=len(results), prefix=prefix, texts=True)):
+                d["correction"] = c
+        return results
+
+    def _correct_buffers(self, rows: int):
+        ops_pitch = CORRECT_MAX_REF + self.max_transcript
+        return (np.zeros(rows, CORRECT_INFO_DTYPE), np.zeros((rows, ops_pitch), np.uint8),
+                np.zeros((rows, CORRECT_MAX_WORDS), CORRECT_WORD_DTYPE))
+
+    @staticmethod
+    def _corrections(info, ops, words) -> list[dict]:
+        out = []
+        for b in range(len(info)):
+            d = {k: int(info[b][k]) for k in CORRECT_INFO_FIELDS}
+            d["ops"] = ops[b, : d["n_ops"]].copy()
+            d["words"] = words[b, : d["n_words"]].copy()
+            out.append(d)
+        return out
+
+    def correct_raw(self, pred_codes, ref_codes, prefix: bool = False):
+        """qv_correct on lists of code arrays (alphabet codes with their spaces) as the C ABI's arrays, whole: (info [rows]
+        of CORRECT_INFO_DTYPE, ops uint8 [rows, 1280 + window] padded with 0xFF, words [rows, 288] of CORRECT_WORD_DTYPE)."""
+        rows = len(pred_codes)
+        assert rows == len(ref_codes) and rows >= 1
+
+        def pack(texts):
+            arrs = [np.asarray(t, np.uint8).reshape(-1) for t in texts]
+            off = np.zeros(rows + 1, np.int32)
+            off[1:] = np.cumsum([len(a) for a in arrs])
+            return np.ascontiguousarray(np.concatenate(arrs + [np.zeros(1, np.uint8)])), off
+
+        (pc, po), (rc_, ro) = pack(pred_codes), pack(ref_codes)
+        info, ops, words = self._correct_buffers(rows)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_correct(self.h, p(pc), p(po), p(rc_), p(ro), rows, CORRECT_PREFIX if prefix else 0, p(info), p(ops),
+                                 ops.shape[1], p(words), words.shape[1], self._stream())
+        self._check(rc, "qv_correct")
+        return info, ops, words
+
+    def correct(self, pred_texts, ref_texts, prefix: bool = False) -> list[dict]:
+        """Word-level comparison of what was heard with what should have been said, on the device (qv_correct): a
+        Levenshtein alignment of the two texts' symbols (spaces only separate words) under the reference's tie rule,
+        folded into the words of the reference text.  pred_texts / ref_texts: normalised strings (encoded with
+        tables.encode) or arrays of alphabet codes, at most 2,048 characters each, at most max_batch rows.  Per row a
+        dict of the qv_correct_info fields ("n_ref", "n_pred", "n_words", "n_ref_used", "words_touched", "distance",
+        "n_match", "n_sub", "n_del", "n_ins", "n_ops", "flags", "start_verse", "span") plus "ops" (uint8 per alignment
+        column: 0 match, 1 substitution, 2 deletion, 3 insertion) and "words" (CORRECT_WORD_DTYPE per reference word).
+        prefix=True: the recitation may stop anywhere in the reference (QV_CORRECT_PREFIX).  correction.fold turns a row
+        into the reference's list of wrong words."""
+        enc = lambda t: self.tables.encode(t) if isinstance(t, str) else np.asarray(t, np.uint8)  # noqa: E731
+        return self._corrections(*self.correct_raw([enc(t) for t in pred_texts], [enc(t) for t in ref_texts], prefix))
+
+    def correct_results(self, ctx: int | None = None, batch: int = 1, prefix: bool = False, texts: bool = False) -> list[dict]:
+        """The same comparison for every row of context `ctx`'s last batch (default: the most recent call's), entirely from
+        what the batch left on the device (qv_correct_results_ctx): the decode stage's normalised transcript against the
+        text the winner's tokens were tokenised from, so word k is word k of the word timings.  Rows as correct() returns
+        them, "start_verse" / "span" naming the winner; a row without a prediction carries CORRECT_NO_TARGET.
+        texts=True adds "pred_codes" (transcript_codes) and "ref_codes" (tables.span_codes), what correction.fold spells
+        the wrong words from.  Call it before the context is reused."""
+        if ctx is None:
+            ctx = int(self.lib.qv_last_context(self.h))
+        info, ops, words = self._correct_buffers(batch)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_correct_results_ctx(self.h, int(ctx), int(batch), CORRECT_PREFIX if prefix else 0, p(info), p(ops),
+                                             ops.shape[1], p(words), words.shape[1])
+        self._check(rc, "qv_correct_results_ctx")
+        out = self._corrections(info, ops, words)
+        if texts:
+            for d, t in zip(out, self.transcript_codes(ctx, batch)):
+                d["pred_codes"] = t["codes"]
+                d["ref_codes"] = (self.tables.span_codes(d["start_verse"], d["span"]) if d["span"] else np.zeros(0, np.uint8))
+        return out
 
     # ---------------------------------------------------------------- ranked alternatives
     def _with_nbest(self, results: list[dict], nbest: int | None) -> list[dict]:

@@ -41,6 +41,9 @@ _WORDS = os.getenv("QVERSE_WORDS", "") not in ("", "0", "false", "False")
 # QVERSE_CANDIDATES=K: predict() adds the reference's "candidates" list (c2c-direct/run.py:424-435) with up to K entries
 # (1..32; the reference keeps 5) -- see predict_candidates
 _CANDIDATES = int(os.getenv("QVERSE_CANDIDATES", "0") or 0) or None
+# QVERSE_CORRECTIONS=1: predict() adds "correction" -- the words of the recognised verse the reciter got wrong, from the
+# device's symbol alignment of the transcript with the verse (Engine.correct_results + correction.fold); see predict_corrections
+_CORRECTIONS = os.getenv("QVERSE_CORRECTIONS", "") not in ("", "0", "false", "False")
 _engine = None
 _last_raw: list[dict] = []   # engine-level dicts of the most recent predict_arrays() call (profile line)
 
@@ -109,11 +112,21 @@ def shape_candidates(nbest: list[dict]) -> list[dict]:
             for e in nbest]
 
 
-def _finish(eng, raw: list[dict], round_score: bool, words: bool, candidates: int | None = None) -> list[dict]:
+def _finish(eng, raw: list[dict], round_score: bool, words: bool, candidates: int | None = None,
+            corrections: bool = False) -> list[dict]:
     out = [_to_dict(r, round_score) for r in raw]
     if words:
         for d, r in zip(out, raw):
             d["words"] = _words_of(eng, r)
+    if corrections:
+        from .correction import fold, word_status
+
+        for d, r in zip(out, raw):
+            d["correction"] = fold(eng.tables, r["correction"])
+            if words:   # the timings and the correction number the words of one text the same way
+                status = word_status(d["correction"])
+                for w in d["words"]:
+                    w["status"] = status.get((w["ayah"], w["word"]), "ok")
     if candidates is not None:
         for d, r in zip(out, raw):
             d["candidates"] = shape_candidates(r["nbest"]) if r["surah"] else []
@@ -138,15 +151,17 @@ def _trie_fallback(eng, out: list[dict], raw: list[dict], beam_rows) -> list[dic
         hyps = row["hypotheses"]
         if hyps and hyps[0]["complete"]:
             h = hyps[0]
-            extra = {k: v for k, v in out[i].items() if k in ("words", "candidates")}
+            extra = {k: v for k, v in out[i].items() if k in ("words", "candidates", "correction")}
             out[i] = {"surah": h["surah"], "ayah": h["ayah"], "ayah_end": h["ayah_end"], "score": h["score"],
                       "transcript": out[i].get("transcript", ""), "source": "trie", **extra}
     return out
 
 
-def predict_arrays(arrays, round_score: bool = True, words: bool = False, candidates: int | None = None) -> list[dict]:
+def predict_arrays(arrays, round_score: bool = True, words: bool = False, candidates: int | None = None,
+                   corrections: bool = False, prefix: bool = False) -> list[dict]:
     """audio arrays (float32, 16 kHz) -> predict()-shaped dicts, one engine call per <= MAX_BATCH.
-    words=True: every dict gains "words" (see predict_words); candidates=K: "candidates" (see predict_candidates)."""
+    words=True: every dict gains "words" (see predict_words); candidates=K: "candidates" (see predict_candidates);
+    corrections=True: "correction" (see predict_corrections; prefix=True: the recitation may stop mid-verse)."""
     import torch
 
     eng = _ensure_engine()
@@ -158,42 +173,56 @@ def predict_arrays(arrays, round_score: bool = True, words: bool = False, candid
         for i, a in enumerate(chunk):
             buf[i, : len(a)] = a
         dev = torch.from_numpy(buf).cuda(eng.device)
-        raw = eng.predict_batch(dev, lens, align=words, nbest=candidates)
+        raw = eng.predict_batch(dev, lens, align=words, nbest=candidates, correct=corrections, correct_prefix=prefix)
         _last_raw[:] = raw
-        part = _finish(eng, raw, round_score, words, candidates)
+        part = _finish(eng, raw, round_score, words, candidates, corrections)
         if trie_fallback_enabled():
             part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(dev[idx].contiguous(), [lens[i] for i in idx]))
         out.extend(part)
     return out
 
 
-def predict_device(dev, lens, round_score: bool = True, words: bool = False, candidates: int | None = None) -> list[dict]:
+def predict_device(dev, lens, round_score: bool = True, words: bool = False, candidates: int | None = None,
+                   corrections: bool = False, prefix: bool = False) -> list[dict]:
     """a zero-padded float32 cuda matrix of 16 kHz clips -> predict()-shaped dicts, one engine call per <= MAX_BATCH rows"""
     eng = _ensure_engine()
     out = []
     for s in range(0, len(lens), eng.max_batch):
         chunk = lens[s: s + eng.max_batch]
         rows = dev[s: s + len(chunk), : max(chunk)].contiguous()
-        raw = eng.predict_batch(rows, chunk, align=words, nbest=candidates)
+        raw = eng.predict_batch(rows, chunk, align=words, nbest=candidates, correct=corrections, correct_prefix=prefix)
         _last_raw[:] = raw
-        part = _finish(eng, raw, round_score, words, candidates)
+        part = _finish(eng, raw, round_score, words, candidates, corrections)
         if trie_fallback_enabled():
             part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(rows[idx].contiguous(), [chunk[i] for i in idx]))
         out.extend(part)
     return out
 
 
-def predict_batch(audio_paths, words: bool = False, candidates: int | None = None) -> list[dict]:
+def predict_batch(audio_paths, words: bool = False, candidates: int | None = None, corrections: bool = False,
+                  prefix: bool = False) -> list[dict]:
     """files -> dicts.  The ingest (mix-down, resampling to 16 kHz) runs on the GPU (audio.load_audio_device: the same float32
     arithmetic as the host load_audio, bit for bit); QVERSE_INGEST=host keeps it on the host.
     words=True: every dict gains "words" (see predict_words); candidates=K: every dict carries "candidates" (see
-    predict_candidates); without them the dicts are unchanged."""
+    predict_candidates); corrections=True: every dict gains "correction" (see predict_corrections), and with words=True every
+    entry of "words" a "status" ("ok", "substitution", "deletion" or "insertion"); without them the dicts are unchanged."""
     if os.getenv("QVERSE_INGEST", "device") == "host":
-        return predict_arrays([load_audio(p) for p in audio_paths], words=words, candidates=candidates)
+        return predict_arrays([load_audio(p) for p in audio_paths], words=words, candidates=candidates, corrections=corrections,
+                              prefix=prefix)
     from .audio import load_audio_device
 
     dev, lens = load_audio_device(list(audio_paths), _ensure_engine())
-    return predict_device(dev, lens, words=words, candidates=candidates)
+    return predict_device(dev, lens, words=words, candidates=candidates, corrections=corrections, prefix=prefix)
+
+
+def predict_corrections(audio_path: str, prefix: bool = False) -> dict:
+    """predict() plus "correction": which words of the recognised verse or span were recited wrong.  {"errors": [{"word_index",
+    "ayah", "word" (1-based within the ayah, as in predict_words), "text", "expected", "got", "error_type" ("substitution",
+    "deletion" or "insertion")}], "per", "correct_rate", "distance", "words_touched", "flags"} from the device's Levenshtein
+    alignment of the transcript with the verse's text (Engine.correct_results, correction.fold); no errors and flags != 0 when
+    nothing was recognised.  prefix=True: the recitation may stop anywhere in the verse -- the unrecited rest is not an
+    error, "words_touched" says how far it got."""
+    return predict_arrays([load_audio(audio_path)], corrections=True, prefix=prefix)[0]
 
 
 def predict_candidates(audio_path: str, k: int = 5) -> dict:
@@ -230,7 +259,7 @@ def predict(audio_path: str) -> dict:
     t0 = time.perf_counter()
     audio = load_audio(audio_path)
     t1 = time.perf_counter()
-    res = predict_arrays([audio], words=_WORDS, candidates=_CANDIDATES)[0]
+    res = predict_arrays([audio], words=_WORDS, candidates=_CANDIDATES, corrections=_CORRECTIONS)[0]
     if _PROFILE:
         # the reference's line (mixed/run.py:76-81,117-124): forward= decode= build= rerank= total=
         # candidates= use_ctc= source= -- stage times from HIP events around the device stages of this

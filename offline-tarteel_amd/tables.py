@@ -62,6 +62,26 @@ class Tables:
     def verse_index(self, surah: int, ayah: int) -> int:
         return int(self.s["surah_start"][surah - 1]) + ayah - 1
 
+    def span_codes(self, start: int, span: int) -> np.ndarray:
+        """Codes of the text the token list (start, span) was tokenised from (tools/build_tables.py:148-162): a single verse
+        is its clean text; in a span the first ayah loses its bismillah where it has one, single spaces between the ayat."""
+        def sl(name, v):
+            off = self.s[name + "_off"]
+            return self.s[name][off[v]: off[v + 1]]
+
+        if span == 1:
+            return np.array(sl("clean", start), np.uint8)
+        head = sl("nobsm", start)
+        parts = [head if len(head) else sl("clean", start)] + [sl("clean", start + j) for j in range(1, span)]
+        out = []
+        for k, part in enumerate(parts):
+            out.extend(([np.zeros(1, np.uint8)] if k else []) + [part])
+        return np.concatenate(out).astype(np.uint8)
+
+    def decode(self, codes) -> str:
+        """alphabet codes back to text; a code outside the alphabet (63) is U+FFFD"""
+        return "".join(self.alphabet[int(c)] if int(c) < len(self.alphabet) else "\ufffd" for c in codes)
+
     def token_ids(self, start: int, span: int) -> np.ndarray:
         k = start * 6 + (span - 1)
         return self.s["tok"][self.s["tok_off"][k]: self.s["tok_off"][k + 1]]
