@@ -524,6 +524,52 @@ int qv_transcribe_windows(qv_engine *e, const float *logprobs_dev, int32_t t_max
                           float *logp_host, int32_t *first_host, int32_t *last_host,
                           int32_t pitch, void *stream);
 
+/* ---- word and verse timings for recordings of any length: long CTC alignment ----------------------
+ * The Viterbi contract of "word timings" above -- start state, recursion, tie rule, end rule, float32 with one add per state
+ * and frame, `score` reproducible bit for bit, per token first / last / logp -- over the frames of a whole recording and a
+ * target of up to QV_ALIGN_LONG_MAX_TOKENS tokens.  lp[t] is the log-prob row of GLOBAL frame t from the window that owns it
+ * ("recordings of any length": the same windows, the same rounds, the same ownership); frames a window does not own and
+ * frames past a window's length are never read and may hold NaN.  first / last are global frames (int32, inclusive); logp
+ * is the float32 sum of lp[t][tgt[i]] over them in ascending t, divided by their count.
+ * Flags as qv_align's: QV_ALIGN_NO_TARGET (L == 0), QV_ALIGN_TOO_LONG (L > QV_ALIGN_LONG_MAX_TOKENS), QV_ALIGN_INFEASIBLE
+ * (T < L + number of adjacent equal tokens, or a final score below -1e29).  A flagged row holds -1 in first / last and 0 in
+ * logp and score, as do the entries past n_tokens; the other rows of the call are unaffected.  For a recording of one window
+ * with L <= QV_ALIGN_MAX_TOKENS and T within the engine's capacity the result equals qv_align's on that row, field for field.
+ * Row r aligns targets[off[r] ..] (off = running sum of lens_host, ids 0..1023 else QV_ERR_ARG); output rows are `pitch`
+ * entries apart, pitch >= the largest lens_host[r] (else QV_ERR_ARG).  Argument checks are those of qv_transcribe_long /
+ * qv_transcribe_windows.
+ * Workspace (one per engine, grown on need, freed by qv_destroy), in bytes, summed over the rows of a call:
+ *     kept rows       T * 1025 * 4, rounded up to a multiple of 16
+ *   + back-pointers   T * threads * NS / 4     for a row with 1 <= L <= QV_ALIGN_LONG_MAX_TOKENS, else 0
+ * with S = 2 L + 1, NS = 4, 8, 16 or 32 states per thread for S <= 4096, 8192, 16384, 32767, and threads = ceil(S / NS)
+ * rounded up to a multiple of 64: two bits per state and frame, padded to the thread layout.  The largest surah (14,403
+ * tokens) over 2.5 hours is about 1.3 GB.  Rows above max_batch, T above QV_LONG_MAX_FRAMES or more than
+ * QV_ALIGN_LONG_MAX_BYTES (a design limit): QV_ERR_CAPACITY before anything is allocated or launched.  How close windowed
+ * log-probs come to one forward over the whole recording is not measured; that limit carries over. */
+#define QV_ALIGN_LONG_MAX_TOKENS 16383      /* S <= 32767; the largest surah has 14,403 */
+#define QV_ALIGN_LONG_MAX_BYTES 4294967296LL /* 4 GiB */
+typedef struct { int32_t n_tokens, flags, t_frames, n_windows; float score, reserved_f; } qv_align_long_info;
+
+/* host only, no GPU, no engine: the windows of all rows and the workspace bytes (the formula above) a call with these rows
+ * would need.  QV_ERR_ARG for rows < 1, a null or negative length or token count, bad window / margin values;
+ * QV_ERR_CAPACITY above QV_LONG_MAX_FRAMES or QV_ALIGN_LONG_MAX_BYTES (the outputs are written all the same where the
+ * frames allow).  Output pointers may be NULL. */
+int qv_align_long_plan(const int64_t *n_samples, const int32_t *n_tokens, int32_t rows, int32_t max_samples,
+                       int32_t window_samples, int32_t margin_frames, int32_t *n_windows_total, int64_t *bytes);
+/* behind the forward, like qv_transcribe_windows (the same logprobs_dev, t_max, n_samples_host): works on an engine without
+ * a model.  SYNCHRONOUS. */
+int qv_align_windows(qv_engine *e, const float *logprobs_dev, int32_t t_max, const int64_t *n_samples_host, int32_t rows,
+                     int32_t window_samples, int32_t margin_frames, const uint16_t *targets_host, const int32_t *lens_host,
+                     qv_align_long_info *info_host, int32_t *first_host, int32_t *last_host, float *logp_host,
+                     int32_t pitch, void *stream);
+/* audio in, as qv_transcribe_long: the same rounds of max_batch windows through the forward, every round's owned rows kept
+ * before the next round reuses the log-prob workspace.  Waits for batches in flight and forgets the workspace's earlier batch
+ * exactly as qv_transcribe_long does.  SYNCHRONOUS.  QV_ERR_NO_MODEL without a model. */
+int qv_align_long(qv_engine *e, const float *audio_dev, int64_t audio_pitch, const int64_t *lengths_host, int32_t rows,
+                  int32_t window_samples, int32_t margin_frames, const uint16_t *targets_host, const int32_t *lens_host,
+                  qv_align_long_info *info_host, int32_t *first_host, int32_t *last_host, float *logp_host,
+                  int32_t pitch, void *stream);
+
 /* ---- verse-constrained beam search ------------------------------------------------------------------
  * A CTC prefix beam search in which every hypothesis is a prefix of a real verse or of a run of up to max_span consecutive
  * verses: it cannot leave the Quran, needs no text matching, and recognises a recitation that stops mid-verse as a prefix
@@ -716,6 +762,9 @@ int qv_stage_times(qv_engine *e, int32_t ctx, float *ms4_host);
 /* ... and while enabled, qv_transcribe_long / qv_transcribe_windows bracket every launch of their own three kernels: the last
  * call's milliseconds in k_long_gather, k_long_frames and k_long_collapse (summed over the rounds).  QV_ERR_ARG without one. */
 int qv_long_kernel_times(qv_engine *e, float *ms3_host);
+/* ... and qv_align_long / qv_align_windows theirs: the last call's milliseconds in k_long_keep (summed over the rounds) and in
+ * k_align_long (one launch per instantiation in use; the recordings of a launch run side by side). */
+int qv_align_long_kernel_times(qv_engine *e, float *ms2_host);
 
 /* Host-only: block-128 symmetric int4 quantisation of one Linear weight w[N][K] (f32 row-major,
  * N % 64 == 0, K % 128 == 0) followed by the inverse of the device packing, i.e. the f32 matrix

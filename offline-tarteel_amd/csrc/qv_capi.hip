@@ -426,6 +426,7 @@ extern "C" void qv_destroy(qv_engine *e) {
     if (e->model) qv_model_destroy(e->model);
     for (void *p : e->allocs) (void)hipFree(p);
     qv_long_free(e->long_ws);
+    qv_align_long_free(e->align_long_ws);
     qv_beam_free(e);
     for (QvCtx &c : e->ctx) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
@@ -1141,11 +1142,56 @@ extern "C" int qv_transcribe_windows(qv_engine *eng, const float *logprobs_dev, 
                        info_host, ids_host, logp_host, first_host, last_host, pitch, (hipStream_t)stream);
 }
 
+// ---- word and verse timings for recordings of any length (qv_align_long.hip) ----------------------------------------
+extern "C" int qv_align_long(qv_engine *eng, const float *audio_dev, int64_t audio_pitch, const int64_t *lengths_host, int32_t rows,
+                             int32_t window_samples, int32_t margin_frames, const uint16_t *targets_host, const int32_t *lens_host,
+                             qv_align_long_info *info_host, int32_t *first_host, int32_t *last_host, float *logp_host, int32_t pitch,
+                             void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    if (!audio_dev || !lengths_host || !lens_host || !info_host || !first_host || !last_host || !logp_host || rows < 1 || audio_pitch < 1) {
+        qv_set_error(eng, "qv_align_long: null argument, no rows or audio_pitch < 1");
+        return QV_ERR_ARG;
+    }
+    QV_ORDERED(eng, stream);
+    // as qv_transcribe_long: the forward runs into the current context's log-prob workspace, no batch may be in flight on it
+    QV_TRY(quiesce_contexts(eng));
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    const int rc = qv_align_long_run(eng, c, audio_dev, audio_pitch, nullptr, 0, lengths_host, rows, window_samples, margin_frames,
+                                     targets_host, lens_host, info_host, first_host, last_host, logp_host, pitch, (hipStream_t)stream);
+    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
+    return rc;
+}
+
+extern "C" int qv_align_windows(qv_engine *eng, const float *logprobs_dev, int32_t t_max, const int64_t *n_samples_host, int32_t rows,
+                                int32_t window_samples, int32_t margin_frames, const uint16_t *targets_host, const int32_t *lens_host,
+                                qv_align_long_info *info_host, int32_t *first_host, int32_t *last_host, float *logp_host, int32_t pitch,
+                                void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!logprobs_dev || !n_samples_host || !lens_host || !info_host || !first_host || !last_host || !logp_host || rows < 1 || t_max < 1) {
+        qv_set_error(eng, "qv_align_windows: null argument, no rows or t_max < 1");
+        return QV_ERR_ARG;
+    }
+    QV_ORDERED(eng, stream);
+    return qv_align_long_run(eng, eng->ctx[eng->cur_ctx], nullptr, 0, logprobs_dev, t_max, n_samples_host, rows, window_samples,
+                             margin_frames, targets_host, lens_host, info_host, first_host, last_host, logp_host, pitch, (hipStream_t)stream);
+}
+
 extern "C" int qv_long_kernel_times(qv_engine *eng, float *ms3_host) {
     QV_SERIALISE(eng);
     if (!eng || !ms3_host) return QV_ERR_ARG;
     if (!eng->profile_stages || !eng->long_ws.m.dev) { qv_set_error(eng, "qv_long_kernel_times: no profiled long call (qv_profile_stages first)"); return QV_ERR_ARG; }
     memcpy(ms3_host, eng->long_ws.kernel_ms, sizeof(float) * 3);
+    return QV_OK;
+}
+
+extern "C" int qv_align_long_kernel_times(qv_engine *eng, float *ms2_host) {
+    QV_SERIALISE(eng);
+    if (!eng || !ms2_host) return QV_ERR_ARG;
+    if (!eng->profile_stages || !eng->align_long_ws.big) { qv_set_error(eng, "qv_align_long_kernel_times: no profiled long alignment (qv_profile_stages first)"); return QV_ERR_ARG; }
+    memcpy(ms2_host, eng->align_long_ws.kernel_ms, sizeof(float) * 2);
     return QV_OK;
 }
 

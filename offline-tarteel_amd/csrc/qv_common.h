@@ -5,12 +5,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/qverse.h"
 #include "qv_limits.h"   // QV_NSYM, QV_OTHER, QV_MAX_SPAN, QV_MAX_VW, qv_tmpl_w
+#include "qv_long_plan.h"
 #include "qv_switches.h"
 
 #define QV_CAND_CAP 2048
@@ -278,6 +280,52 @@ void qv_long_free(QvLongWs &w);
 int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitch, const float *lp_in, int t_max_in,
                 const int64_t *n_host, int rows, int window_samples, int margin_frames, qv_long_info *info_host, int32_t *ids_host,
                 float *logp_host, int32_t *first_host, int32_t *last_host, int pitch, hipStream_t stream);
+// What qv_long_run is made of, for the other caller of the windowed forward (qv_align_long.hip).  One window of the call, in
+// the flattened recording-then-window order (device plan table):
+struct QvLongWin {
+    int64_t src_off;   // first sample of the window in the caller's audio (elements)
+    int64_t dst;       // index of the window's first OWNED frame in the fid / m arrays
+    int32_t len;       // samples to copy; the rest of the row is zero
+    int32_t lp_win;    // the window's row in the log-prob tensor the round's kernel reads
+    int32_t j0;        // local index of the first owned frame
+    int32_t count;     // owned frames
+};
+struct QvLongRec { int32_t t_frames, n_windows; };
+struct QvLongTimer;
+// a call after qv_long_check (nothing allocated or launched yet) and qv_long_tables (tables in the long workspace, uploaded)
+struct QvLongCall {
+    std::vector<QvLongPlan> plans;   // per recording
+    std::vector<int64_t> fwd_len;    // per window: the length the forward is given (audio calls)
+    size_t n_win;
+    int t_top, kw, wn, P;            // most frames of a recording; frames and samples of a full window; t_top rounded up to 4
+    const QvLongWin *tab_d;
+    const QvLongRec *rec_d;
+};
+// every check of a long call that does not concern its outputs; `who` is the entry point's name in the error text
+int qv_long_check(qv_engine *eng, const char *who, QvCtx &c, const float *audio, int64_t audio_pitch, int t_max_in,
+                  const int64_t *n_host, int rows, int window_samples, int margin_frames, QvLongCall &call);
+int qv_long_tables(qv_engine *eng, QvCtx &c, bool audio, int64_t audio_pitch, int rows, QvLongCall &call, hipStream_t stream);
+// the rounds: per_round(lp, t_max, k0, nb) enqueues what reads windows k0 .. k0 + nb - 1 of the table out of lp f32[*, t_max, 1025]
+// (the context's log-prob workspace, reused by the next round, or the caller's tensor) -- in stream order, nothing waits
+int qv_long_rounds(qv_engine *eng, QvCtx &c, const QvLongCall &call, const float *audio, int64_t audio_pitch, const float *lp_in,
+                   int t_max_in, hipStream_t stream, QvLongTimer *tm,
+                   const std::function<int(const float *lp, int t_max, size_t k0, int nb)> &per_round);
+
+// word and verse timings of recordings of any length (qv_align_long.hip; the byte formula: qv_align_long_plan.h).  One
+// workspace per engine, grown on need and freed by qv_destroy: `big` holds the kept log-prob rows of every recording and
+// behind them the back-pointers; the mirror carries the plan rows, the windows' destinations and the targets up and the
+// records back.
+struct QvAlignLongWs {
+    QvMirror m;
+    unsigned char *big;
+    size_t big_bytes;
+    float kernel_ms[3];   // qv_profile_stages: the last call's time in k_long_keep and k_align_long (the third is unused)
+};
+void qv_align_long_free(QvAlignLongWs &w);
+int qv_align_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitch, const float *lp_in, int t_max_in,
+                      const int64_t *n_host, int rows, int window_samples, int margin_frames, const uint16_t *targets_host,
+                      const int32_t *lens_host, qv_align_long_info *info_host, int32_t *first_host, int32_t *last_host,
+                      float *logp_host, int pitch, hipStream_t stream);
 
 // The matching window is a compile-time constant of the kernels that touch the transcript (buffer pitches, LDS arrays, the
 // word counts the LCS core is instantiated for).  Those kernels -- and only those -- are compiled once per window
@@ -415,6 +463,7 @@ struct qv_engine {
     unsigned resample_at = 0;
     QvTrack track;
     QvLongWs long_ws = {};
+    QvAlignLongWs align_long_ws = {};
     QvBeamState *beam = nullptr;   // the trie of the beam search (qv_beam.hip), built by the first call that asks for it
     bool profile_stages;
     // measurement hook (qv_profile_inject_logprobs): caller-owned log-probs the post-logits stages of

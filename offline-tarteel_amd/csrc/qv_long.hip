@@ -22,18 +22,9 @@ static_assert(sizeof(qv_long_info) == 48, "record layout");
 
 namespace {
 
-// one window of the call, in the flattened recording-then-window order (device plan table)
-struct LongWin {
-    int64_t src_off;   // first sample of the window in the caller's audio (elements)
-    int64_t dst;       // index of the window's first OWNED frame in the fid / m arrays
-    int32_t len;       // samples to copy; the rest of the row is zero
-    int32_t lp_win;    // the window's row in the log-prob tensor k_long_frames reads
-    int32_t j0;        // local index of the first owned frame
-    int32_t count;     // owned frames
-};
+typedef QvLongWin LongWin;   // one window of the call (qv_common.h)
 static_assert(sizeof(LongWin) == 32, "plan table layout");
-
-struct LongRec { int32_t t_frames, n_windows; };
+typedef QvLongRec LongRec;
 
 #define LG_THREADS 256
 // grid: (ceil(window_samples / 4 / LG_THREADS), windows of the round).  vec: every window start is 16-byte aligned.
@@ -153,33 +144,6 @@ __global__ __launch_bounds__(64 * LC_WAVES) void k_long_collapse(const int16_t *
     }
 }
 
-// qv_profile_stages: HIP events around every launch of the three kernels, summed per kernel after the call's synchronisation
-struct LongTimer {
-    bool on;
-    hipStream_t s;
-    std::vector<hipEvent_t> ev[3];
-    void mark(int which) {
-        if (!on) return;
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
-        (void)hipEventRecord(e, s);
-        ev[which].push_back(e);
-    }
-    void finish(float ms[3]) {   // after the stream has been synchronised
-        for (int k = 0; k < 3; ++k) {
-            ms[k] = 0.f;
-            for (size_t i = 0; i + 1 < ev[k].size(); i += 2) {
-                float t = 0.f;
-                if (hipEventElapsedTime(&t, ev[k][i], ev[k][i + 1]) == hipSuccess) ms[k] += t;
-            }
-        }
-    }
-    ~LongTimer() {
-        for (auto &v : ev)
-            for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    }
-};
-
 }  // namespace
 
 void qv_long_free(QvLongWs &w) {
@@ -211,48 +175,45 @@ static int long_ws(qv_engine *eng, QvLongWs &w, size_t n_win, int rows, int P, s
     return QV_OK;
 }
 
-// audio != nullptr: cut, forward and collapse (qv_transcribe_long).  audio == nullptr: the caller's window log-probs
-// lp_in f32[*, t_max_in, 1025] (qv_transcribe_windows).  Everything is checked before the first launch and before an output
-// array is written.  SYNCHRONOUS on `stream`.
-int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitch, const float *lp_in, int t_max_in,
-                const int64_t *n_host, int rows, int window_samples, int margin_frames, qv_long_info *info_host, int32_t *ids_host,
-                float *logp_host, int32_t *first_host, int32_t *last_host, int pitch, hipStream_t stream) {
-    const char *who = audio ? "qv_transcribe_long" : "qv_transcribe_windows";
-    const int max_batch = c.work.max_batch;
-    if (rows > max_batch) { qv_set_error(eng, std::string(who) + ": rows exceed engine capacity"); return QV_ERR_CAPACITY; }
-    std::vector<QvLongPlan> plans(rows);
-    size_t n_win = 0;
-    int t_top = 0;
-    for (int r = 0; r < rows; ++r) {
-        const int rc = qv_long_plan_make(n_host[r], eng->cfg.max_samples, window_samples, margin_frames, &plans[r]);
-        if (rc == QV_LONG_TOO_LONG) { qv_set_error(eng, std::string(who) + ": recording longer than QV_LONG_MAX_FRAMES frames"); return QV_ERR_CAPACITY; }
-        if (rc) { qv_set_error(eng, std::string(who) + ": bad length, window_samples (a multiple of 1280, at most max_samples) or margin_frames (window - 2 margins >= 1 frame)"); return QV_ERR_ARG; }
-        if (audio && n_host[r] > audio_pitch) { qv_set_error(eng, std::string(who) + ": a recording is longer than audio_pitch"); return QV_ERR_ARG; }
-        if (audio && n_host[r] < QV_LONG_MIN_SAMPLES) { qv_set_error(eng, "utterance length out of range (need 400 <= n)"); return QV_ERR_CAPACITY; }
-        n_win += plans[r].n_windows;
-        t_top = std::max(t_top, plans[r].t_total);
-    }
-    if (pitch < t_top) { qv_set_error(eng, std::string(who) + ": pitch smaller than the longest recording's frame count"); return QV_ERR_ARG; }
-    const int kw = plans[0].kw, wn = kw * QV_LONG_HOP;
-    if (!audio && t_max_in < kw + 1) { qv_set_error(eng, std::string(who) + ": t_max smaller than a window's frame count"); return QV_ERR_ARG; }
-    if (n_win > (size_t)INT32_MAX) { qv_set_error(eng, std::string(who) + ": too many windows"); return QV_ERR_CAPACITY; }
 
-    const int P = (t_top + 3) & ~3;
+int qv_long_check(qv_engine *eng, const char *who_c, QvCtx &c, const float *audio, int64_t audio_pitch, int t_max_in,
+                  const int64_t *n_host, int rows, int window_samples, int margin_frames, QvLongCall &call) {
+    const std::string who = who_c;
+    if (rows > c.work.max_batch) { qv_set_error(eng, who + ": rows exceed engine capacity"); return QV_ERR_CAPACITY; }
+    call.plans.assign(rows, QvLongPlan{});
+    call.n_win = 0;
+    call.t_top = 0;
+    for (int r = 0; r < rows; ++r) {
+        const int rc = qv_long_plan_make(n_host[r], eng->cfg.max_samples, window_samples, margin_frames, &call.plans[r]);
+        if (rc == QV_LONG_TOO_LONG) { qv_set_error(eng, who + ": recording longer than QV_LONG_MAX_FRAMES frames"); return QV_ERR_CAPACITY; }
+        if (rc) { qv_set_error(eng, who + ": bad length, window_samples (a multiple of 1280, at most max_samples) or margin_frames (window - 2 margins >= 1 frame)"); return QV_ERR_ARG; }
+        if (audio && n_host[r] > audio_pitch) { qv_set_error(eng, who + ": a recording is longer than audio_pitch"); return QV_ERR_ARG; }
+        if (audio && n_host[r] < QV_LONG_MIN_SAMPLES) { qv_set_error(eng, "utterance length out of range (need 400 <= n)"); return QV_ERR_CAPACITY; }
+        call.n_win += call.plans[r].n_windows;
+        call.t_top = std::max(call.t_top, call.plans[r].t_total);
+    }
+    call.kw = call.plans[0].kw;
+    call.wn = call.kw * QV_LONG_HOP;
+    call.P = (call.t_top + 3) & ~3;
+    if (!audio && t_max_in < call.kw + 1) { qv_set_error(eng, who + ": t_max smaller than a window's frame count"); return QV_ERR_ARG; }
+    if (call.n_win > (size_t)INT32_MAX) { qv_set_error(eng, who + ": too many windows"); return QV_ERR_CAPACITY; }
+    return QV_OK;
+}
+
+// the long workspace for this call (call.P entries per record; 0 = a caller without fid / m / records), its tables filled
+// and on their way up
+int qv_long_tables(qv_engine *eng, QvCtx &c, bool audio, int64_t audio_pitch, int rows, QvLongCall &call, hipStream_t stream) {
+    const int max_batch = c.work.max_batch, P = call.P;
     QvLongWs &w = eng->long_ws;
-    QV_TRY_RC(long_ws(eng, w, n_win, rows, P, audio ? (size_t)max_batch * wn : 0));
+    QV_TRY_RC(long_ws(eng, w, call.n_win, rows, P, audio ? (size_t)max_batch * call.wn : 0));
     LongWin *tab_h = (LongWin *)w.m.host;
     LongRec *rec_h = (LongRec *)(w.m.host + w.tab_bytes);
-    const LongWin *tab_d = (const LongWin *)w.m.dev;
-    const LongRec *rec_d = (const LongRec *)(w.m.dev + w.tab_bytes);
-    unsigned char *out_d = w.m.dev + w.tab_bytes + w.rec_bytes, *out_h = w.m.host + w.tab_bytes + w.rec_bytes;
-    int16_t *fid_d = (int16_t *)(out_d + w.out_bytes);
-    float *m_d = (float *)((unsigned char *)fid_d + w.fid_bytes);
-
-    std::vector<int64_t> fwd_len(audio ? n_win : 0);
-    bool vec = audio && ((uintptr_t)audio & 15) == 0 && audio_pitch % 4 == 0;
+    call.tab_d = (const LongWin *)w.m.dev;
+    call.rec_d = (const LongRec *)(w.m.dev + w.tab_bytes);
+    call.fwd_len.assign(audio ? call.n_win : 0, 0);
     size_t k = 0;
     for (int r = 0; r < rows; ++r) {
-        const QvLongPlan &p = plans[r];
+        const QvLongPlan &p = call.plans[r];
         rec_h[r].t_frames = p.t_total;
         rec_h[r].n_windows = p.n_windows;
         for (int v = 0; v < p.n_windows; ++v, ++k) {
@@ -264,44 +225,74 @@ int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitc
             t.lp_win = audio ? (int32_t)(k % (size_t)max_batch) : (int32_t)k;
             t.j0 = lo - v * p.h;
             t.count = hi - lo;
-            if (audio) fwd_len[k] = qv_long_fwd_len(p, v);
+            if (audio) call.fwd_len[k] = qv_long_fwd_len(p, v);
         }
     }
     QV_HIP(hipMemcpyAsync(w.m.dev, w.m.host, w.tab_bytes + w.rec_bytes, hipMemcpyHostToDevice, stream));
-    LongTimer tm = {eng->profile_stages, stream, {}};
-    const int most_owned = kw + 1;   // grid of k_long_frames: a wave whose frame its window does not own leaves at once
+    return QV_OK;
+}
+
+int qv_long_rounds(qv_engine *eng, QvCtx &c, const QvLongCall &call, const float *audio, int64_t audio_pitch, const float *lp_in,
+                   int t_max_in, hipStream_t stream, QvLongTimer *tm,
+                   const std::function<int(const float *lp, int t_max, size_t k0, int nb)> &per_round) {
+    const int max_batch = c.work.max_batch, wn = call.wn;
+    QvLongWs &w = eng->long_ws;
+    const size_t n_win = call.n_win;
     if (audio) {
+        const bool vec = ((uintptr_t)audio & 15) == 0 && audio_pitch % 4 == 0;
         std::vector<int32_t> t_out(max_batch);
         for (size_t k0 = 0; k0 < n_win; k0 += max_batch) {
             const int nb = (int)std::min<size_t>(max_batch, n_win - k0);
             int64_t lmax = 0;
-            for (int b = 0; b < nb; ++b) lmax = std::max(lmax, fwd_len[k0 + b]);
+            for (int b = 0; b < nb; ++b) lmax = std::max(lmax, call.fwd_len[k0 + b]);
             const int t_max = qv_long_frames(lmax);
-            tm.mark(0);
-            hipLaunchKernelGGL(k_long_gather, dim3((wn / 4 + LG_THREADS - 1) / LG_THREADS, nb), dim3(LG_THREADS), 0, stream, audio, tab_d + k0,
-                               w.batch, wn, (int)vec);
+            if (tm) tm->mark(0);
+            hipLaunchKernelGGL(k_long_gather, dim3((wn / 4 + LG_THREADS - 1) / LG_THREADS, nb), dim3(LG_THREADS), 0, stream, audio,
+                               call.tab_d + k0, w.batch, wn, (int)vec);
             QV_HIP(hipGetLastError());
-            tm.mark(0);
-            QV_TRY_RC(qv_model_forward(eng, eng->model, eng->cur_ctx, w.batch, fwd_len.data() + k0, nb, wn, c.logprobs_ws, t_max, t_out.data(),
-                                       stream, /*zero_pad_rows=*/false));
-            tm.mark(1);
-            hipLaunchKernelGGL(k_long_frames, dim3((most_owned + LF_WAVES - 1) / LF_WAVES, nb), dim3(64 * LF_WAVES), 0, stream,
-                               (const float *)c.logprobs_ws, t_max, tab_d + k0, fid_d, m_d);
-            QV_HIP(hipGetLastError());
-            tm.mark(1);
+            if (tm) tm->mark(0);
+            QV_TRY_RC(qv_model_forward(eng, eng->model, eng->cur_ctx, w.batch, call.fwd_len.data() + k0, nb, wn, c.logprobs_ws, t_max,
+                                       t_out.data(), stream, /*zero_pad_rows=*/false));
+            QV_TRY_RC(per_round((const float *)c.logprobs_ws, t_max, k0, nb));
         }
     } else {
         for (size_t k0 = 0; k0 < n_win; k0 += 32768) {
             const int nb = (int)std::min<size_t>(32768, n_win - k0);
-            tm.mark(1);
-            hipLaunchKernelGGL(k_long_frames, dim3((most_owned + LF_WAVES - 1) / LF_WAVES, nb), dim3(64 * LF_WAVES), 0, stream, lp_in, t_max_in,
-                               tab_d + k0, fid_d, m_d);
-            QV_HIP(hipGetLastError());
-            tm.mark(1);
+            QV_TRY_RC(per_round(lp_in, t_max_in, k0, nb));
         }
     }
+    return QV_OK;
+}
+
+// audio != nullptr: cut, forward and collapse (qv_transcribe_long).  audio == nullptr: the caller's window log-probs
+// lp_in f32[*, t_max_in, 1025] (qv_transcribe_windows).  Everything is checked before the first launch and before an output
+// array is written.  SYNCHRONOUS on `stream`.
+int qv_long_run(qv_engine *eng, QvCtx &c, const float *audio, int64_t audio_pitch, const float *lp_in, int t_max_in,
+                const int64_t *n_host, int rows, int window_samples, int margin_frames, qv_long_info *info_host, int32_t *ids_host,
+                float *logp_host, int32_t *first_host, int32_t *last_host, int pitch, hipStream_t stream) {
+    const char *who = audio ? "qv_transcribe_long" : "qv_transcribe_windows";
+    QvLongCall call;
+    QV_TRY_RC(qv_long_check(eng, who, c, audio, audio_pitch, t_max_in, n_host, rows, window_samples, margin_frames, call));
+    const int t_top = call.t_top, P = call.P;
+    if (pitch < t_top) { qv_set_error(eng, std::string(who) + ": pitch smaller than the longest recording's frame count"); return QV_ERR_ARG; }
+    QV_TRY_RC(qv_long_tables(eng, c, audio != nullptr, audio_pitch, rows, call, stream));
+    QvLongWs &w = eng->long_ws;
+    unsigned char *out_d = w.m.dev + w.tab_bytes + w.rec_bytes, *out_h = w.m.host + w.tab_bytes + w.rec_bytes;
+    int16_t *fid_d = (int16_t *)(out_d + w.out_bytes);
+    float *m_d = (float *)((unsigned char *)fid_d + w.fid_bytes);
+
+    QvLongTimer tm = {eng->profile_stages, stream, {}};
+    const int most_owned = call.kw + 1;   // grid of k_long_frames: a wave whose frame its window does not own leaves at once
+    QV_TRY_RC(qv_long_rounds(eng, c, call, audio, audio_pitch, lp_in, t_max_in, stream, &tm, [&](const float *lp, int t_max, size_t k0, int nb) -> int {
+        tm.mark(1);
+        hipLaunchKernelGGL(k_long_frames, dim3((most_owned + LF_WAVES - 1) / LF_WAVES, nb), dim3(64 * LF_WAVES), 0, stream, lp, t_max,
+                           call.tab_d + k0, fid_d, m_d);
+        QV_HIP(hipGetLastError());
+        tm.mark(1);
+        return QV_OK;
+    }));
     tm.mark(2);
-    hipLaunchKernelGGL(k_long_collapse, dim3(rows), dim3(64 * LC_WAVES), 0, stream, (const int16_t *)fid_d, (const float *)m_d, rec_d, out_d, P);
+    hipLaunchKernelGGL(k_long_collapse, dim3(rows), dim3(64 * LC_WAVES), 0, stream, (const int16_t *)fid_d, (const float *)m_d, call.rec_d, out_d, P);
     QV_HIP(hipGetLastError());
     tm.mark(2);
     QV_TRY_RC(qv_fetch_sync(eng, out_h, out_d, w.out_bytes, stream));

@@ -88,3 +88,31 @@ static inline void scatter_column(T *dst, int pitch, int row, const T *src, int 
     memcpy(d, src, sizeof(T) * n);
     for (int i = n; i < pitch; ++i) d[i] = fill;
 }
+
+// qv_profile_stages: HIP events around every launch of a long call's own kernels (up to three kinds), summed per kind after
+// the call's synchronisation (qv_long.hip, qv_align_long.hip)
+struct QvLongTimer {
+    bool on;
+    hipStream_t s;
+    std::vector<hipEvent_t> ev[3];
+    void mark(int which) {
+        if (!on) return;
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
+        (void)hipEventRecord(e, s);
+        ev[which].push_back(e);
+    }
+    void finish(float ms[3]) {   // after the stream has been synchronised
+        for (int k = 0; k < 3; ++k) {
+            ms[k] = 0.f;
+            for (size_t i = 0; i + 1 < ev[k].size(); i += 2) {
+                float t = 0.f;
+                if (hipEventElapsedTime(&t, ev[k][i], ev[k][i + 1]) == hipSuccess) ms[k] += t;
+            }
+        }
+    }
+    ~QvLongTimer() {
+        for (auto &v : ev)
+            for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+};

@@ -151,6 +151,19 @@ assert LONG_INFO_DTYPE.itemsize == C.sizeof(QvLongInfo) == 48
 QV_LONG_MAX_FRAMES = 262144
 QV_LONG_HOP = 1280   # samples per encoder frame
 
+
+class QvAlignLongInfo(C.Structure):
+    """include/qverse.h: qv_align_long_info"""
+    _fields_ = [("n_tokens", C.c_int32), ("flags", C.c_int32), ("t_frames", C.c_int32), ("n_windows", C.c_int32),
+                ("score", C.c_float), ("reserved_f", C.c_float)]
+
+
+ALIGN_LONG_MAX_TOKENS = 16383     # include/qverse.h: QV_ALIGN_LONG_MAX_TOKENS
+ALIGN_LONG_MAX_BYTES = 1 << 32    # QV_ALIGN_LONG_MAX_BYTES
+ALIGN_LONG_INFO_DTYPE = np.dtype([("n_tokens", "<i4"), ("flags", "<i4"), ("t_frames", "<i4"), ("n_windows", "<i4"),
+                                  ("score", "<f4"), ("reserved_f", "<f4")])
+assert ALIGN_LONG_INFO_DTYPE.itemsize == C.sizeof(QvAlignLongInfo) == 24
+
 BEAM_MAX = 64        # include/qverse.h: QV_BEAM_MAX
 BEAM_COMPLETE = 1    # QV_BEAM_COMPLETE
 
@@ -250,6 +263,10 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_transcribe_long.argtypes = [vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_transcribe_windows.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     lib.qv_long_kernel_times.argtypes = [vp, vp]
+    lib.qv_align_long_plan.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.qv_align_windows.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_align_long.argtypes = [vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.qv_align_long_kernel_times.argtypes = [vp, vp]
     lib.qv_trie_stats.argtypes = [C.c_char_p, i32, vp, vp, vp, vp]
     lib.qv_trie_node_tokens.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.qv_beam_decode.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
@@ -1210,6 +1227,87 @@ class Engine:
         frames of the whole recording.  window_s / margin_s in seconds; None = QVERSE_LONG_WINDOW_S / QVERSE_LONG_MARGIN_S,
         else the largest window and min(50, Kw / 4) frames."""
         return self._long_transcripts(*self.transcribe_long_raw(audio, lengths, *self._long_args(window_s, margin_s)))
+
+    # ------------------------------------------------ timings for recordings of any length -----
+    def align_long_plan(self, n_samples, n_tokens, window_samples: int = 0, margin_frames: int = -1) -> dict:
+        """qv_align_long_plan for this engine's max_samples; host only.  {"n_windows" (of all rows), "bytes" (the workspace a
+        call with these rows would need: include/qverse.h gives the formula)}; QvError where the call would be refused."""
+        n = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64).reshape(-1))
+        lt = np.ascontiguousarray(np.asarray(n_tokens, dtype=np.int32).reshape(-1))
+        assert len(n) == len(lt)
+        nw, nbytes = C.c_int32(), C.c_int64()
+        rc = self.lib.qv_align_long_plan(n.ctypes.data_as(C.c_void_p), lt.ctypes.data_as(C.c_void_p), len(n), self.max_samples,
+                                         int(window_samples), int(margin_frames), C.byref(nw), C.byref(nbytes))
+        if rc != 0:
+            raise QvError(f"qv_align_long_plan failed ({rc}): {len(n)} rows, {int(nbytes.value)} bytes")
+        return {"n_windows": int(nw.value), "bytes": int(nbytes.value)}
+
+    def _align_long_call(self, fn, what, head, rows, targets, window_samples, margin_frames, pitch):
+        assert len(targets) == rows
+        lens = np.ascontiguousarray(np.array([len(x) for x in targets], np.int32))
+        tg = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint16).reshape(-1) for x in targets] + [np.zeros(1, np.uint16)]))
+        pitch = max(int(lens.max()), 1) if pitch is None else int(pitch)
+        info = np.zeros(rows, dtype=ALIGN_LONG_INFO_DTYPE)
+        first, last = np.zeros((rows, max(pitch, 1)), np.int32), np.zeros((rows, max(pitch, 1)), np.int32)
+        logp = np.zeros((rows, max(pitch, 1)), np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = fn(self.h, *head, rows, int(window_samples), int(margin_frames), p(tg), p(lens), p(info), p(first), p(last), p(logp), pitch,
+                self._stream())
+        self._check(rc, what)
+        return info, first, last, logp
+
+    def align_windows_raw(self, log_probs, n_samples, targets, window_samples: int = 0, margin_frames: int = -1, pitch: int | None = None):
+        """qv_align_windows as arrays: log_probs float32 cuda [windows of all recordings, t_max, 1025] in recording-then-window
+        order (as transcribe_windows_raw), targets a list of id lists (0..1023), one per recording.  Returns (info [R] of
+        ALIGN_LONG_INFO_DTYPE, first / last int32 [R, pitch] in frames of the whole recording, logp float32 [R, pitch])."""
+        torch = self.torch
+        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        n = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64))
+        plans = [self.long_plan_raw(int(v), window_samples, margin_frames) for v in n]
+        if log_probs.shape[0] != sum(p["n_windows"] for p in plans) or log_probs.shape[2] != 1025:
+            raise QvError(f"align_windows: log_probs {tuple(log_probs.shape)} does not hold the {sum(p['n_windows'] for p in plans)} planned windows")
+        head = (C.c_void_p(log_probs.data_ptr()), int(log_probs.shape[1]), n.ctypes.data_as(C.c_void_p))
+        return self._align_long_call(self.lib.qv_align_windows, "qv_align_windows", head, len(n), targets, window_samples, margin_frames, pitch)
+
+    def align_long_raw(self, audio, lengths, targets, window_samples: int = 0, margin_frames: int = -1, pitch: int | None = None):
+        """qv_align_long as arrays (audio: float32 cuda [R, N]); see align_windows_raw"""
+        torch = self.torch
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous() and audio.dim() == 2
+        R, N = audio.shape
+        n = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        assert len(n) == R and n.max() <= N
+        head = (C.c_void_p(audio.data_ptr()), int(N), n.ctypes.data_as(C.c_void_p))
+        return self._align_long_call(self.lib.qv_align_long, "qv_align_long", head, R, targets, window_samples, margin_frames, pitch)
+
+    @staticmethod
+    def _long_alignments(targets, info, first, last, logp) -> list[dict]:
+        out = []
+        for b in range(len(info)):
+            flags = int(info[b]["flags"])
+            n = 0 if flags else int(info[b]["n_tokens"])
+            out.append({"ids": np.asarray(targets[b], np.int32).reshape(-1)[:n], "first": first[b, :n].copy(), "last": last[b, :n].copy(),
+                        "logp": logp[b, :n].copy(), "score": float(info[b]["score"]), "flags": flags,
+                        "n_tokens": int(info[b]["n_tokens"]), "t_frames": int(info[b]["t_frames"]), "n_windows": int(info[b]["n_windows"])})
+        return out
+
+    def align_windows(self, log_probs, n_samples, targets, window_s: float | None = None, margin_s: float | None = None) -> list[dict]:
+        """align_long behind the forward: the caller's window log-probs (align_windows_raw).  Works without a model."""
+        return self._long_alignments(targets, *self.align_windows_raw(log_probs, n_samples, targets, *self._long_args(window_s, margin_s)))
+
+    def align_long(self, audio, lengths, targets, window_s: float | None = None, margin_s: float | None = None) -> list[dict]:
+        """CTC forced alignment of token lists of up to 16,383 ids against recordings of ANY length (float32 cuda [R, N],
+        R <= max_batch): the windows and rounds of transcribe_long, every window's owned log-prob rows kept at their frame of
+        the whole recording, one Viterbi pass per recording on the device (include/qverse.h, "word and verse timings for
+        recordings of any length").  One dict per recording as align() returns it -- "ids", "first", "last" (frames of the whole
+        recording, 0.08 s each), "logp", "score", "flags", "n_tokens", "t_frames" -- plus "n_windows"."""
+        return self._long_alignments(targets, *self.align_long_raw(audio, lengths, targets, *self._long_args(window_s, margin_s)))
+
+    def align_long_kernel_times(self) -> dict:
+        """milliseconds the last align_long / align_windows call spent in its own two kernels (HIP events; needs
+        profile_stages(True))"""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.qv_align_long_kernel_times(self.h, ms), "qv_align_long_kernel_times")
+        return {"keep": ms[0], "align": ms[1]}
 
     def long_kernel_times(self) -> dict:
         """milliseconds the last transcribe_long / transcribe_windows call spent in its own three kernels (HIP events; needs

@@ -315,14 +315,64 @@ def transcribe_detailed(audio_path: str) -> dict:
     return eng.transcribe_batch(dev, [len(audio)], confidence=True)[0]
 
 
-def predict_long(audio_path: str) -> list[dict]:
+def _align_verses(eng, audio_path, verses, ids=None, ends=None) -> tuple[dict, list[dict]]:
+    """the recording against the single-verse token lists of `verses` (global indices, in recited order) as ONE target
+    (ids, ends: that target where the caller has it already): (the alignment row of Engine.align_long,
+    words.verses_from_alignment on it)"""
+    import torch
+
+    from .words import verses_from_alignment
+
+    if ids is None:
+        parts = [eng.tables.token_ids(int(v), 1) for v in verses]
+        ids = np.concatenate(parts).astype(np.uint16) if parts else np.zeros(0, np.uint16)
+        ends = np.cumsum([len(p) for p in parts], dtype=np.int64)
+    audio = load_audio(audio_path) if isinstance(audio_path, (str, Path)) else np.asarray(audio_path, np.float32)
+    dev = torch.from_numpy(np.ascontiguousarray(audio[None, :])).cuda(eng.device)
+    row = eng.align_long(dev, [len(audio)], [ids])[0]
+    return row, verses_from_alignment(eng.tables, verses, ends, row)
+
+
+def align_recitation(audio_path: str, surah: int, ayah: int, ayah_end: int | None = None) -> dict:
+    """Where in a recording of ANY length every ayah and every word of a KNOWN recitation was spoken: ayat `ayah` ..
+    `ayah_end` of `surah` (None = to the end of the surah; up to 16,383 tokens -- the largest surah has 14,403) are aligned as
+    one target to the frames of the whole recording (Engine.align_long).  Returns {"score", "flags", "t_frames", "n_windows",
+    "verses": [{"surah", "ayah", "start", "end" (seconds), "logp", "words": [...]}]}; "verses" is [] when no alignment exists
+    (flags: ALIGN_TOO_LONG, ALIGN_INFEASIBLE -- fewer frames than tokens)."""
+    eng = _ensure_engine()
+    n_ayat = int(eng.tables.s["surah_len"][surah - 1])
+    ayah_end = n_ayat if ayah_end is None else int(ayah_end)
+    if not (1 <= ayah <= ayah_end <= n_ayat):
+        raise ValueError(f"align_recitation: ayat {ayah}..{ayah_end} outside surah {surah} (1..{n_ayat})")
+    start = eng.tables.verse_index(surah, ayah)
+    count = ayah_end - ayah + 1
+    row, verses = _align_verses(eng, audio_path, list(range(start, start + count)), *eng.tables.range_token_ids(start, count))
+    return {"score": row["score"], "flags": row["flags"], "t_frames": row["t_frames"], "n_windows": row["n_windows"], "verses": verses}
+
+
+# QVERSE_LONG_TIMINGS=1: predict_long() adds "start" / "end" / "logp" to every emission
+_LONG_TIMINGS = os.getenv("QVERSE_LONG_TIMINGS", "") not in ("", "0", "false", "False")
+
+
+def predict_long(audio_path: str, timings: bool = False) -> list[dict]:
     """The verses of a recording of ANY length: the emissions of StreamingPipeline.run_on_full_transcript ({"surah", "ayah",
     "score"} per ayah, in order) on the engine's own transcript -- one forward for a clip the engine accepts, overlapping
     windows stitched on the device (Engine.transcribe_long) for a longer one.  Transcripts above 1,024 normalised characters
-    need QVERSE_MAX_TRANSCRIPT=2048."""
+    need QVERSE_MAX_TRANSCRIPT=2048.
+    timings=True (or QVERSE_LONG_TIMINGS=1): the emitted ayat, in emission order, are aligned to the recording as one target
+    (Engine.align_long; the forward runs a second time) and every emission gains "start", "end" (seconds) and "logp" -- None
+    when no alignment exists."""
     from .streaming import StreamingPipeline
 
-    return StreamingPipeline(_ensure_engine()).run_on_full_transcript(audio_path)
+    eng = _ensure_engine()
+    out = StreamingPipeline(eng).run_on_full_transcript(audio_path)
+    if not (timings or _LONG_TIMINGS) or not out:
+        return out
+    _, verses = _align_verses(eng, audio_path, [eng.tables.verse_index(e["surah"], e["ayah"]) for e in out])
+    for k, e in enumerate(out):
+        v = verses[k] if verses else {}
+        e.update(start=v.get("start"), end=v.get("end"), logp=v.get("logp"))
+    return out
 
 
 def model_size() -> int:

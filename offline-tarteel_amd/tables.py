@@ -85,3 +85,11 @@ class Tables:
     def token_ids(self, start: int, span: int) -> np.ndarray:
         k = start * 6 + (span - 1)
         return self.s["tok"][self.s["tok_off"][k]: self.s["tok_off"][k + 1]]
+
+    def range_token_ids(self, start: int, count: int):
+        """(ids, verse_ends): the single-verse token lists of `count` consecutive verses from global index `start`, back to
+        back, and the running token count behind each verse -- the target of a recited run of ayat (Engine.align_long), with
+        the verse boundaries inside it.  Unlike token_ids(start, span) the first ayah keeps its bismillah where it has one."""
+        parts = [self.token_ids(start + j, 1) for j in range(count)]
+        ids = np.concatenate(parts).astype(np.uint16) if parts else np.zeros(0, np.uint16)
+        return ids, np.cumsum([len(p) for p in parts], dtype=np.int64)

@@ -55,3 +55,27 @@ def words_from_alignment(tables, start, span, alignment) -> list[dict]:
             "logp": sum(float(logp[i]) * n for i, n in zip(g, frames)) / sum(frames),
         })
     return out
+
+
+def verses_from_alignment(tables, verses, verse_ends, alignment) -> list[dict]:
+    """alignment: one row of Engine.align_long / align_windows for the target tables.range_token_ids built; verses: the
+    global verse indices it covers, verse_ends: the running token count behind each.  Returns one dict per verse:
+    {"surah", "ayah", "start", "end" (seconds), "logp" (frame-weighted mean of its tokens' mean log-probs), "words"
+    (words_from_alignment on the verse's own tokens, span 1)}; [] when the row has no alignment."""
+    if not alignment or alignment.get("flags", 0) or not len(alignment["ids"]):
+        return []
+    out, lo = [], 0
+    for v, hi in zip(verses, verse_ends):
+        v, hi = int(v), int(hi)
+        part = {k: alignment[k][lo:hi] for k in ("ids", "first", "last", "logp")}
+        words = words_from_alignment(tables, v, 1, part)
+        frames = [int(l) - int(f) + 1 for f, l in zip(part["first"], part["last"])]
+        out.append({
+            "surah": int(tables.surah[v]), "ayah": int(tables.ayah[v]),
+            "start": words[0]["start"] if words else None,
+            "end": words[-1]["end"] if words else None,
+            "logp": sum(float(x) * n for x, n in zip(part["logp"], frames)) / sum(frames) if frames else None,
+            "words": words,
+        })
+        lo = hi
+    return out
