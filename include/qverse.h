@@ -140,7 +140,13 @@ int32_t qv_frames_for_samples(int64_t n_samples);
 /* Acoustic model.  audio_dev: f32[B, n_max] row-major, rows zero-padded past lengths_host[b].
  * logprobs_dev: f32[B, t_max, 1025] with t_max >= qv_frames_for_samples(max length); rows
  * t >= T[b] are ZEROED (onnxruntime hands the reference exactly [1, T, 1025], mixed/run.py:59-63: a padded batch tensor
- * never exposes uninitialised memory).  t_out_host[b] receives T[b] (computed on the host, no sync). */
+ * never exposes uninitialised memory).  t_out_host[b] receives T[b] (computed on the host, no sync).
+ * Isolation: the valid frames of row b are a function of that row's lengths_host[b] samples alone -- the same bits whatever
+ * the other rows of the batch, or earlier batches on the engine, held, NaN / +-inf / samples whose spectrum overflows float32
+ * included (tests/test_gpu_forward_isolation.py).  A row WITH non-finite samples keeps its frame count T[b] and its zeroed
+ * rows t >= T[b]; its valid frames hold unspecified values, finite or not.  Such a row is outside the contract of every
+ * post-logits entry point below ("valid frames hold no NaN"), qv_predict_batch and the other calls that run them on the
+ * forward's output included: what they do with it is not defined. */
 int qv_forward(qv_engine *e, const float *audio_dev, const int64_t *lengths_host, int32_t batch,
                int64_t n_max, float *logprobs_dev, int32_t t_max, int32_t *t_out_host, void *stream);
 

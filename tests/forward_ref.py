@@ -13,6 +13,8 @@
   * `telltale_weights`, `PLANTS`, `layer_power`, `tap_floor` (second half of the file): the weight set on which one wrong
     tensor in one layer shows at the tap behind that layer, the 46 wrong tensors, what each does to each of the 17 taps,
     and the taps' own float16 floor.
+  * `POISON_KINDS`, `poisoned`: the non-finite rows (and the harmless "loud" one) of tests/test_gpu_forward_isolation.py and
+    tests/test_forward_isolation_host.py.
 """
 
 from __future__ import annotations
@@ -91,6 +93,37 @@ def clips(lens, seed: int) -> torch.Tensor:
     for b, n in enumerate(lens):
         a[b, n:] = 0
     return a
+
+
+# Rows that must not reach their neighbours or the next batch (tests/test_forward_isolation_host.py shows on the oracle that
+# each POISON kind really leaves no finite log-prob in its own row, and that "loud" is harmless):
+#   nan       every sample NaN
+#   pos_inf   one +inf sample in the middle of an otherwise normal clip
+#   neg_inf   one -inf sample there
+#   huge      the clip times 1e30: finite samples whose power spectrum overflows float32
+#   nan_tail  NaN in the last 400 samples only
+POISON_KINDS = ("nan", "pos_inf", "neg_inf", "huge", "nan_tail")
+LOUD_GAIN = 32768.0      # "loud": a normal clip in unscaled int16 units -- finite everywhere
+
+
+def poisoned(clip: torch.Tensor, n: int, kind: str) -> torch.Tensor:
+    """a copy of the 1-D `clip` (n samples, zeros behind them) made into poison row `kind`, or "loud"; still zero behind n"""
+    out = clip.clone()
+    if kind == "nan":
+        out[:n] = float("nan")
+    elif kind == "pos_inf":
+        out[n // 2] = float("inf")
+    elif kind == "neg_inf":
+        out[n // 2] = float("-inf")
+    elif kind == "huge":
+        out[:n] *= 1e30
+    elif kind == "nan_tail":
+        out[max(0, n - 400): n] = float("nan")
+    elif kind == "loud":
+        out[:n] *= LOUD_GAIN
+    else:
+        raise KeyError(kind)
+    return out
 
 
 @contextlib.contextmanager
