@@ -709,6 +709,15 @@ int qv_debug_gemm_tiles(int32_t mode);
  * the wide kernel runs, -1 = back to the environment (QVERSE_GEMM_BM) / default.  Same products, same accumulation order:
  * the tile height never changes a result either.  Both switches bump an epoch that is part of the forward-graph key. */
 int qv_debug_gemm_tile_height(int32_t mode);
+/* Pipeline of the 128- / 64-wide GEMM kernels, the three switches a host sets with QVERSE_GEMM_LD / _NST / _NARROW
+ * (INTEGRATION.md 7), for the tests that walk every variant in one process.  ld: 1 = register-staged loader waves (default),
+ * 0 = direct global->LDS loads; nst: LDS stages of the direct loads, 2..4 (a 64-wide tile has at most 3), 0 = chosen from
+ * the shape; narrow: 1 = 64-wide tiles wherever a kernel of that width exists, 0 = 128-wide wherever N allows.  -1 = that
+ * switch back to its variable / default (for narrow: chosen from the shape).  An argument out of range: QV_ERR_ARG, nothing
+ * set.  int8 weights and A8W8 only exist 128-wide with register staging and ignore all three.  No variant changes a result.
+ * Part of the forward-graph key like the two above; qv_profile_replay_kernel names the pipeline when it is not the
+ * default's ("k_gemm<resid,64,lds3>": 64-wide, direct loads, 3 stages). */
+int qv_debug_gemm_pipeline(int32_t ld, int32_t nst, int32_t narrow);
 /* Process-wide attention kernel variant, for the tests: 3 = the default: an utterance of at most 128 encoder frames
  * (10.2 s) is served by the single-pass short-utterance kernel, a longer one by the key-tiled kernel -- by its OWN length,
  * so the bits of an utterance never depend on the batch it travels in; 0 = the key-tiled kernel (two heads per block)

@@ -1284,6 +1284,14 @@ extern "C" int qv_debug_gemm_tile_height(int32_t mode) {
     return QV_OK;
 }
 
+extern "C" int qv_debug_gemm_pipeline(int32_t ld, int32_t nst, int32_t narrow) {
+    const int ids[3] = {QV_SW_GEMM_LD, QV_SW_GEMM_NST, QV_SW_GEMM_NARROW}, modes[3] = {ld, nst, narrow};
+    for (int i = 0; i < 3; ++i)
+        if (modes[i] < -1 || modes[i] > QV_SWITCH_TABLE[ids[i]].hi) return QV_ERR_ARG;   // (nothing is set when one is out of range)
+    for (int i = 0; i < 3; ++i) qv_switch_set(ids[i], modes[i]);
+    return QV_OK;
+}
+
 extern "C" int qv_profile_replay_gemm(qv_engine *eng, int32_t which, int32_t iters, double *avg_us, double *flops_per_launch,
                                       void *stream) {
     QV_SERIALISE(eng);

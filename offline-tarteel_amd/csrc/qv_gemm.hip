@@ -146,12 +146,12 @@ void qv_gemm_prof_collect(double *ms, double *flops, int *n) {
     g_prof.flops.clear();
 }
 
-// the 128-wide path of a (weights, epilogue) pair of the table (qv_gemm_epilogue.h): its shape rules, then launch_shape
+// the 128-wide path of a (weights, epilogue) pair of the table (qv_gemm_epilogue.h): its shape rules, then the instantiation
+// gemm_kernel (qv_launch_plan.h) names
 struct Launch128 {
     const GemmArgs &g;
     hipStream_t s;
-    bool narrow;
-    int nst;
+    GemmKernel k;
     template <int EPI, int WQ>
     bool operator()() const {
         if constexpr (WQ == 88) {
@@ -159,10 +159,10 @@ struct Launch128 {
             if (g.N % 128 != 0 || !g.wsum || !g.mm_in) abort();
             launch_one<EPI, 128, 88, 2, 1>(g, s);
         } else if constexpr (WQ == 8) {
-            if (narrow || g.N % 128 != 0) abort();
-            launch_shape<EPI, 8>(g, s, false, nst > 3 ? 3 : nst);
+            if (k.bn != 128 || g.N % 128 != 0) abort();
+            launch_shape<EPI, 8>(g, s, false, k.nst);
         } else {
-            launch_shape<EPI, WQ>(g, s, EPI == EPI_GLU ? false : narrow, nst);
+            launch_shape<EPI, WQ>(g, s, k.bn == 64, k.ld == 1 ? 0 : k.nst);
         }
         return true;
     }
@@ -173,14 +173,18 @@ static GemmShape gemm_shape(int epi, const GemmArgs &g) {
     return {g.M, g.N, g.K, g.Wq ? GEMM_W_INT4 : g.Wi8 ? GEMM_W_A8W8 : g.W8 ? GEMM_W_INT8 : GEMM_W_F16, g.bias != nullptr, epi == EPI_GLU, g.in_flight};
 }
 
-// "k_gemm256<f16_swish>" / "k_gemm<resid,128>": the kernel launch_gemm picks for this call (measurement reports)
+// "k_gemm256<f16_swish>" / "k_gemm<resid,128>": the kernel launch_gemm picks for this call (measurement reports).  A pipeline
+// that is not the default's register staging shows: "k_gemm<resid,128,lds3>" = direct global->LDS loads, 3 stages.
 const char *qv_gemm_kernel_name(int epi, const GemmArgs &g, const QvSwitches &sw) {
     static thread_local char buf[64];
     const char *name = gemm_epi_name(epi);
-    const GemmPlan p = gemm_plan(gemm_shape(epi, g), sw);
+    const GemmShape sh = gemm_shape(epi, g);
+    const GemmPlan p = gemm_plan(sh, sw);
+    const GemmKernel k = gemm_kernel(sh, p);
     if (g.Wi8) snprintf(buf, sizeof buf, p.wide ? (p.bm == 192 ? "k_gemm256<%s,a8w8,192>" : "k_gemm256<%s,a8w8>") : "k_gemm<%s,128,a8w8>", name);
     else if (p.wide) snprintf(buf, sizeof buf, p.bm == 192 ? "k_gemm256<%s,192>" : "k_gemm256<%s>", name);
-    else snprintf(buf, sizeof buf, "k_gemm<%s,%d>", name, p.narrow ? 64 : 128);
+    else if (k.ld == 0) snprintf(buf, sizeof buf, "k_gemm<%s,%d,lds%d>", name, k.bn, k.nst);
+    else snprintf(buf, sizeof buf, "k_gemm<%s,%d>", name, k.bn);
     return buf;
 }
 
@@ -189,10 +193,12 @@ void launch_gemm(int epi, const GemmArgs &g, hipStream_t s, const QvSwitches &sw
         fprintf(stderr, "launch_gemm: unsupported shape N=%d K=%d\n", g.N, g.K);
         abort();
     }
-    const GemmPlan p = gemm_plan(gemm_shape(epi, g), sw);
+    const GemmShape sh = gemm_shape(epi, g);
+    const GemmPlan p = gemm_plan(sh, sw);
+    const GemmKernel k = gemm_kernel(sh, p);
     auto go = [&] {
         if (p.wide && launch_gemm256(epi, g, s, p.bm)) return;
-        if (!gemm_for_pair(g, epi, Launch128{g, s, p.narrow, p.nst})) abort();   // no kernel for this (weights, epilogue) pair
+        if (!gemm_for_pair(g, epi, Launch128{g, s, k})) abort();   // no kernel for this (weights, epilogue) pair
     };
     if (!g_prof.on) { go(); return; }
     size_t i = g_prof.cls.size();
@@ -204,6 +210,6 @@ void launch_gemm(int epi, const GemmArgs &g, hipStream_t s, const QvSwitches &sw
     (void)hipEventRecord(g_prof.ev[2 * i], s);
     go();
     (void)hipEventRecord(g_prof.ev[2 * i + 1], s);
-    g_prof.cls.push_back((epi == EPI_F32_RELU ? EPI_F16_RELU : epi) * 3 + (p.wide ? 2 : p.narrow ? 0 : 1));   // (21 classes in the ABI)
+    g_prof.cls.push_back((epi == EPI_F32_RELU ? EPI_F16_RELU : epi) * 3 + (p.wide ? 2 : k.bn == 64 ? 0 : 1));   // (21 classes in the ABI)
     g_prof.flops.push_back(2.0 * (double)g.M * (double)g.N * (double)g.K * (g.Wi8 ? 2.0 : 1.0));
 }

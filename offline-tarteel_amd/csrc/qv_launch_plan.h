@@ -67,6 +67,19 @@ inline GemmPlan gemm_plan(const GemmShape &g, const QvSwitches &sw) {
     return p;
 }
 
+// The k_gemm instantiation a plan that is not wide ends in: tile width, LDS stages and loader scheme (1 = register staging,
+// 0 = direct global->LDS loads) AFTER the clamps of the kernels that exist -- int8 weights and A8W8 are built 128-wide with
+// register-staged loaders and two stages only, whatever the switches ask for; the GLU tile holds both halves of a channel
+// pair and is never narrow; a narrow tile has at most 3 stages.  launch_gemm launches exactly this and qv_gemm_kernel_name
+// prints exactly this, so the two cannot disagree (tools/launch_plan_check.cpp pins it).
+struct GemmKernel { int bn, nst, ld; };
+inline GemmKernel gemm_kernel(const GemmShape &g, const GemmPlan &p) {
+    if (g.weights == GEMM_W_INT8 || g.weights == GEMM_W_A8W8) return {128, 2, 1};
+    const int bn = p.narrow && !g.glu ? 64 : 128;
+    if (p.nst == 0) return {bn, 2, 1};
+    return {bn, p.nst <= 2 ? 2 : p.nst == 3 || bn == 64 ? 3 : 4, 0};
+}
+
 // Tiles per block of k_sub01, from the launch shape alone (the forward graph is keyed on the shape; no output value depends
 // on it).  A CU holds two blocks, so the chip takes 512 at a time: the cost of a run length is (rounds of 512 blocks) x
 // (2 x tiles + 1: a block's statistics, first mel rows and halo row cost about half a tile).  64 x 10 s = 64 x 63 tiles:

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <map>
 
 #define N_LAYERS QV_N_LAYERS
@@ -168,7 +169,10 @@ struct QvModel {
     // capacities
     int max_batch, max_samples, tm_cap, t1_cap, t2_cap, t3_cap;
     size_t rows_cap;     // max_batch * t3_cap: rows of the [M][*] activation tensors
-    std::map<int, half_t *> pos_cache;  // t_max -> projected positions f16 [2*t_max-1][17*512]
+    // {t_max, QVERSE_GEMM_LD, _NST, _NARROW} -> projected positions f16 [2*t_max-1][17*512].  The pipeline switches are part
+    // of the key so that a forward under a forced pipeline computes its table with that pipeline's kernel as well (same bits;
+    // tests/test_gpu_gemm_pipelines.py); a process that never changes them keeps one table per t_max
+    std::map<std::array<int, 4>, half_t *> pos_cache;
     bool save_taps;
     // forward graphs of all contexts together (qv_debug_forward_graph_stats / _failures): graph launches, captures, and
     // captures or instantiations that failed
@@ -551,11 +555,11 @@ GemmArgs gemm_args(const int8_t *q8, const OrtConv &W, const float *bias, void *
     return g;
 }
 
-// projected relative positions for every layer, cached per t_max (weights are fixed)
-int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const half_t **out) {
-    auto it = m->pos_cache.find(t_max);
+// projected relative positions for every layer, cached per t_max and GEMM pipeline (weights are fixed)
+int get_pos(qv_engine *eng, QvModel *m, int t_max, const QvSwitches &sw, hipStream_t stream, const half_t **out) {
+    const std::array<int, 4> key = {t_max, sw[QV_SW_GEMM_LD], sw[QV_SW_GEMM_NST], sw[QV_SW_GEMM_NARROW]};
+    auto it = m->pos_cache.find(key);
     if (it != m->pos_cache.end()) { *out = it->second; return QV_OK; }
-    const QvSwitches sw = qv_switches_now();
     int R = 2 * t_max - 1;
     std::vector<half_t> pe((size_t)R * QV_D);
     for (int r = 0; r < R; ++r) {
@@ -574,7 +578,7 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, hipStream_t stream, const hal
     QV_HIP(hipStreamSynchronize(stream));
     QV_HIP(hipFree(d_pe));
     m->allocs.push_back(d_out);
-    m->pos_cache[t_max] = d_out;
+    m->pos_cache[key] = d_out;
     *out = d_out;
     return QV_OK;
 }
@@ -930,9 +934,9 @@ int qv_model_forward(qv_engine *eng, QvModel *m, int k, const float *audio, cons
     QvActs &a = m->ctx_acts[k];
     FwdShape sh;
     TRY(fwd_shape(eng, m, a, len_host, batch, n_max, t_max_out, zero_pad_rows, t_out_host, s, &sh));
-    const half_t *posp = nullptr;
-    TRY(get_pos(eng, m, sh.T, s, &posp));
     const QvSwitches sw = qv_switches_now();   // read once per forward: the graph key and every launch below see these values
+    const half_t *posp = nullptr;
+    TRY(get_pos(eng, m, sh.T, sw, s, &posp));
     auto plain = [&] { return launch_all(eng, m, a, sh, audio, n_max, logprobs, posp, sw, s); };
     // One graph launch for the whole forward when this context has already run a batch of exactly this shape from
     // these buffers (a serving loop over a fixed staging buffer with equal-length or equally-ragged batches): the

@@ -32,7 +32,7 @@
 //   QV_SW_ATT         the attention kernels (qv_debug_attention_variant; attention_plan in qv_launch_plan.h describes 0..5).  Its
 //                     environment value comes from the four flags behind it, QVERSE_ATT_OLD > _HPB > _TILED > _X -> 2 / 1 / 0 / 5
 //   QV_SW_GEMM_*      launch_gemm's tile and pipeline policy (gemm_plan in qv_launch_plan.h); T256 and BM have setters
-//                     (qv_debug_gemm_tiles, qv_debug_gemm_tile_height)
+//                     (qv_debug_gemm_tiles, qv_debug_gemm_tile_height), LD / NST / NARROW share one (qv_debug_gemm_pipeline)
 //   QV_SW_DEBUG_TAPS, QV_SW_SUB_UNFUSED, QV_SW_SUB35_UNFUSED, QV_SW_CU_PARTITION   what qv_create looks at
 //   QV_SW_POST_GRAPH  the post-logits chain as one graph launch (qv_post_run)
 //   QV_SW_SKIP, QV_SW_DUP   timing experiments (qv_model.hip); the rows exist in a QV_DEV_HOOKS build only

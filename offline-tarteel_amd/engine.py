@@ -283,6 +283,7 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_profile_replay_kernel.argtypes = [vp, i32, C.c_char_p, i32]
     lib.qv_debug_gemm_tiles.argtypes = [i32]
     lib.qv_debug_gemm_tile_height.argtypes = [i32]
+    lib.qv_debug_gemm_pipeline.argtypes = [i32, i32, i32]
     lib.qv_debug_forward_graph_failures.argtypes = [vp]
     lib.qv_debug_forward_graph_failures.restype = i64
     lib.qv_debug_attention_variant.argtypes = [i32]
@@ -823,6 +824,19 @@ class Engine:
         """tile height of the wide GEMM kernel (qv_debug_gemm_tile_height): 0 = 256 rows always, 1 = default (192 rows where
         they save a round of tiles and < 3 batches are in flight), 2 = that rule always, 3 = 192 rows always, -1 = env / default."""
         self._check(self.lib.qv_debug_gemm_tile_height(int(mode)), "qv_debug_gemm_tile_height")
+
+    def gemm_pipeline(self, ld: int = -1, nst: int = -1, narrow: int = -1):
+        """process-wide pipeline of the 128- / 64-wide GEMM kernels (qv_debug_gemm_pipeline; QVERSE_GEMM_LD / _NST / _NARROW):
+        ld 1 = register-staged loaders (default), 0 = direct global->LDS loads; nst = LDS stages of the direct loads (2..4,
+        0 = from the shape); narrow 1 / 0 = 64- / 128-wide tiles where the kernel exists; -1 = environment / default."""
+        self._check(self.lib.qv_debug_gemm_pipeline(int(ld), int(nst), int(narrow)), "qv_debug_gemm_pipeline")
+
+    def replay_kernel(self, which: int) -> str:
+        """name of the kernel the launcher picks for layer-0 GEMM `which` (REPLAY_SHAPES) at the last forward's row count
+        under the current switches (qv_profile_replay_kernel); launches nothing."""
+        name = C.create_string_buffer(64)
+        self._check(self.lib.qv_profile_replay_kernel(self.h, which, name, 64), "qv_profile_replay_kernel")
+        return name.value.decode()
 
     def weights_info(self) -> str:
         """precision mode and where the quantisation grids came from (qv_weights_info)"""

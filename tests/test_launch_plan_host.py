@@ -150,6 +150,16 @@ def gemm_plan_codes(M, N, K, w4, has_bias, glu, in_flight, t256, bm_mode, e_nst,
     return wide.astype(np.int64) | narrow.astype(np.int64) << 1 | nst << 2 | bm192.astype(np.int64) << 5
 
 
+def gemm_kernel_codes(plan, w, glu):
+    """gemm_kernel restated: the k_gemm instantiation behind a plan code (weights: 0 f16, 1 int4, 2 int8, 3 A8W8)"""
+    narrow, nst = (plan >> 1 & 1) != 0, plan >> 2 & 7
+    fixed = w >= 2                                     # int8 / A8W8: 128-wide, register staging, whatever the plan says
+    bn64 = narrow & ~glu & ~fixed
+    ld = ((nst == 0) | fixed).astype(np.int64)
+    knst = np.where(ld == 1, 2, np.where(bn64, np.minimum(nst, 3), nst))
+    return bn64.astype(np.int64) | (knst - 2) << 1 | ld << 3
+
+
 def run_lengths(batch, frames, forced, per_step, longest_auto, forced_runs, round_blocks, cost_of_run):
     """sub01_run_tiles / sub35_run_steps restated on a [batch][frames] grid"""
     n = (frames + per_step - 1) // per_step
@@ -184,6 +194,14 @@ def test_plans_over_a_grid_equal_the_restated_rules(check_exe):
     assert bad.size == 0, [(np.unravel_index(i, M.shape), int(got[i]), int(want[i])) for i in bad[:5]]
     # the grid reaches wide and 128-wide and narrow tiles (a wide plan keeps the width of its fall-back), every stage count, both tile heights
     assert set((got & 3).tolist()) == {0, 1, 2, 3} and set((got >> 2 & 7).tolist()) == {0, 2, 3, 4} and set((got >> 5).tolist()) == {0, 1}
+    # ... and the kernel behind every plan: 64- and 128-wide register staging, direct loads with 2 / 3 stages at both widths and 4 at 128
+    kern = np.frombuffer(re.search(r"^plan kernels: (\S+)$", out, re.M).group(1).encode(), dtype=np.uint8).astype(np.int64) - ord("0")
+    want_kern = gemm_kernel_codes(want, W.ravel(), ((BG & 1) != 0).ravel())
+    bad = np.flatnonzero(kern != want_kern)
+    assert kern.shape == want.shape and bad.size == 0, [(np.unravel_index(i, M.shape), int(kern[i]), int(want_kern[i])) for i in bad[:5]]
+    assert set(kern.tolist()) == {8, 9, 0, 1, 2, 3, 4}
+    fixed = W.ravel() >= 2
+    assert set(kern[fixed].tolist()) == {8} and set(kern[((BG & 1) != 0).ravel()].tolist()) <= {8, 0, 2, 4}   # int8 / A8W8: one kernel; GLU: never narrow
 
     lines = re.findall(r"^(sub01|sub35) batch 1\.\.(\d+) t\d 1\.\.(\d+) forced (\d): (\S+)$", out, re.M)
     assert [(k, int(f)) for k, _, _, f, _ in lines] == [("sub01", f) for f in range(5)] + [("sub35", f) for f in range(4)]

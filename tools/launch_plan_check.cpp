@@ -56,7 +56,8 @@ int switches() {
     QvSwitches a = env, b = env;
     b.v[QV_KV_SPANS] ^= 1; b.v[QV_KV_CTC] ^= 1; b.v[QV_KV_FWD_GRAPH] ^= 1; b.v[QV_SW_POST_GRAPH] ^= 1;
     CHECK(!(a == b) && a.forward_part() == b.forward_part());
-    for (int id : {(int)QV_KV_LOGMEL, (int)QV_KV_ORT_SUB, (int)QV_KV_SUB_RUN, (int)QV_KV_SUB35, (int)QV_SW_ATT, (int)QV_SW_GEMM_T256, (int)QV_SW_GEMM_BM}) {
+    for (int id : {(int)QV_KV_LOGMEL, (int)QV_KV_ORT_SUB, (int)QV_KV_SUB_RUN, (int)QV_KV_SUB35, (int)QV_SW_ATT, (int)QV_SW_GEMM_T256, (int)QV_SW_GEMM_BM,
+                   (int)QV_SW_GEMM_NST, (int)QV_SW_GEMM_NARROW, (int)QV_SW_GEMM_LD}) {
         b = a;
         b.v[id] += 1;
         CHECK(!(a.forward_part() == b.forward_part()));
@@ -111,6 +112,34 @@ int pins() {
     up4.weights = GEMM_W_INT4;
     p = gemm_plan(up4, with(d, QV_SW_GEMM_T256, 0));
     CHECK(!p.wide && p.narrow);                                                   // int4: 16 x 24 = 384 < 400 tiles of 128
+    // the k_gemm instantiation behind a plan (gemm_kernel): what launch_gemm launches and qv_gemm_kernel_name prints
+    auto kernel = [](const GemmShape &g, const QvSwitches &sw) { return gemm_kernel(g, gemm_plan(g, sw)); };
+    auto is = [](const GemmKernel &k, int bn, int nst, int ld) { return k.bn == bn && k.nst == nst && k.ld == ld; };
+    const QvSwitches t0 = with(d, QV_SW_GEMM_T256, 0), lds = with(t0, QV_SW_GEMM_LD, 0);
+    CHECK(is(kernel(up, t0), 128, 2, 1) && is(kernel(up4, t0), 64, 2, 1));          // the defaults: register staging
+    CHECK(is(kernel(up, with(t0, QV_SW_GEMM_NARROW, 1)), 64, 2, 1) && is(kernel(up4, with(t0, QV_SW_GEMM_NARROW, 0)), 128, 2, 1));
+    CHECK(is(kernel(up, with(t0, QV_SW_GEMM_NST, 3)), 128, 2, 1));                  // a stage count alone does not leave register staging
+    CHECK(is(kernel(up, lds), 128, 3, 0));                                          // direct loads: 384 tiles < 400, K / 64 = 8 < 16 -> 3 stages
+    CHECK(is(kernel(up, with(lds, QV_SW_GEMM_NST, 2)), 128, 2, 0) && is(kernel(up, with(lds, QV_SW_GEMM_NST, 4)), 128, 4, 0));
+    CHECK(is(kernel(up, with(lds, QV_SW_GEMM_NARROW, 1)), 64, 2, 0));               // 32 x 24 = 768 tiles of 64 -> 2 stages
+    CHECK(is(kernel(up, with(with(lds, QV_SW_GEMM_NARROW, 1), QV_SW_GEMM_NST, 3)), 64, 3, 0));
+    CHECK(is(kernel(up, with(with(lds, QV_SW_GEMM_NARROW, 1), QV_SW_GEMM_NST, 4)), 64, 2, 0));   // 4 is not a narrow stage count: the plan's own
+    GemmShape down = {420, 512, 2048, GEMM_W_F16, true, false, 1};                  // FFN-down of 420 rows: 16 tiles, K / 64 = 32 -> 4 stages
+    CHECK(is(kernel(down, lds), 128, 4, 0) && is(kernel(down, with(lds, QV_SW_GEMM_NARROW, 1)), 64, 3, 0));
+    down.weights = GEMM_W_INT4;
+    CHECK(is(kernel(down, lds), 64, 3, 0) && is(kernel(down, with(lds, QV_SW_GEMM_NARROW, 0)), 128, 4, 0));
+    CHECK(is(gemm_kernel(down, GemmPlan{false, true, 4, 256}), 64, 3, 0));          // (a narrow tile never has 4 stages, whoever made the plan)
+    GemmShape glu = {420, 1024, 512, GEMM_W_F16, true, true, 1};                    // pointwise conv + GLU: never narrow
+    CHECK(is(kernel(glu, with(with(lds, QV_SW_GEMM_NARROW, 1), QV_SW_GEMM_NST, 3)), 128, 3, 0));
+    CHECK(is(gemm_kernel(glu, GemmPlan{false, true, 0, 256}), 128, 2, 1) && is(gemm_kernel(glu, GemmPlan{false, true, 4, 256}), 128, 4, 0));
+    for (int w : {(int)GEMM_W_INT8, (int)GEMM_W_A8W8})                              // int8 weights, A8W8: one instantiation, whatever is set
+        for (int n : {512, 1024})
+            for (int narrow : {-1, 0, 1})
+                for (int nst : {0, 2, 3, 4})
+                    for (int ld : {0, 1}) {
+                        const GemmShape g8 = {420, n, 512, w, true, n == 1024, 1};
+                        CHECK(is(kernel(g8, with(with(with(t0, QV_SW_GEMM_NARROW, narrow), QV_SW_GEMM_NST, nst), QV_SW_GEMM_LD, ld)), 128, 2, 1));
+                    }
     // attention
     AttentionPlan a = attention_plan(3, 20, ATT_SHORT_T);
     CHECK(a.run_short && a.rest == ATT_NONE);                                     // every utterance is short
@@ -141,7 +170,8 @@ void print_axis(const char *name, const std::vector<int> &v) {
 }
 
 // Grid axes in loop order (outermost first), then one character per point: gemm_plan as '0' + (wide | narrow << 1 |
-// nst << 2 | (bm == 192) << 5), a run length as 'a' + run - 1.
+// nst << 2 | (bm == 192) << 5), its kernel (gemm_kernel) as '0' + ((bn == 64) | (nst - 2) << 1 | ld << 3), a run length as
+// 'a' + run - 1.
 int sweep() {
     std::vector<int> Ms = {1, 2, 63, 64, 127, 128, 129, 191, 192, 193, 255, 256, 257, 383, 384, 385, 511, 512, 576, 768, 1000, 1536, 1920, 3024, 3072, 4097,
                            6143, 8064, 12288, 16128, 19200, 24064, 24065, 32256, 40001, 49920, 50000};
@@ -165,15 +195,20 @@ int sweep() {
         print_axis("gemm env", shown);
         env_sw.push_back(sw);
     }
-    std::string out;
+    std::string out, kernels;
     for (int M : Ms) for (int N : Ns) for (int K : Ks) for (int w : weights) for (int bg : bias_glu) for (int inf : in_flight)
         for (int t : t256) for (int b : bm) for (QvSwitches sw : env_sw) {
             sw.v[QV_SW_GEMM_T256] = t; sw.v[QV_SW_GEMM_BM] = b;
-            const GemmPlan p = gemm_plan({M, N, K, w, (bg & 2) != 0, (bg & 1) != 0, inf}, sw);
+            const GemmShape g = {M, N, K, w, (bg & 2) != 0, (bg & 1) != 0, inf};
+            const GemmPlan p = gemm_plan(g, sw);
             CHECK(p.nst >= 0 && p.nst <= 4 && (p.bm == 256 || p.bm == 192));
             out.push_back((char)('0' + (p.wide | p.narrow << 1 | p.nst << 2 | (p.bm == 192) << 5)));
+            const GemmKernel k = gemm_kernel(g, p);
+            CHECK((k.bn == 64 || k.bn == 128) && k.nst >= 2 && k.nst <= (k.bn == 64 ? 3 : 4) && (k.ld == 0 || (k.ld == 1 && k.nst == 2)));
+            kernels.push_back((char)('0' + ((k.bn == 64) | (k.nst - 2) << 1 | k.ld << 3)));
         }
     printf("gemm plans: %s\n", out.c_str());
+    printf("plan kernels: %s\n", kernels.c_str());
     // the run lengths: every batch size up to 256 and every frame count an engine accepts (61 s: 1526 c1 frames, 763 c2 frames)
     const int B = 256, T2 = 1536, T3 = 768;
     for (int forced = 0; forced <= 4; ++forced) {
