@@ -189,26 +189,6 @@ extern "C" int32_t qv_frames_for_samples(int64_t n) {
     return (int32_t)t;
 }
 
-template <typename T>
-static int upload(qv_engine *eng, const T *host, size_t count, const T **dev) {
-    void *p = nullptr;
-    QV_HIP(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
-    eng->allocs.push_back(p);
-    if (count) QV_HIP(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
-    *dev = (const T *)p;
-    return QV_OK;
-}
-
-template <typename T>
-static int dalloc(qv_engine *eng, size_t count, T **dev) {
-    void *p = nullptr;
-    QV_HIP(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
-    QV_HIP(hipMemset(p, 0, std::max<size_t>(count * sizeof(T), 16)));
-    eng->allocs.push_back(p);
-    *dev = (T *)p;
-    return QV_OK;
-}
-
 #define QV_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // the tables file: read it, let qv_tables_host.h check it and build the host arrays, upload each under its own name
@@ -229,7 +209,7 @@ static int load_tables(qv_engine *eng, const char *path) {
     t.n_verses = h.n_verses; t.n_surah = h.n_surah; t.n_tri = h.n_tri; t.n_text = h.n_text;
     eng->h_surah = std::move(h.h_surah);
     eng->h_ayah = std::move(h.h_ayah);
-#define UP(member) QV_TRY(upload(eng, h.member.data(), h.member.size(), &t.member))
+#define UP(member) QV_TRY(qv_dev_upload(eng, eng->allocs, h.member.data(), h.member.size(), &t.member))
     UP(surah); UP(ayah); UP(surah_start); UP(surah_len);
     UP(clean8); UP(clean8_off);
     UP(clean); UP(clean_off); UP(clean_len); UP(nobsm_len);
@@ -254,43 +234,43 @@ static int alloc_work(qv_engine *eng, int k, const QvSwitches &sw) {
     w.max_batch = B;
     w.t_cap = qv_frames_for_samples(eng->cfg.max_samples) + 2;
     size_t Bz = (size_t)B;
-    QV_TRY(dalloc(eng, Bz, &w.utt));
-    QV_TRY(dalloc(eng, Bz * w.t_cap, &w.frame_ids));
-    QV_TRY(dalloc(eng, Bz * w.t_cap, &w.greedy));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz, &w.utt));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * w.t_cap, &w.frame_ids));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * w.t_cap, &w.greedy));
     const size_t maxq = (size_t)eng->max_q;   // the engine's window: pitch of q / qs, 64 bits of it per mask word
-    QV_TRY(dalloc(eng, Bz * maxq + 64, &w.q));
-    QV_TRY(dalloc(eng, Bz * maxq + 64, &w.qs));
-    QV_TRY(dalloc(eng, Bz * 2 * QV_NSYM * (maxq / 64), &w.pm));
-    QV_TRY(dalloc(eng, Bz * N, &w.cand1));
-    QV_TRY(dalloc(eng, Bz * N * 3, &w.lcsf));
-    QV_TRY(dalloc(eng, Bz * N * 3, &w.fs));
-    QV_TRY(dalloc(eng, Bz * N, &w.lcs_p3));
-    QV_TRY(dalloc(eng, Bz * N * 3, &w.frag_list));
-    QV_TRY(dalloc(eng, (size_t)4, &w.frag_ctr));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * maxq + 64, &w.q));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * maxq + 64, &w.qs));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * 2 * QV_NSYM * (maxq / 64), &w.pm));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * N, &w.cand1));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * N * 3, &w.lcsf));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * N * 3, &w.fs));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * N, &w.lcs_p3));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * N * 3, &w.frag_list));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)4, &w.frag_ctr));
     w.frag_cap = (int)(Bz * N * 3);
     w.search_sc = nullptr;
-    QV_TRY(dalloc(eng, Bz * QV_RUNNER_CAP, &w.runner_idx));
-    QV_TRY(dalloc(eng, Bz * QV_RUNNER_CAP, &w.runner_score));
-    QV_TRY(dalloc(eng, Bz * QV_RUNNER_CAP, &w.top_search));
-    QV_TRY(dalloc(eng, Bz * QV_RUNNER_CAP, &w.top_search_sc));
-    QV_TRY(dalloc(eng, Bz * QV_RUNNER_CAP, &w.top_p3));
-    QV_TRY(dalloc(eng, Bz * QV_RUNNER_CAP, &w.top_p3_sc));
-    QV_TRY(dalloc(eng, Bz * QV_SPAN_BLOCKS, &w.span_part_score));
-    QV_TRY(dalloc(eng, Bz * QV_SPAN_BLOCKS, &w.span_part_key));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP, &w.cand_start));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP, &w.cand_span));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP, &w.cand_score));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP, &w.cand_lead));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP * QV_MAX_SPAN, &w.cand_memb));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP, &w.cand_loss));
-    QV_TRY(dalloc(eng, Bz * QV_CAND_CAP, &w.cand_final));
-    QV_TRY(dalloc(eng, Bz, &w.results));
-    QV_TRY(dalloc(eng, Bz * 4, &w.packed));
-    QV_TRY(dalloc(eng, Bz, &w.fail_list));
-    QV_TRY(dalloc(eng, (size_t)1, &w.n_fail));
-    QV_TRY(dalloc(eng, Bz, &c.t_dev));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_RUNNER_CAP, &w.runner_idx));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_RUNNER_CAP, &w.runner_score));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_RUNNER_CAP, &w.top_search));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_RUNNER_CAP, &w.top_search_sc));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_RUNNER_CAP, &w.top_p3));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_RUNNER_CAP, &w.top_p3_sc));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_SPAN_BLOCKS, &w.span_part_score));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_SPAN_BLOCKS, &w.span_part_key));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP, &w.cand_start));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP, &w.cand_span));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP, &w.cand_score));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP, &w.cand_lead));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP * QV_MAX_SPAN, &w.cand_memb));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP, &w.cand_loss));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * QV_CAND_CAP, &w.cand_final));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz, &w.results));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * 4, &w.packed));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz, &w.fail_list));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)1, &w.n_fail));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz, &c.t_dev));
     QV_HIP(hipHostMalloc((void **)&c.t_host_scratch, sizeof(int32_t) * Bz * QV_STAGE_SLOTS, hipHostMallocDefault));
-    if (eng->cfg.with_model) QV_TRY(dalloc(eng, Bz * w.t_cap * QV_VOCAB, &c.logprobs_ws));
+    if (eng->cfg.with_model) QV_TRY(qv_dev_zeroed(eng, eng->allocs, Bz * w.t_cap * QV_VOCAB, &c.logprobs_ws));
     for (int i = 0; i < QV_STAGE_SLOTS; ++i) QV_HIP(hipEventCreateWithFlags(&c.t_copied[i], hipEventDisableTiming));
     if (eng->n_ctx > 1) {
         // QVERSE_CU_PARTITION=1 (experiment, DESIGN.md "Batches in flight"): context k's stream only sees its share of
@@ -405,10 +385,10 @@ extern "C" int qv_create(const qv_config *cfg_in, qv_engine **out) {
     }
     {   // verse tracker workspace (qv_tracker_match)
         QvTrack &t = eng->track;
-        if ((rc = dalloc(eng, (size_t)QV_TRACK_CAP * eng->max_q + 64, &t.q)) || (rc = dalloc(eng, (size_t)QV_TRACK_CAP * 4, &t.meta)) ||
-            (rc = dalloc(eng, (size_t)QV_TRACK_CAP * QV_TRACK_BLOCKS, &t.part_s)) ||
-            (rc = dalloc(eng, (size_t)QV_TRACK_CAP * QV_TRACK_BLOCKS, &t.part_k)) ||
-            (rc = dalloc(eng, (size_t)QV_TRACK_CAP, &t.out)))
+        if ((rc = qv_dev_zeroed(eng, eng->allocs, (size_t)QV_TRACK_CAP * eng->max_q + 64, &t.q)) || (rc = qv_dev_zeroed(eng, eng->allocs, (size_t)QV_TRACK_CAP * 4, &t.meta)) ||
+            (rc = qv_dev_zeroed(eng, eng->allocs, (size_t)QV_TRACK_CAP * QV_TRACK_BLOCKS, &t.part_s)) ||
+            (rc = qv_dev_zeroed(eng, eng->allocs, (size_t)QV_TRACK_CAP * QV_TRACK_BLOCKS, &t.part_k)) ||
+            (rc = qv_dev_zeroed(eng, eng->allocs, (size_t)QV_TRACK_CAP, &t.out)))
             return fail(rc);
     }
     if (cfg->with_model) {
@@ -637,7 +617,7 @@ static int fir_for(qv_engine *eng, const float *taps, int32_t n_taps, int32_t up
             if (k < n_taps) hf[(size_t)t * P + j] = taps[k];
         }
     float *d = nullptr;
-    QV_TRY(dalloc(eng, hf.size(), &d));
+    QV_TRY(qv_dev_zeroed(eng, eng->allocs, hf.size(), &d));
     QV_HIP(hipMemcpy(d, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
     eng->firs.push_back({up, std::vector<float>(taps, taps + n_taps), d, P});
     *out = &eng->firs.back();
@@ -661,7 +641,7 @@ extern "C" int qv_upfirdn_batch(qv_engine *eng, const float *x_dev, int64_t x_pi
     QV_TRY(fir_for(eng, taps, n_taps, up, &fir));
     // row table: [QV_RESAMPLE_ROWS] int64 lengths + int32 source rows, one slot of a small ring per call (the copy is issued
     // from pageable memory: the runtime stages it before this function returns, so the host vectors may go away)
-    if (!eng->resample_tab) QV_TRY(dalloc(eng, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
+    if (!eng->resample_tab) QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
     unsigned char *slot = eng->resample_tab + (size_t)(eng->resample_at++ % QV_RESAMPLE_SLOTS) * QV_RESAMPLE_ROWS * 12;
     hipStream_t s = (hipStream_t)stream;
     QV_HIP(hipMemcpyAsync(slot, n_in_host, sizeof(int64_t) * rows, hipMemcpyHostToDevice, s));
@@ -685,7 +665,7 @@ extern "C" int qv_mixdown_batch(qv_engine *eng, const float *x_dev, int64_t x_pi
         if (n_frames_host[r] < 0 || n_frames_host[r] * channels > x_pitch || n_frames_host[r] > y_pitch) return QV_ERR_ARG;
         mx = n_frames_host[r] > mx ? n_frames_host[r] : mx;
     }
-    if (!eng->resample_tab) QV_TRY(dalloc(eng, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
+    if (!eng->resample_tab) QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
     unsigned char *slot = eng->resample_tab + (size_t)(eng->resample_at++ % QV_RESAMPLE_SLOTS) * QV_RESAMPLE_ROWS * 12;
     hipStream_t s = (hipStream_t)stream;
     QV_HIP(hipMemcpyAsync(slot, n_frames_host, sizeof(int64_t) * rows, hipMemcpyHostToDevice, s));

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -30,6 +31,27 @@
 
 struct qv_engine;
 void qv_set_error(qv_engine *e, const std::string &msg);
+
+// Device memory that lives as long as its owner (`allocs`: qv_engine::allocs or QvModel::allocs, freed by qv_destroy), at
+// least 16 bytes each: `count` elements copied from the host / `count` zeroed elements.
+template <typename T>
+int qv_dev_upload(qv_engine *eng, std::vector<void *> &allocs, const T *host, size_t count, const T **dev) {
+    void *p = nullptr;
+    QV_HIP(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
+    allocs.push_back(p);
+    if (count) QV_HIP(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
+    *dev = (const T *)p;
+    return QV_OK;
+}
+template <typename T>
+int qv_dev_zeroed(qv_engine *eng, std::vector<void *> &allocs, size_t count, T **dev) {
+    void *p = nullptr;
+    QV_HIP(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
+    QV_HIP(hipMemset(p, 0, std::max<size_t>(count * sizeof(T), 16)));
+    allocs.push_back(p);
+    *dev = (T *)p;
+    return QV_OK;
+}
 
 // ------------------------------------------------------------------ static tables -----
 // Device-resident verse database (built once at qv_create from qverse_tables.bin).

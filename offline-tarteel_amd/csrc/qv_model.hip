@@ -14,7 +14,7 @@
 #include "qv_graph.h"
 #include "qv_layers.h"
 #include "qv_ort.h"
-#include "qv_weights_host.h"   // HostWeights, weight_shapes, random_tensor, init_random, load_weight_file
+#include "qv_model_prep_host.h"   // the weight source (qv_weights_host.h) and what becomes of it: ModelW, WeightPrep
 
 #include <math.h>
 #include <stdio.h>
@@ -24,8 +24,6 @@
 #include <array>
 #include <map>
 
-#define N_LAYERS QV_N_LAYERS
-#define HEAD_N 1152  // 1025 padded to a multiple of 128
 // QV_PREC_ORT_MIXED: quantiser sites, one {min, max} pair per utterance each (qv_ort.h): normalised mel, ReLU(conv.0),
 // conv.2, ReLU(conv.3), conv.5, then per layer norm_conv / GLU / depthwise output, then the encoder output (CTC head)
 #define MM_MEL 0
@@ -36,41 +34,6 @@
 #define MM_LAYER(l) (5 + 3 * (l))
 #define MM_HEAD (5 + 3 * N_LAYERS)
 #define MM_SITES (MM_HEAD + 1)
-
-namespace {
-
-// one GEMM weight matrix: f16 [N][K], or (int4 mode, Linear layers) packed nibbles + f16 scales
-struct WMat {
-    const half_t *w = nullptr;
-    const uint8_t *q = nullptr;
-    const half_t *sc = nullptr;
-    const uint8_t *q8 = nullptr;   // int8 mode (pointwise convolutions): packed q + 128 ...
-    const float *sc8 = nullptr;    // ... and the per-output-channel scales
-};
-
-// QV_PREC_ORT_MIXED: a Conv weight as quantize_dynamic(QInt8) stores it -- ONE symmetric scale per tensor
-struct OrtConv {                   // GEMM-shaped (1x1) convolution: s8 [N][K] row-major + the row sums the epilogue needs
-    const int8_t *wq = nullptr;
-    const int32_t *wsum = nullptr;
-    float scale = 1.f;
-};
-struct OrtDw {                     // depthwise / strided convolution: taps as integer-valued floats, tap-major [9][C]
-    const float *wq = nullptr;
-    float scale = 1.f;
-};
-
-struct LayerW {
-    const float *ln_g[5], *ln_b[5];  // ff1, att, conv, ff2, out
-    WMat ff1_w1, ff1_w2, ff2_w1, ff2_w2, qkv_w, out_w, pw1_w, pw2_w;
-    const float *ff1_b1, *ff1_b2, *ff2_b1, *ff2_b2, *qkv_b, *out_b, *pw1_b, *pw2_b;
-    const float *bias_u, *bias_v, *dw_w, *dw_b;
-    // QV_PREC_ORT_MIXED
-    OrtConv o_pw1, o_pw2;
-    OrtDw o_dw;
-    const float *o_dw_b, *bn_alpha, *bn_beta;   // raw depthwise bias; BatchNorm as torch evaluates it: fma(y, alpha, beta)
-};
-
-}  // namespace
 
 // ---- host-only C ABI: what the weight file must hold (tools/convert_weights.py) ----------
 extern "C" int32_t qv_weight_count(void) { return (int32_t)weight_shapes().size(); }
@@ -153,19 +116,10 @@ struct QvModel {
     QvActs ctx_acts[QV_MAX_CTX] = {};   // context k's state: the functions that run on a context are handed k
     int n_ctx;
     std::vector<void *> allocs;
-    FrontendTab ft;
-    const float *c0_w, *c0_b, *dw2_w, *dw2_b, *dw5_w, *dw5_b, *pw3_b, *pw6_b, *sub_out_b, *head_b;
-    const half_t *pw3_w, *pw6_w, *sub_out_w, *head_w;
-    WMat pos_w;
-    const float *zero_bias;
+    ModelW w;            // every weight image, on the device (qv_model_prep_host.h)
     bool w4;             // QV_PREC_MIXED_INT4_INT8 / QV_PREC_ORT_MIXED: Linear-layer weights are block-128 int4
     bool ort;            // QV_PREC_ORT_MIXED: every Conv runs DynamicQuantizeLinear -> ConvInteger (qv_ort.h)
     bool prequant;       // the weight file is marked pre-quantised (HostWeights::prequantised): nothing is re-quantised
-    int prequant_w4_linears = 0, prequant_f16_linears = 0;   // ... its Linear weights on the file's int4 grid / as f16 values
-    OrtDw o_c0, o_dw2, o_dw5;
-    OrtConv o_pw3, o_pw6, o_head;
-    const float *o_dw2_b, *o_dw5_b;
-    LayerW L[N_LAYERS];
     // capacities
     int max_batch, max_samples, tm_cap, t1_cap, t2_cap, t3_cap;
     size_t rows_cap;     // max_batch * t3_cap: rows of the [M][*] activation tensors
@@ -181,358 +135,16 @@ struct QvModel {
 
 namespace {
 
-template <typename T>
-int up(qv_engine *eng, QvModel *m, const std::vector<T> &h, const T **dev) {
-    void *p = nullptr;
-    QV_HIP(hipMalloc(&p, std::max<size_t>(h.size() * sizeof(T), 16)));
-    m->allocs.push_back(p);
-    QV_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = (const T *)p;
-    return QV_OK;
-}
+// the library's sink of qv_model_prep_host.h: one device allocation per image, owned by the model
+struct DevSink {
+    qv_engine *eng;
+    QvModel *m;
+    template <typename T>
+    int operator()(const std::vector<T> &h, const T **dev) { return qv_dev_upload(eng, m->allocs, h.data(), h.size(), dev); }
+};
 
-template <typename T>
-int dal(qv_engine *eng, QvModel *m, size_t count, T **dev) {
-    void *p = nullptr;
-    QV_HIP(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
-    QV_HIP(hipMemset(p, 0, std::max<size_t>(count * sizeof(T), 16)));
-    m->allocs.push_back(p);
-    *dev = (T *)p;
-    return QV_OK;
-}
-
-// [C][9] -> [9][C] (tap-major) so a thread's 8 channels of one tap are one 32-byte load
-std::vector<float> tap_major(const std::vector<float> &w, int C) {
-    std::vector<float> t((size_t)C * 9);
-    for (int c = 0; c < C; ++c)
-        for (int k = 0; k < 9; ++k) t[(size_t)k * C + c] = w[(size_t)c * 9 + k];
-    return t;
-}
-
-std::vector<half_t> to_half(const std::vector<float> &v) {
-    std::vector<half_t> h(v.size());
-    for (size_t i = 0; i < v.size(); ++i) h[i] = (half_t)v[i];
-    return h;
-}
-
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
-// upload a Linear weight [N][K]: f16, or int4 nibbles + scales when the model runs W4A16.  A pre-quantised file's weight
-// goes onto the FILE's grid (`gs`, `gz`: its block scales / zero points) and is never re-quantised; without a grid
-// (MatMulNBits block size other than 128) it runs as its dequantised values, f16.
-int up_mat(qv_engine *eng, QvModel *m, const std::vector<float> &w, int N, int K, WMat *out,
-           const std::vector<float> *gs = nullptr, const std::vector<float> *gz = nullptr) {
-    const bool grid = m->prequant && gs && gz && gs->size() == (size_t)N * (K / 128) && gz->size() == gs->size();
-    if (!m->w4 || (m->prequant && !grid)) {
-        if (m->w4) ++m->prequant_f16_linears;
-        return up(eng, m, to_half(w), &out->w);
-    }
-    std::vector<uint8_t> q((size_t)N * K / 2, 0);
-    std::vector<half_t> sc((size_t)N * (K / 128) * 2);
-    if (grid) {
-        const int64_t bad = qv_pack_w4_given(w.data(), N, K, gs->data(), gz->data(), q.data(), sc.data());
-        if (bad) { qv_set_error(eng, "pre-quantised weight file: a Linear weight does not sit on the int4 grid it declares (or a block has a non-integer zero point / a scale outside f16's normal range)"); return QV_ERR_IO; }
-        ++m->prequant_w4_linears;
-    } else
-    qv_pack_w4(w.data(), N, K, q.data(), sc.data());
-    TRY(up(eng, m, q, &out->q));
-    return up(eng, m, sc, &out->sc);
-}
-
-// upload a pointwise-convolution weight [N][K]: f16, or per-channel int8 when the model runs mixed
-int up_mat8(qv_engine *eng, QvModel *m, const std::vector<float> &w, int N, int K, WMat *out) {
-    if (m->ort) return QV_OK;   // (the A8W8 operands are prepared by up_ort_conv)
-    if (!m->w4 || m->prequant) return up(eng, m, to_half(w), &out->w);
-    std::vector<uint8_t> q((size_t)N * K, 0);
-    std::vector<float> sc((size_t)N);
-    qv_pack_w8(w.data(), N, K, q.data(), sc.data());
-    TRY(up(eng, m, q, &out->q8));
-    return up(eng, m, sc, &out->sc8);
-}
-
-// MatMulNBits' symmetric block-128 int4 (qv_pack_w4's rule: scale = the block's extreme value / -8, zero point 8) with
-// the FLOAT32 scale: w <- (q - 8) * scale in place -- oracle/fastconformer_ref.py::quant_dequant_int4_f32scale
-void int4_quant_dequant(std::vector<float> &w, int N, int K) {
-    for (int n = 0; n < N; ++n)
-        for (int kb = 0; kb < K / 128; ++kb) {
-            float *blk = w.data() + (size_t)n * K + kb * 128;
-            float vmax = 0.f, amax = -1.f;
-            for (int k = 0; k < 128; ++k) {
-                float a = fabsf(blk[k]);
-                if (a > amax) { amax = a; vmax = blk[k]; }
-            }
-            const float scale = vmax / -8.0f, rs = scale != 0.f ? 1.0f / scale : 0.f;
-            for (int k = 0; k < 128; ++k) {
-                int q = (int)floorf(blk[k] * rs + 8.5f);
-                q = q < 0 ? 0 : q > 15 ? 15 : q;
-                blk[k] = ((float)q - 8.0f) * scale;
-            }
-        }
-}
-
-// quantize_dynamic(weight_type = QInt8) on one Conv weight tensor: scale = max|w| / 127 (the division in double, the
-// result rounded to float32), q = saturate(round-half-even(w / scale)) -- oracle/fastconformer_ref.py::quantize_weight_int8
-// `given` > 0: the scale a pre-quantised file stored for this tensor (w = q * given exactly, so q comes back verbatim).
-float quant_w8_tensor(const std::vector<float> &w, std::vector<int8_t> &q, float given = 0.f) {
-    float amax = 0.f;
-    for (float v : w) amax = std::max(amax, fabsf(v));
-    const float sw = given > 0.f ? given : amax > 0.f ? (float)((double)amax / 127.0) : 1.0f;
-    q.resize(w.size());
-    for (size_t i = 0; i < w.size(); ++i) {
-        float t = nearbyintf(w[i] / sw);   // default rounding mode: half to even
-        t = t < -127.f ? -127.f : t > 127.f ? 127.f : t;
-        q[i] = (int8_t)t;
-    }
-    return sw;
-}
-
-// GEMM-shaped convolution weight [N][K] (rows past n_valid are zero padding): s8 row-major, row sums, scale
-int up_ort_conv(qv_engine *eng, QvModel *m, const std::vector<float> &w, int n_valid, int N, int K, OrtConv *out,
-                float given = 0.f) {
-    std::vector<int8_t> q;
-    out->scale = quant_w8_tensor(w, q, given);
-    std::vector<int8_t> qp((size_t)N * K, 0);
-    std::vector<int32_t> ws(N, 0);
-    for (int n = 0; n < n_valid; ++n) {
-        int32_t sum = 0;
-        for (int k = 0; k < K; ++k) { qp[(size_t)n * K + k] = q[(size_t)n * K + k]; sum += q[(size_t)n * K + k]; }
-        ws[n] = sum;
-    }
-    TRY(up(eng, m, qp, &out->wq));
-    return up(eng, m, ws, &out->wsum);
-}
-
-// depthwise weight [C][9]: integer-valued floats, tap-major [9][C]
-int up_ort_dw(qv_engine *eng, QvModel *m, const std::vector<float> &w, int C, OrtDw *out, float given = 0.f) {
-    std::vector<int8_t> q;
-    out->scale = quant_w8_tensor(w, q, given);
-    std::vector<float> t((size_t)C * 9);
-    for (int c = 0; c < C; ++c)
-        for (int k = 0; k < 9; ++k) t[(size_t)k * C + c] = (float)q[(size_t)c * 9 + k];
-    return up(eng, m, t, &out->wq);
-}
-
-int build_frontend(qv_engine *eng, QvModel *m) {
-    // symmetric Hann(400) centred in 512
-    std::vector<float> win(512, 0.f);
-    for (int i = 0; i < 400; ++i) win[56 + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / 399.0));
-    std::vector<float2> tw(256);
-    for (int k = 0; k < 256; ++k) tw[k] = make_float2((float)cos(-2.0 * M_PI * k / 512.0), (float)sin(-2.0 * M_PI * k / 512.0));
-    // Slaney mel filterbank (librosa.filters.mel, htk=False, norm='slaney'), f64 then f32
-    auto hz_to_mel = [](double f) {
-        const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = 1000.0 / f_sp, logstep = log(6.4) / 27.0;
-        return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
-    };
-    auto mel_to_hz = [](double mm) {
-        const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = 1000.0 / f_sp, logstep = log(6.4) / 27.0;
-        return mm >= min_log_mel ? min_log_hz * exp(logstep * (mm - min_log_mel)) : f_sp * mm;
-    };
-    double mlo = hz_to_mel(0.0), mhi = hz_to_mel(8000.0);
-    std::vector<double> mel_f(QV_NMEL + 2);
-    for (int i = 0; i < QV_NMEL + 2; ++i) mel_f[i] = mel_to_hz(mlo + (mhi - mlo) * i / (QV_NMEL + 1));
-    std::vector<int32_t> lo(QV_NMEL), cnt(QV_NMEL);
-    std::vector<float> w(QV_NMEL * 32, 0.f);
-    for (int i = 0; i < QV_NMEL; ++i) {
-        double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        int first = -1, last = -1;
-        std::vector<float> row(257);
-        for (int k = 0; k < 257; ++k) {
-            double fk = 8000.0 * k / 256.0;
-            double lower = (fk - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
-            double upper = (mel_f[i + 2] - fk) / (mel_f[i + 2] - mel_f[i + 1]);
-            double v = std::max(0.0, std::min(lower, upper));
-            row[k] = (float)(v * enorm);
-            if (row[k] > 0.f) { if (first < 0) first = k; last = k; }
-        }
-        if (first < 0) { first = 0; last = 0; }
-        if (last - first + 1 > 32) { qv_set_error(eng, "mel filter wider than 32 bins"); return QV_ERR_ARG; }
-        lo[i] = first; cnt[i] = last - first + 1;
-        // tap-major [32][80]: the lanes of k_logmel's projection are consecutive filters reading the same tap, so a
-        // wave's load is 320 contiguous bytes (filter-major, every lane hit its own cache line: 64 lines per load)
-        for (int k = first; k <= last; ++k) w[(size_t)(k - first) * QV_NMEL + i] = row[k];
-    }
-    TRY(up(eng, m, win, &m->ft.window));
-    TRY(up(eng, m, tw, &m->ft.twiddle));
-    TRY(up(eng, m, lo, &m->ft.mel_lo));
-    TRY(up(eng, m, cnt, &m->ft.mel_cnt));
-    TRY(up(eng, m, w, &m->ft.mel_w));
-    return QV_OK;
-}
-
-int prepare_weights(qv_engine *eng, QvModel *m, const HostWeights &hw) {
-    const std::string pe = "encoder.pre_encode.";
-    TRY(up(eng, m, tap_major(hw.get(pe + "conv.0.weight"), QV_SUBC), &m->c0_w));
-    TRY(up(eng, m, hw.get(pe + "conv.0.bias"), &m->c0_b));
-    TRY(up(eng, m, tap_major(hw.get(pe + "conv.2.weight"), QV_SUBC), &m->dw2_w));
-    TRY(up(eng, m, hw.get(pe + "conv.2.bias"), &m->dw2_b));
-    TRY(up(eng, m, to_half(hw.get(pe + "conv.3.weight")), &m->pw3_w));
-    TRY(up(eng, m, hw.get(pe + "conv.3.bias"), &m->pw3_b));
-    TRY(up(eng, m, tap_major(hw.get(pe + "conv.5.weight"), QV_SUBC), &m->dw5_w));
-    TRY(up(eng, m, hw.get(pe + "conv.5.bias"), &m->dw5_b));
-    TRY(up(eng, m, to_half(hw.get(pe + "conv.6.weight")), &m->pw6_w));
-    TRY(up(eng, m, hw.get(pe + "conv.6.bias"), &m->pw6_b));
-    if (m->ort) {
-        TRY(up_ort_dw(eng, m, hw.get(pe + "conv.0.weight"), QV_SUBC, &m->o_c0, hw.int8_scale(pe + "conv.0.weight")));
-        TRY(up_ort_dw(eng, m, hw.get(pe + "conv.2.weight"), QV_SUBC, &m->o_dw2, hw.int8_scale(pe + "conv.2.weight")));
-        TRY(up_ort_dw(eng, m, hw.get(pe + "conv.5.weight"), QV_SUBC, &m->o_dw5, hw.int8_scale(pe + "conv.5.weight")));
-        TRY(up_ort_conv(eng, m, hw.get(pe + "conv.3.weight"), QV_SUBC, QV_SUBC, QV_SUBC, &m->o_pw3, hw.int8_scale(pe + "conv.3.weight")));
-        TRY(up_ort_conv(eng, m, hw.get(pe + "conv.6.weight"), QV_SUBC, QV_SUBC, QV_SUBC, &m->o_pw6, hw.int8_scale(pe + "conv.6.weight")));
-        TRY(up_ort_conv(eng, m, hw.get("ctc_decoder.decoder_layers.0.weight"), QV_VOCAB, HEAD_N, QV_D, &m->o_head,
-                        hw.int8_scale("ctc_decoder.decoder_layers.0.weight")));
-    }
-    {
-        // Linear(2560 -> 512): NeMo flattens [C=256][F=10] as c*10+f; activations here are
-        // channels-last [F][C], so permute K to f*256+c
-        std::vector<float> w = hw.get(pe + "out.weight");
-        if (m->ort && !m->prequant) {
-            // MatMulNBits quantises along the ORIGINAL K order (blocks of 128 consecutive c*10+f); the permuted layout
-            // no longer has those blocks, so this one Linear is quantised -> dequantised here and runs as an f16 GEMM
-            // on exactly the values (q - 8) * scale
-            int4_quant_dequant(w, QV_D, 2560);
-        }
-        std::vector<half_t> p((size_t)QV_D * 2560);
-        for (int n = 0; n < QV_D; ++n)
-            for (int c = 0; c < QV_SUBC; ++c)
-                for (int f = 0; f < 10; ++f) p[(size_t)n * 2560 + f * QV_SUBC + c] = (half_t)w[(size_t)n * 2560 + c * 10 + f];
-        TRY(up(eng, m, p, &m->sub_out_w));
-        TRY(up(eng, m, hw.get(pe + "out.bias"), &m->sub_out_b));
-    }
-    {
-        const std::vector<float> &w = hw.get("ctc_decoder.decoder_layers.0.weight");
-        const std::vector<float> &b = hw.get("ctc_decoder.decoder_layers.0.bias");
-        std::vector<half_t> p((size_t)HEAD_N * QV_D, (half_t)0.f);
-        std::vector<float> pb(HEAD_N, 0.f);
-        for (size_t i = 0; i < (size_t)QV_VOCAB * QV_D; ++i) p[i] = (half_t)w[i];
-        for (int i = 0; i < QV_VOCAB; ++i) pb[i] = b[i];
-        TRY(up(eng, m, p, &m->head_w));
-        TRY(up(eng, m, pb, &m->head_b));
-    }
-    std::vector<float> posw((size_t)N_LAYERS * QV_D * QV_D);
-    // the file's own int4 grid of a Linear weight (pre-quantised files only), concatenated along N for fused weights
-    std::vector<float> gs_tmp, gz_tmp;
-    auto grid_of = [&](std::initializer_list<std::string> names, const std::vector<float> *&gs, const std::vector<float> *&gz) {
-        gs = gz = nullptr;
-        if (!m->prequant) return;
-        gs_tmp.clear(); gz_tmp.clear();
-        for (const std::string &n : names) {
-            const std::vector<float> *a = hw.int4_scale(n), *b = hw.int4_zp(n);
-            if (!a || !b || a->size() != b->size()) return;
-            gs_tmp.insert(gs_tmp.end(), a->begin(), a->end());
-            gz_tmp.insert(gz_tmp.end(), b->begin(), b->end());
-        }
-        gs = &gs_tmp; gz = &gz_tmp;
-    };
-    auto up_lin = [&](const std::string &name, int N, int K, WMat *out) {
-        const std::vector<float> *gs, *gz;
-        grid_of({name}, gs, gz);
-        return up_mat(eng, m, hw.get(name), N, K, out, gs, gz);
-    };
-    std::vector<float> pos_gs, pos_gz;
-    bool pos_grid = m->prequant;
-    for (int i = 0; i < N_LAYERS; ++i) {
-        std::string p = "encoder.layers." + std::to_string(i) + ".";
-        LayerW &L = m->L[i];
-        const char *lns[5] = {"norm_feed_forward1", "norm_self_att", "norm_conv", "norm_feed_forward2", "norm_out"};
-        for (int k = 0; k < 5; ++k) {
-            TRY(up(eng, m, hw.get(p + lns[k] + ".weight"), &L.ln_g[k]));
-            TRY(up(eng, m, hw.get(p + lns[k] + ".bias"), &L.ln_b[k]));
-        }
-        TRY(up_lin(p + "feed_forward1.linear1.weight", QV_FF, QV_D, &L.ff1_w1));
-        TRY(up(eng, m, hw.get(p + "feed_forward1.linear1.bias"), &L.ff1_b1));
-        TRY(up_lin(p + "feed_forward1.linear2.weight", QV_D, QV_FF, &L.ff1_w2));
-        TRY(up(eng, m, hw.get(p + "feed_forward1.linear2.bias"), &L.ff1_b2));
-        TRY(up_lin(p + "feed_forward2.linear1.weight", QV_FF, QV_D, &L.ff2_w1));
-        TRY(up(eng, m, hw.get(p + "feed_forward2.linear1.bias"), &L.ff2_b1));
-        TRY(up_lin(p + "feed_forward2.linear2.weight", QV_D, QV_FF, &L.ff2_w2));
-        TRY(up(eng, m, hw.get(p + "feed_forward2.linear2.bias"), &L.ff2_b2));
-        {
-            std::vector<float> w, b;
-            for (const char *lin : {"linear_q", "linear_k", "linear_v"}) {
-                const auto &ww = hw.get(p + "self_attn." + lin + ".weight");
-                const auto &bb = hw.get(p + "self_attn." + lin + ".bias");
-                w.insert(w.end(), ww.begin(), ww.end());
-                b.insert(b.end(), bb.begin(), bb.end());
-            }
-            const std::vector<float> *gs, *gz;
-            grid_of({p + "self_attn.linear_q.weight", p + "self_attn.linear_k.weight", p + "self_attn.linear_v.weight"}, gs, gz);
-            TRY(up_mat(eng, m, w, 3 * QV_D, QV_D, &L.qkv_w, gs, gz));
-            TRY(up(eng, m, b, &L.qkv_b));
-        }
-        TRY(up_lin(p + "self_attn.linear_out.weight", QV_D, QV_D, &L.out_w));
-        TRY(up(eng, m, hw.get(p + "self_attn.linear_out.bias"), &L.out_b));
-        TRY(up(eng, m, hw.get(p + "self_attn.pos_bias_u"), &L.bias_u));
-        TRY(up(eng, m, hw.get(p + "self_attn.pos_bias_v"), &L.bias_v));
-        {
-            const auto &pw = hw.get(p + "self_attn.linear_pos.weight");
-            for (size_t k = 0; k < pw.size(); ++k) posw[(size_t)i * QV_D * QV_D + k] = pw[k];
-            const std::vector<float> *a = hw.int4_scale(p + "self_attn.linear_pos.weight"), *b = hw.int4_zp(p + "self_attn.linear_pos.weight");
-            if (pos_grid && a && b && a->size() == b->size()) {
-                pos_gs.insert(pos_gs.end(), a->begin(), a->end());
-                pos_gz.insert(pos_gz.end(), b->begin(), b->end());
-            } else pos_grid = false;
-        }
-        {
-            // GLU pairing: 64-column groups = [32 value channels | their 32 gate channels]
-            const auto &w = hw.get(p + "conv.pointwise_conv1.weight");
-            const auto &b = hw.get(p + "conv.pointwise_conv1.bias");
-            std::vector<float> pwm((size_t)2 * QV_D * QV_D);
-            std::vector<float> pb(2 * QV_D);
-            for (int g = 0; g < QV_D / 32; ++g)
-                for (int j = 0; j < 32; ++j) {
-                    int ra = g * 32 + j, rg = QV_D + g * 32 + j;
-                    int da = g * 64 + j, dg = g * 64 + 32 + j;
-                    for (int k = 0; k < QV_D; ++k) {
-                        pwm[(size_t)da * QV_D + k] = w[(size_t)ra * QV_D + k];
-                        pwm[(size_t)dg * QV_D + k] = w[(size_t)rg * QV_D + k];
-                    }
-                    pb[da] = b[ra];
-                    pb[dg] = b[rg];
-                }
-            TRY(up_mat8(eng, m, pwm, 2 * QV_D, QV_D, &L.pw1_w));
-            TRY(up(eng, m, pb, &L.pw1_b));
-            // (one scale per tensor: the row permutation changes neither the scale nor the codes)
-            if (m->ort) TRY(up_ort_conv(eng, m, pwm, 2 * QV_D, 2 * QV_D, QV_D, &L.o_pw1, hw.int8_scale(p + "conv.pointwise_conv1.weight")));
-        }
-        {
-            // fold eval-mode BatchNorm into the depthwise conv
-            const auto &w = hw.get(p + "conv.depthwise_conv.weight");
-            const auto &b = hw.get(p + "conv.depthwise_conv.bias");
-            const auto &g = hw.get(p + "conv.batch_norm.weight");
-            const auto &be = hw.get(p + "conv.batch_norm.bias");
-            const auto &mu = hw.get(p + "conv.batch_norm.running_mean");
-            const auto &var = hw.get(p + "conv.batch_norm.running_var");
-            std::vector<float> fw((size_t)QV_D * 9), fb(QV_D);
-            for (int c = 0; c < QV_D; ++c) {
-                float s = g[c] / sqrtf(var[c] + 1e-5f);
-                for (int k = 0; k < 9; ++k) fw[(size_t)c * 9 + k] = w[(size_t)c * 9 + k] * s;
-                fb[c] = (b[c] - mu[c]) * s + be[c];
-            }
-            TRY(up(eng, m, tap_major(fw, QV_D), &L.dw_w));
-            TRY(up(eng, m, fb, &L.dw_b));
-            if (m->ort) {
-                // the reference quantises the RAW depthwise weight; BatchNorm stays a float op behind it
-                std::vector<float> al(QV_D), bt(QV_D);
-                for (int c = 0; c < QV_D; ++c) {
-                    al[c] = g[c] * (1.0f / sqrtf(var[c] + 1e-5f));
-                    bt[c] = fmaf(-mu[c], al[c], be[c]);
-                }
-                TRY(up_ort_dw(eng, m, w, QV_D, &L.o_dw, hw.int8_scale(p + "conv.depthwise_conv.weight")));
-                TRY(up(eng, m, b, &L.o_dw_b));
-                TRY(up(eng, m, al, &L.bn_alpha));
-                TRY(up(eng, m, bt, &L.bn_beta));
-            }
-        }
-        TRY(up_mat8(eng, m, hw.get(p + "conv.pointwise_conv2.weight"), QV_D, QV_D, &L.pw2_w));
-        if (m->ort)
-            TRY(up_ort_conv(eng, m, hw.get(p + "conv.pointwise_conv2.weight"), QV_D, QV_D, QV_D, &L.o_pw2,
-                            hw.int8_scale(p + "conv.pointwise_conv2.weight")));
-        TRY(up(eng, m, hw.get(p + "conv.pointwise_conv2.bias"), &L.pw2_b));
-    }
-    TRY(up_mat(eng, m, posw, N_LAYERS * QV_D, QV_D, &m->pos_w, pos_grid ? &pos_gs : nullptr, pos_grid ? &pos_gz : nullptr));
-    // linear_pos has no bias; the GEMM epilogue always reads one
-    TRY(up(eng, m, std::vector<float>((size_t)N_LAYERS * QV_D, 0.f), &m->zero_bias));
-    return QV_OK;
-}
+// the table argument of launch_logmel (twiddle: the {re, im} pairs as the float2 the kernel declares)
+FrontendTab frontend_tab(const ModelW &w) { return {w.window, (const float2 *)w.twiddle, w.mel_lo, w.mel_cnt, w.mel_w}; }
 
 int stage_len(int t) { return (t + 2 - 3) / 2 + 1; }
 
@@ -574,7 +186,7 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, const QvSwitches &sw, hipStre
     QV_HIP(hipMalloc((void **)&d_pe, pe.size() * sizeof(half_t)));
     QV_HIP(hipMalloc((void **)&d_out, (size_t)R * N_LAYERS * QV_D * sizeof(half_t)));
     QV_HIP(hipMemcpyAsync(d_pe, pe.data(), pe.size() * sizeof(half_t), hipMemcpyHostToDevice, stream));
-    launch_gemm(EPI_F16, gemm_args(d_pe, m->pos_w, m->zero_bias, d_out, R, N_LAYERS * QV_D, QV_D, N_LAYERS * QV_D, 1.f), stream, sw);
+    launch_gemm(EPI_F16, gemm_args(d_pe, m->w.pos_w, m->w.zero_bias, d_out, R, N_LAYERS * QV_D, QV_D, N_LAYERS * QV_D, 1.f), stream, sw);
     QV_HIP(hipStreamSynchronize(stream));
     QV_HIP(hipFree(d_pe));
     m->allocs.push_back(d_out);
@@ -587,45 +199,45 @@ int get_pos(qv_engine *eng, QvModel *m, int t_max, const QvSwitches &sw, hipStre
 int alloc_context(qv_engine *eng, QvModel *m, int k, bool sub_unfused, bool sub35_unfused) {
     QvActs &a = m->ctx_acts[k];
     const size_t Bz = (size_t)m->max_batch, M = m->rows_cap, lens_words = LenRows::words(Bz);
-    TRY(dal(eng, m, Bz * m->tm_cap * QV_NMEL, &a.feats));
-    TRY(dal(eng, m, qv_melstats_doubles(Bz), &a.mel_stats));
+    TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->tm_cap * QV_NMEL, &a.feats));
+    TRY(qv_dev_zeroed(eng, m->allocs, qv_melstats_doubles(Bz), &a.mel_stats));
     // the conv0 activation only exists on the two-kernel cross-check path (QVERSE_SUB_UNFUSED=1)
-    if (sub_unfused) TRY(dal(eng, m, Bz * m->t1_cap * 40 * QV_SUBC, &a.c0));
-    TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1));
+    if (sub_unfused) TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t1_cap * 40 * QV_SUBC, &a.c0));
+    TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1));
     // the conv.3 activation and the dense conv.6 output only exist where conv.3 / conv.5 / conv.6 / k_pack_rows run as four
     // launches: the ORT front end and the cross-check path of k_sub35 (QVERSE_SUB35_UNFUSED=1)
     a.sub35 = !m->ort && !sub35_unfused;
-    if (!a.sub35) TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1p));
-    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2));
-    if (!a.sub35) TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2p));
-    TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2k));
-    TRY(dal(eng, m, M * QV_D, &a.x));
-    TRY(dal(eng, m, M * QV_D, &a.ln));
-    TRY(dal(eng, m, M * QV_FF, &a.hbuf));
-    TRY(dal(eng, m, M * 2 * QV_D, &a.qk));
-    TRY(dal(eng, m, Bz * QV_D * pad32(m->t3_cap), &a.vt));
-    TRY(dal(eng, m, M * QV_D, &a.att));
-    TRY(dal(eng, m, M * QV_D, &a.glu));
-    TRY(dal(eng, m, M * QV_D, &a.dw));
-    TRY(dal(eng, m, M * QV_D, &a.xh));
-    TRY(dal(eng, m, M * HEAD_N, &a.logits));
-    TRY(dal(eng, m, lens_words, &a.lens_dev));
-    TRY(dal(eng, m, M, &a.row_map));
+    if (!a.sub35) TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1p));
+    TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2));
+    if (!a.sub35) TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2p));
+    TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2k));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.x));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.ln));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_FF, &a.hbuf));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * 2 * QV_D, &a.qk));
+    TRY(qv_dev_zeroed(eng, m->allocs, Bz * QV_D * pad32(m->t3_cap), &a.vt));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.att));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.glu));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.dw));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.xh));
+    TRY(qv_dev_zeroed(eng, m->allocs, M * HEAD_N, &a.logits));
+    TRY(qv_dev_zeroed(eng, m->allocs, lens_words, &a.lens_dev));
+    TRY(qv_dev_zeroed(eng, m->allocs, M, &a.row_map));
     QV_HIP(hipHostMalloc((void **)&a.lens_host, sizeof(int32_t) * lens_words * QV_STAGE_SLOTS, hipHostMallocDefault));
     for (int i = 0; i < QV_STAGE_SLOTS; ++i) QV_HIP(hipEventCreateWithFlags(&a.lens_copied[i], hipEventDisableTiming));
-    if (m->save_taps) TRY(dal(eng, m, (size_t)(N_LAYERS + 1) * M * QV_D, &a.tap_x));
+    if (m->save_taps) TRY(qv_dev_zeroed(eng, m->allocs, (size_t)(N_LAYERS + 1) * M * QV_D, &a.tap_x));
     if (m->ort) {
-        TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1f));
-        TRY(dal(eng, m, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1pf));
-        TRY(dal(eng, m, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2f));
-        TRY(dal(eng, m, M * QV_D, &a.gluf));
-        TRY(dal(eng, m, M * QV_D, &a.dwf));
-        TRY(dal(eng, m, std::max(Bz * m->t2_cap * 20 * QV_SUBC, M * QV_D), &a.q8));
-        TRY(dal(eng, m, (size_t)MM_SITES * Bz * QV_MM_STRIDE, &a.mm));
+        TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1f));
+        TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t2_cap * 20 * QV_SUBC, &a.c1pf));
+        TRY(qv_dev_zeroed(eng, m->allocs, Bz * m->t3_cap * 10 * QV_SUBC, &a.c2f));
+        TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.gluf));
+        TRY(qv_dev_zeroed(eng, m->allocs, M * QV_D, &a.dwf));
+        TRY(qv_dev_zeroed(eng, m->allocs, std::max(Bz * m->t2_cap * 20 * QV_SUBC, M * QV_D), &a.q8));
+        TRY(qv_dev_zeroed(eng, m->allocs, (size_t)MM_SITES * Bz * QV_MM_STRIDE, &a.mm));
         if (m->save_taps) {
-            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &a.tap_lnc));
-            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &a.tap_glu));
-            TRY(dal(eng, m, (size_t)N_LAYERS * M * QV_D, &a.tap_dw));
+            TRY(qv_dev_zeroed(eng, m->allocs, (size_t)N_LAYERS * M * QV_D, &a.tap_lnc));
+            TRY(qv_dev_zeroed(eng, m->allocs, (size_t)N_LAYERS * M * QV_D, &a.tap_glu));
+            TRY(qv_dev_zeroed(eng, m->allocs, (size_t)N_LAYERS * M * QV_D, &a.tap_dw));
         }
     }
     return QV_OK;
@@ -650,12 +262,20 @@ int qv_model_create(qv_engine *eng, const qv_config *cfg, const QvSwitches &sw, 
         if (int rc = load_weight_file(cfg->weights_path, hw, err)) { qv_set_error(eng, err); return rc; }
     } else init_random(hw, cfg->random_weights_seed);
     m->prequant = hw.prequantised();
-    TRY(build_frontend(eng, m));
-    try {
-        TRY(prepare_weights(eng, m, hw));
-    } catch (const QvMissingWeight &e) {   // HostWeights::get: a tensor outside weight_shapes() was asked for
-        qv_set_error(eng, e.what());
-        return QV_ERR_IO;
+    {
+        // a refusal of the preparation leaves its text in err; a HIP failure of the sink has already set the engine's error
+        DevSink sink = {eng, m};
+        std::string err;
+        WeightPrep<DevSink> prep = {sink, m->w4, m->ort, m->prequant, m->w, err};
+        int rc = prep.build_frontend();
+        try {
+            if (!rc) rc = prep.prepare_weights(hw);
+        } catch (const QvMissingWeight &e) {   // HostWeights::get: a tensor outside weight_shapes() was asked for
+            qv_set_error(eng, e.what());
+            return QV_ERR_IO;
+        }
+        if (rc && !err.empty()) qv_set_error(eng, err);
+        if (rc) return rc;
     }
     int B = cfg->max_batch;
     m->max_batch = B;
@@ -762,7 +382,7 @@ GemmArgs layer_gemm_args(const QvModel *m, const QvActs &a, int M, int T, const 
 // QV_PREC_ORT_MIXED: pointwise_conv1 + GLU of layer l on the s8 rows in q8; input range in the layer's first site, the output's goes to its second
 GemmArgs ort_pw1_args(const QvModel *m, const QvActs &a, int M, int l) {
     uint32_t *mm_ln = a.mm + (size_t)MM_LAYER(l) * m->max_batch * QV_MM_STRIDE;
-    return gemm_args(a.q8, m->L[l].o_pw1, m->L[l].pw1_b, a.gluf, M, 2 * QV_D, QV_D / 2, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_ln,
+    return gemm_args(a.q8, m->w.L[l].o_pw1, m->w.L[l].pw1_b, a.gluf, M, 2 * QV_D, QV_D / 2, QV_D, RowOwner{a.row_map, nullptr, 0, 0}, mm_ln,
                      mm_ln + (size_t)m->max_batch * QV_MM_STRIDE);
 }
 
@@ -774,31 +394,31 @@ struct Fwd {
     uint32_t *mm(int site) const { return a.mm + (size_t)site * m->max_batch * QV_MM_STRIDE; }   // QV_PREC_ORT_MIXED: range keys of a quantiser site
 
     void sub_out() const {   // Linear(2560 -> 512) and xscaling (x * sqrt(d_model)) in one epilogue
-        GemmArgs g = gemm_args(a.c2k, WMat{m->sub_out_w}, m->sub_out_b, a.x, sh.M, QV_D, 2560, QV_D, sqrtf((float)QV_D));
+        GemmArgs g = gemm_args(a.c2k, WMat{m->w.sub_out_w}, m->w.sub_out_b, a.x, sh.M, QV_D, 2560, QV_D, sqrtf((float)QV_D));
         g.in_flight = m->n_ctx;
         launch_gemm(EPI_F32, g, s, sw);
     }
     void frontend_f16() const {
-        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, sh.B, s, sw);
+        launch_logmel(audio, n_max, d.n_samples, frontend_tab(m->w), a.feats, sh.tm_max, a.mel_stats, sh.B, s, sw);
         if (a.c0) {
             // cross-check path: conv0 and the depthwise conv as two kernels through HBM
-            launch_conv0(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, a.c0, sh.t1m, sh.B, s);
-            launch_dwconv2d(a.c0, sh.t1m, 40, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, 20, sh.B, s);
+            launch_conv0(a.feats, sh.tm_max, d.tm, a.mel_stats, m->w.c0_w, m->w.c0_b, a.c0, sh.t1m, sh.B, s);
+            launch_dwconv2d(a.c0, sh.t1m, 40, d.l1, m->w.dw2_w, m->w.dw2_b, a.c1, sh.t2m, 20, sh.B, s);
         } else {
-            launch_sub01(a.feats, sh.tm_max, d.tm, a.mel_stats, m->c0_w, m->c0_b, d.l1, m->dw2_w, m->dw2_b, a.c1, sh.t2m, sh.B, s, sw);
+            launch_sub01(a.feats, sh.tm_max, d.tm, a.mel_stats, m->w.c0_w, m->w.c0_b, d.l1, m->w.dw2_w, m->w.dw2_b, a.c1, sh.t2m, sh.B, s, sw);
         }
         auto pw = [&](const half_t *A, const half_t *W, const float *bias, half_t *out, int M) {   // pointwise conv + ReLU
             launch_gemm(EPI_F16_RELU, gemm_args(A, WMat{W}, bias, out, M, QV_SUBC, QV_SUBC, QV_SUBC, 1.f), s, sw);
         };
         if (a.sub35) {
             // conv.3 + conv.5 in one kernel, c2 packed from here on: conv.6 runs on the valid rows only and writes c2k itself
-            launch_sub35(a.c1, sh.t2m, m->pw3_w, m->pw3_b, m->dw5_w, m->dw5_b, d.l2, d.l3, d.row_off, a.c2, a.row_map, sh.t3m, sh.B, s, sw);
-            pw(a.c2, m->pw6_w, m->pw6_b, a.c2k, sh.M * 10);
+            launch_sub35(a.c1, sh.t2m, m->w.pw3_w, m->w.pw3_b, m->w.dw5_w, m->w.dw5_b, d.l2, d.l3, d.row_off, a.c2, a.row_map, sh.t3m, sh.B, s, sw);
+            pw(a.c2, m->w.pw6_w, m->w.pw6_b, a.c2k, sh.M * 10);
         } else {
             // cross-check path: four launches, c1p and the dense c2 / c2p through HBM
-            pw(a.c1, m->pw3_w, m->pw3_b, a.c1p, sh.B * sh.t2m * 20);
-            launch_dwconv2d(a.c1p, sh.t2m, 20, d.l2, m->dw5_w, m->dw5_b, a.c2, sh.t3m, 10, sh.B, s);
-            pw(a.c2, m->pw6_w, m->pw6_b, a.c2p, sh.B * sh.t3m * 10);
+            pw(a.c1, m->w.pw3_w, m->w.pw3_b, a.c1p, sh.B * sh.t2m * 20);
+            launch_dwconv2d(a.c1p, sh.t2m, 20, d.l2, m->w.dw5_w, m->w.dw5_b, a.c2, sh.t3m, 10, sh.B, s);
+            pw(a.c2, m->w.pw6_w, m->w.pw6_b, a.c2p, sh.B * sh.t3m * 10);
             launch_pack_rows(a.c2p, sh.t3m, 10 * QV_SUBC, d.l3, d.row_off, a.c2k, a.row_map, sh.B, s);
         }
         sub_out();
@@ -809,16 +429,16 @@ struct Fwd {
         const int B = sh.B, M2 = B * sh.t2m * 20, M3 = B * sh.t3m * 10;
         const RowOwner own2 = {nullptr, d.l2, sh.t2m * 20, 20}, own3 = {nullptr, d.l3, sh.t3m * 10, 10};   // dense rows
         launch_mm_init(a.mm, (size_t)MM_SITES * m->max_batch * QV_MM_STRIDE, s);
-        launch_logmel(audio, n_max, d.n_samples, m->ft, a.feats, sh.tm_max, a.mel_stats, B, s, sw);
+        launch_logmel(audio, n_max, d.n_samples, frontend_tab(m->w), a.feats, sh.tm_max, a.mel_stats, B, s, sw);
         launch_mel_minmax(a.feats, d.n_samples, sh.tm_max, a.mel_stats, mm(MM_MEL), B, s);
         for (int pass = 0; pass < 2; ++pass)
-            launch_sub01_ort(pass, a.feats, sh.tm_max, d.tm, a.mel_stats, m->o_c0.wq, m->o_c0.scale, m->c0_b, d.l1, m->o_dw2.wq,
-                             m->o_dw2.scale, m->dw2_b, d.l2, mm(MM_MEL), mm(MM_C0), mm(MM_C1), a.c1f, sh.t2m, B, s, sw);
+            launch_sub01_ort(pass, a.feats, sh.tm_max, d.tm, a.mel_stats, m->w.o_c0.wq, m->w.o_c0.scale, m->w.c0_b, d.l1, m->w.o_dw2.wq,
+                             m->w.o_dw2.scale, m->w.dw2_b, d.l2, mm(MM_MEL), mm(MM_C0), mm(MM_C1), a.c1f, sh.t2m, B, s, sw);
         launch_quant_rows(a.c1f, M2, QV_SUBC, own2, mm(MM_C1), a.q8, s);
-        launch_gemm(EPI_F32_RELU, gemm_args(a.q8, m->o_pw3, m->pw3_b, a.c1pf, M2, QV_SUBC, QV_SUBC / 2, QV_SUBC, own2, mm(MM_C1), mm(MM_C1P)), s, sw);
-        launch_dwconv2d_ort(a.c1pf, sh.t2m, 20, d.l2, m->o_dw5.wq, m->o_dw5.scale, m->dw5_b, d.l3, mm(MM_C1P), mm(MM_C2), a.c2f, sh.t3m, 10, B, s);
+        launch_gemm(EPI_F32_RELU, gemm_args(a.q8, m->w.o_pw3, m->w.pw3_b, a.c1pf, M2, QV_SUBC, QV_SUBC / 2, QV_SUBC, own2, mm(MM_C1), mm(MM_C1P)), s, sw);
+        launch_dwconv2d_ort(a.c1pf, sh.t2m, 20, d.l2, m->w.o_dw5.wq, m->w.o_dw5.scale, m->w.dw5_b, d.l3, mm(MM_C1P), mm(MM_C2), a.c2f, sh.t3m, 10, B, s);
         launch_quant_rows(a.c2f, M3, QV_SUBC, own3, mm(MM_C2), a.q8, s);
-        launch_gemm(EPI_F16_RELU, gemm_args(a.q8, m->o_pw6, m->pw6_b, a.c2p, M3, QV_SUBC, QV_SUBC / 2, QV_SUBC, own3, mm(MM_C2), nullptr), s, sw);
+        launch_gemm(EPI_F16_RELU, gemm_args(a.q8, m->w.o_pw6, m->w.pw6_b, a.c2p, M3, QV_SUBC, QV_SUBC / 2, QV_SUBC, own3, mm(MM_C2), nullptr), s, sw);
         launch_pack_rows(a.c2p, sh.t3m, 10 * QV_SUBC, d.l3, d.row_off, a.c2k, a.row_map, B, s);
         sub_out();
     }
@@ -872,9 +492,9 @@ struct Fwd {
         return QV_OK;
     }
     int layer_out(int l) const {   // norm_out (+ next layer's first LayerNorm; hook class 2)
-        const LayerW &L = m->L[l];
+        const LayerW &L = m->w.L[l];
         hooked(2, [&] {
-            if (l + 1 < N_LAYERS) launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], m->L[l + 1].ln_g[0], m->L[l + 1].ln_b[0], a.ln, sh.M, s);
+            if (l + 1 < N_LAYERS) launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], m->w.L[l + 1].ln_g[0], m->w.L[l + 1].ln_b[0], a.ln, sh.M, s);
             // last layer: the f16 copy of the encoder output (CTC head operand) comes out of the same pass
             else launch_layernorm2(a.x, L.ln_g[4], L.ln_b[4], nullptr, nullptr, a.xh, sh.M, s);
         }, false);
@@ -886,9 +506,9 @@ struct Fwd {
             const RowOwner own = {a.row_map, nullptr, 0, 0};
             launch_rows_minmax(a.x, sh.M, a.row_map, mm(MM_HEAD), s);
             launch_quant_rows(a.x, sh.M, QV_D, own, mm(MM_HEAD), a.q8, s);
-            launch_gemm(EPI_F32, gemm_args(a.q8, m->o_head, m->head_b, a.logits, sh.M, HEAD_N, QV_D / 2, HEAD_N, own, mm(MM_HEAD), nullptr), s, sw);
+            launch_gemm(EPI_F32, gemm_args(a.q8, m->w.o_head, m->w.head_b, a.logits, sh.M, HEAD_N, QV_D / 2, HEAD_N, own, mm(MM_HEAD), nullptr), s, sw);
         } else {
-            launch_gemm(EPI_F32, gemm_args(a.xh, WMat{m->head_w}, m->head_b, a.logits, sh.M, HEAD_N, QV_D, HEAD_N, 1.f), s, sw);
+            launch_gemm(EPI_F32, gemm_args(a.xh, WMat{m->w.head_w}, m->w.head_b, a.logits, sh.M, HEAD_N, QV_D, HEAD_N, 1.f), s, sw);
         }
     }
 };
@@ -902,9 +522,9 @@ int launch_all(qv_engine *eng, const QvModel *m, const QvActs &a, const FwdShape
     else   // (front end skipped: the encoder still needs a row_map; on the packed path the c2 buffer stands in for c2p)
         launch_pack_rows(a.sub35 ? a.c2 : a.c2p, sh.t3m, 10 * QV_SUBC, f.d.l3, f.d.row_off, a.c2k, a.row_map, sh.B, s);
     TRY(f.save_x(0));
-    f.layernorm(m->L[0], 0, false);
+    f.layernorm(m->w.L[0], 0, false);
     for (int l = 0; l < N_LAYERS; ++l) {
-        const LayerW &L = m->L[l];
+        const LayerW &L = m->w.L[l];
         f.ffn_half(L.ff1_w1, L.ff1_b1, L.ff1_w2, L.ff1_b2);
         f.attention_block(L, l);
         if (m->ort) TRY(f.conv_module_ort(L, l));
@@ -984,7 +604,7 @@ static int replay_args(qv_engine *eng, QvModel *m, int k, int which, GemmArgs &g
     QvActs &a = m->ctx_acts[k];
     const int M = a.last.M, T = a.last.T;
     if (M <= 0) { qv_set_error(eng, "replay needs a previous forward"); return QV_ERR_ARG; }
-    const LayerW &L = m->L[0];
+    const LayerW &L = m->w.L[0];
     auto args = [&](const half_t *A, int K, const WMat &W, const float *bias, void *out, int N, int ldo, float alpha) {
         return layer_gemm_args(m, a, M, T, A, K, W, bias, out, N, ldo, alpha);
     };
@@ -1018,7 +638,7 @@ void qv_model_weights_info(const QvModel *m, char *out, int cap) {
         snprintf(out, (size_t)cap, "precision %s; weights quantised by the engine%s", prec, m->w4 ? " (symmetric block-128 int4 Linear)" : " (none: f16)");
     else
         snprintf(out, (size_t)cap, "precision %s; pre-quantised file: %d Linear tensors on the file's own int4 grid (W4A16), %d as "
-                 "dequantised f16 values%s", prec, m->prequant_w4_linears, m->prequant_f16_linears,
+                 "dequantised f16 values%s", prec, m->w.prequant_w4_linears, m->w.prequant_f16_linears,
                  m->ort ? "; Conv weights on the file's int8 integers" : m->w4 ? "; pointwise-conv weights as dequantised f16 values" : "");
 }
 

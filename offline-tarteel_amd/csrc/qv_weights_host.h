@@ -1,7 +1,7 @@
 // qv_weights_host.h -- where the acoustic model's weights come from, on the host: the tensors the model needs
 // (weight_shapes), the seeded init, the flat weight file.  HIP-free (the standard library only), so
-// tools/file_readers_check.cpp runs the file reader under ASan + UBSan on a machine without a GPU; qv_model.hip lays the
-// tensors out for the device.
+// tools/file_readers_check.cpp runs the file reader under ASan + UBSan on a machine without a GPU; qv_model_prep_host.h
+// lays the tensors out for the device.
 #pragma once
 
 #include <math.h>

@@ -1,6 +1,6 @@
 // qv_wpack_host.h -- host-side packers for the quantised weight layouts the GEMM kernels read (GemmArgs in qv_kernels.h:
 // Wq / wscale for W4A16, W8 / w8scale for W8A16).  HIP-free (the standard library only): the half type H of the int4 scale
-// table is the including file's (_Float16 in the library).  qv_model.hip and qv_capi.hip are the callers.
+// table is the including file's (_Float16 in the library).  qv_model_prep_host.h and qv_capi.hip are the callers.
 #pragma once
 
 #include <math.h>

@@ -313,7 +313,7 @@ def dynamic_quantize_linear(x: torch.Tensor):
 def quantize_weight_int8(wt: torch.Tensor):
     """quantize_dynamic(weight_type=QInt8) on a Conv weight: ONE symmetric scale per tensor, scale = max|w| / 127,
     q = saturate(round-half-even(w / scale)) to [-127, 127].  Returns (q as integer-valued float64, scale f32).
-    csrc/qv_model.hip::quant_w8_tensor performs the identical arithmetic."""
+    csrc/qv_model_prep_host.h::quant_w8_tensor performs the identical arithmetic."""
     amax = float(wt.abs().max())
     sw = np.float32(amax / 127.0) if amax > 0 else np.float32(1.0)
     return torch.clamp(torch.round(wt / float(sw)), -127, 127).to(torch.float64), sw

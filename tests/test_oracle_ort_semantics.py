@@ -93,7 +93,7 @@ def test_ort_forward_is_per_utterance_like_the_reference_feeds_it():
 
 def test_batch_norm_eval_formula_the_device_uses_is_torchs():
     """csrc/qv_ort.hip::k_dwconv1d_ort applies BatchNorm as fma(y, alpha, beta) with alpha = gamma * (1 / sqrt(var + eps)),
-    beta = fma(-mean, alpha, bias) (prepared in csrc/qv_model.hip): torch's eval-mode batch_norm on the CPU, bit for bit."""
+    beta = fma(-mean, alpha, bias) (prepared in csrc/qv_model_prep_host.h): torch's eval-mode batch_norm on the CPU, bit for bit."""
     rng = np.random.default_rng(3)
     C, T = 512, 97
     y = rng.standard_normal((1, C, T)).astype(np.float32) * 3
