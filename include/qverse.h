@@ -639,6 +639,66 @@ int qv_beam_batch(qv_engine *e, const float *audio_dev, const int64_t *lengths_h
                   int32_t max_span, int32_t beam, int32_t k, qv_beam_info *info_host, qv_beam_entry *entries_host,
                   int32_t *ids_host, int32_t pitch, void *stream);
 
+/* ---- exhaustive CTC scan ------------------------------------------------------------------------------
+ * Every verse and every run of up to max_span consecutive ayat scored by CTC against the log-probs, the best k returned: the
+ * exact, retrieval-free answer to "which verse is this audio" -- no greedy transcript, no text matching, no candidate cap.
+ * (The reference's brute-force route, experiments/fastconformer-nbest-bruteforce/run.py over
+ * experiments/ctc-alignment/ctc_scorer.py, which a CPU limits to 10 surahs; here the whole table is the default.)
+ *   a key       (v, sp): global verse index v in 0 .. n_verses - 1, span sp in 1 .. max_span, 1 <= max_span <= 6.  Its target
+ *               is the token sequence of key v * 6 + sp - 1 of the tables' token table (what the CTC rerank scores), L its
+ *               length.
+ *   feasible    for a row of T frames: L > 0 (the table leaves spans that cross a surah's end, and over-long ones, empty),
+ *               2 L + 1 <= T (the reference's gate, ctc_scorer.py:48), and the surah of v selected by the row's surah mask
+ *               (bit s - 1 of the 128-bit mask selects surah s; no mask = every surah).  The engine holds at most 766 frames,
+ *               so L never exceeds 382.
+ *   loss        loss(v, sp) = the float32 negative log-likelihood that qv_debug_ctc_loss returns for that target on the row's
+ *               log-probs, bit for bit: the same per-state arithmetic.  One alpha recursion runs per start verse and maximal
+ *               run of spans in which each span's ids are a prefix of the next one's, over the longest feasible one; the
+ *               shorter ones are read out of its last row (alpha of the states 0 .. 2 P does not depend on what follows the
+ *               first P tokens, so sharing changes no bit).
+ *   score       norm = loss / L in float32; final = -(double)norm - span_penalty * (sp - 1) in double, each operation rounded
+ *               once.  span_penalty = 0.0 gives the order of the reference's brute force (loss / L ascending).
+ *   ranking     the feasible keys by final descending, ties to the smaller v, then the smaller sp (repeated verses have
+ *               identical targets: exact ties are real).  The first k are returned, 1 <= k <= QV_SCAN_MAX.
+ * Rows t >= t_host[b] are never read; valid frames hold finite values.  A row of t_host[b] = 0, or without a feasible key,
+ * returns n_entries = 0.  Cost: one state update per frame and state of every recursion -- qv_scan_stats counts them (69 M
+ * for T = 126, 595 M for T = 376 on the whole table); timings: DESIGN.md, "exhaustive CTC scan". */
+#define QV_SCAN_MAX 32
+typedef struct {
+    int32_t start_verse, span;      /* the key: global verse index, number of ayat */
+    int32_t surah, ayah, ayah_end;  /* ... as a reference; ayah_end = ayah + span - 1 */
+    int32_t n_tokens;               /* L */
+    float loss, norm;
+    double final_score;
+} qv_scan_entry;
+typedef struct { int32_t n_entries, n_feasible, n_recursions, t_frames; } qv_scan_info;
+
+/* What a row of t_frames frames costs, from a tables file: host only, no engine, no GPU.  surah_mask4: four 32-bit words, NULL =
+ * every surah.  n_feasible: feasible keys; n_recursions: alpha recursions that score them; state_steps: the sum over the
+ * recursions of (2 L + 1) * t_frames.  Output pointers may be NULL.  QV_ERR_ARG for a null path, t_frames outside 0..768 (two
+ * frames above the largest engine's capacity), a bad span or a mask of all zeros; QV_ERR_IO for a file the reader refuses. */
+int qv_scan_stats(const char *tables_path, int32_t t_frames, int32_t max_span, const uint32_t *surah_mask4, int32_t *n_feasible,
+                  int32_t *n_recursions, int64_t *state_steps);
+/* The scan on the caller's log-probs f32[batch, t_max, 1025]; works on an engine without a model.  SYNCHRONOUS on `stream`.
+ * surah_mask_host: u32[batch][4] or NULL.  info_host[batch]; entries_host[batch][k], entries past n_entries zeroed.
+ * loss_out_dev (may be NULL): the caller's device f32[batch][n_verses * 6]; receives every scored key's loss at v * 6 + sp - 1
+ * and +inf everywhere else (empty, infeasible, masked out, sp > max_span).  One record per row comes back in one copy; the
+ * workspace (plans, records, 12 bytes per row and key) belongs to the current execution context and is allocated by the first
+ * call that uses it.  Null pointers, batch < 1, t_max < 1, max_span / k out of range, a t_host[b] outside 0..t_max, a row mask
+ * of all zeros: QV_ERR_ARG; batch above max_batch or t_max above the engine's frame capacity: QV_ERR_CAPACITY, before anything
+ * is launched. */
+int qv_scan_logprobs(qv_engine *e, const float *logprobs_dev, const int32_t *t_host, int32_t batch, int32_t t_max,
+                     int32_t max_span, double span_penalty, int32_t k, const uint32_t *surah_mask_host,
+                     qv_scan_info *info_host, qv_scan_entry *entries_host, float *loss_out_dev, void *stream);
+/* the forward (as qv_beam_batch runs it, with the same contract: waits for batches in flight, forgets the workspace's
+ * earlier batch, QV_ERR_NO_MODEL without a model) into the current context's log-prob workspace, then the same kernels;
+ * t_max = qv_frames_for_samples(longest row). */
+int qv_scan_batch(qv_engine *e, const float *audio_dev, const int64_t *lengths_host, int32_t batch, int64_t n_max,
+                  int32_t max_span, double span_penalty, int32_t k, const uint32_t *surah_mask_host,
+                  qv_scan_info *info_host, qv_scan_entry *entries_host, float *loss_out_dev, void *stream);
+/* with qv_profile_stages on: milliseconds the last scan spent in the scoring kernel and in the selection kernel */
+int qv_scan_kernel_times(qv_engine *e, float *ms2_host);
+
 /* Device pointer of the packed (surah, ayah, ayah_end, float-bits(score)) i32[B,4] rows of the
  * last async call -- the payload of the per-batch RCCL all-gather. */
 const int32_t *qv_packed_results_dev(qv_engine *e);

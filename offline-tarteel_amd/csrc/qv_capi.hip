@@ -5,6 +5,7 @@
 #include "qv_layers.h"
 #include "qv_long_plan.h"
 #include "qv_rows.h"
+#include "qv_scan_plan.h"
 #include "qv_tables_host.h"
 #include "qv_trie_host.h"
 
@@ -408,6 +409,7 @@ extern "C" void qv_destroy(qv_engine *e) {
     qv_long_free(e->long_ws);
     qv_align_long_free(e->align_long_ws);
     qv_beam_free(e);
+    qv_scan_free(e);
     for (QvCtx &c : e->ctx) {
         if (c.t_host_scratch) (void)hipHostFree(c.t_host_scratch);
         for (QvMirror &m : c.mirrors) qv_mirror_free(m);
@@ -1072,6 +1074,95 @@ extern "C" int qv_beam_batch(qv_engine *eng, const float *audio_dev, const int64
     if (rc) return rc;
     return qv_beam_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, max_span, beam, k, info_host, entries_host, ids_host, pitch,
                         (hipStream_t)stream);
+}
+
+// ---- exhaustive CTC scan (qv_scan.hip, qv_scan_plan.h) --------------------------------------------------------------
+extern "C" int qv_scan_stats(const char *tables_path, int32_t t_frames, int32_t max_span, const uint32_t *surah_mask4, int32_t *n_feasible,
+                             int32_t *n_recursions, int64_t *state_steps) {
+    if (!tables_path || t_frames < 0 || t_frames > 2 * QV_SCAN_MAX_L + 2 || max_span < 1 || max_span > QV_SCAN_MAX_SPAN || qv_scan_mask_empty(surah_mask4)) {
+        qv_set_error(nullptr, "qv_scan_stats: null path, t_frames outside 0..768, max_span outside 1..6 or a mask that selects nothing");
+        return QV_ERR_ARG;
+    }
+    std::ifstream f(tables_path, std::ios::binary | std::ios::ate);
+    if (!f) { qv_set_error(nullptr, std::string("cannot open tables file: ") + tables_path); return QV_ERR_IO; }
+    const std::streamsize sz = f.tellg();
+    f.seekg(0);
+    std::vector<uint8_t> file(sz > 0 ? (size_t)sz : 0);
+    if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();   // refused below: bad magic
+    HostTables h;
+    std::string err;
+    if (int rc = qv_build_host_tables(file.data(), file.size(), h, err)) { qv_set_error(nullptr, err); return rc; }
+    QvScanView v;
+    v.n_verses = h.n_verses;
+    v.tok_off = h.tok_off.p; v.n_tok_off = h.tok_off.n;
+    v.pfx = h.tok_pfx.data(); v.n_pfx = h.tok_pfx.size();
+    v.surah = h.h_surah.data(); v.n_surah = h.h_surah.size();
+    QvScanPlan p;
+    int rc = qv_scan_view_check(v, err);
+    if (!rc) rc = qv_scan_plan_make(v, t_frames, max_span, surah_mask4, p, err);
+    if (rc) { qv_set_error(nullptr, err); return rc == QV_SCAN_BAD_ARG ? QV_ERR_ARG : QV_ERR_IO; }
+    if (n_feasible) *n_feasible = p.n_feasible;
+    if (n_recursions) *n_recursions = (int32_t)p.rec.size();
+    if (state_steps) *state_steps = p.state_steps;
+    return QV_OK;
+}
+
+// the argument rules the two scan entry points share (everything but the log-probs and their frame counts)
+static int scan_args(qv_engine *eng, const char *who, int32_t batch, int32_t max_span, int32_t k, const uint32_t *mask_host,
+                     const void *info_host, const void *entries_host) {
+    bool bad = !info_host || !entries_host || batch < 1 || max_span < 1 || max_span > QV_SCAN_MAX_SPAN || k < 1 || k > QV_SCAN_MAX;
+    for (int b = 0; !bad && mask_host && b < batch; ++b) bad = qv_scan_mask_empty(mask_host + (size_t)b * 4);
+    if (bad) {
+        qv_set_error(eng, std::string(who) + ": null argument, empty batch, max_span outside 1..6, k outside 1..QV_SCAN_MAX or a surah mask that selects nothing");
+        return QV_ERR_ARG;
+    }
+    return QV_OK;
+}
+
+extern "C" int qv_scan_logprobs(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch, int32_t t_max, int32_t max_span,
+                                double span_penalty, int32_t k, const uint32_t *surah_mask_host, qv_scan_info *info_host,
+                                qv_scan_entry *entries_host, float *loss_out_dev, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!lp || !t_host || t_max < 1) { qv_set_error(eng, "qv_scan_logprobs: null argument or t_max < 1"); return QV_ERR_ARG; }
+    QV_TRY(scan_args(eng, "qv_scan_logprobs", batch, max_span, k, surah_mask_host, info_host, entries_host));
+    QV_ORDERED(eng, stream);
+    return qv_scan_rows(eng, eng->ctx[eng->cur_ctx], lp, t_host, batch, t_max, max_span, span_penalty, k, surah_mask_host, info_host,
+                        entries_host, loss_out_dev, (hipStream_t)stream);
+}
+
+extern "C" int qv_scan_batch(qv_engine *eng, const float *audio_dev, const int64_t *lengths_host, int32_t batch, int64_t n_max,
+                             int32_t max_span, double span_penalty, int32_t k, const uint32_t *surah_mask_host, qv_scan_info *info_host,
+                             qv_scan_entry *entries_host, float *loss_out_dev, void *stream) {
+    QV_SERIALISE(eng);
+    if (!eng) return QV_ERR_ARG;
+    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    if (!audio_dev || !lengths_host || batch < 1) { qv_set_error(eng, "qv_scan_batch: null argument or empty batch"); return QV_ERR_ARG; }
+    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "qv_scan_batch: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    int64_t lmax = 0;
+    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
+    const int t_max = qv_frames_for_samples(lmax);
+    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "qv_scan_batch: audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    if (t_max < 1) { qv_set_error(eng, "qv_scan_batch: no frames"); return QV_ERR_ARG; }
+    QV_TRY(scan_args(eng, "qv_scan_batch", batch, max_span, k, surah_mask_host, info_host, entries_host));
+    QV_ORDERED(eng, stream);
+    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
+    QV_TRY(quiesce_contexts(eng));
+    QvCtx &c = eng->ctx[eng->cur_ctx];
+    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
+    std::vector<int32_t> t_out(batch);
+    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max, t_out.data(),
+                              (hipStream_t)stream, /*zero_pad_rows=*/false);
+    if (rc) return rc;
+    return qv_scan_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, max_span, span_penalty, k, surah_mask_host, info_host,
+                        entries_host, loss_out_dev, (hipStream_t)stream);
+}
+
+extern "C" int qv_scan_kernel_times(qv_engine *eng, float *ms2_host) {
+    QV_SERIALISE(eng);
+    if (!eng || !ms2_host) return QV_ERR_ARG;
+    if (!eng->profile_stages || qv_scan_times(eng, ms2_host)) { qv_set_error(eng, "qv_scan_kernel_times: no profiled scan (qv_profile_stages first)"); return QV_ERR_ARG; }
+    return QV_OK;
 }
 
 // ---- recordings of any length (qv_long.hip, qv_long_plan.h) ---------------------------------------------------------

@@ -287,6 +287,16 @@ int qv_beam_node_tokens(qv_engine *eng, int max_span, int node, int32_t *ids_out
 int qv_beam_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max, int max_span, int W, int k,
                  qv_beam_info *info_host, qv_beam_entry *entries_host, int32_t *ids_host, int pitch, hipStream_t stream);
 
+// exhaustive CTC scan (qv_scan.hip; the launch plan: qv_scan_plan.h).  One record per row -- qv_scan_info, then QV_SCAN_MAX
+// entries -- comes back in ONE copy into the pinned mirror (QvCtx::scan); the host copies of the table parts the plans are
+// made from belong to the engine (QvScanState, nullptr until a call needs it).
+struct QvScanState;
+void qv_scan_free(qv_engine *eng);
+int qv_scan_times(qv_engine *eng, float *ms2);   // qv_profile_stages: the last call's time in k_ctc_scan and k_scan_select
+int qv_scan_rows(qv_engine *eng, QvCtx &c, const float *lp, const int32_t *t_host, int batch, int t_max, int max_span, double penalty,
+                 int k, const uint32_t *mask_host, qv_scan_info *info_host, qv_scan_entry *entries_host, float *loss_out_dev,
+                 hipStream_t stream);
+
 // recordings of any length (qv_long.hip; the cutting rule: qv_long_plan.h).  One workspace per engine, allocated or grown by
 // the first call that needs it and freed by qv_destroy: the mirror's device buffer holds the plan tables (tab_bytes,
 // rec_bytes), the records (out_bytes), then fid (fid_bytes) and m; its pinned buffer mirrors tables and records; `batch` is
@@ -453,6 +463,8 @@ struct QvCtx {
     QvRowWs transcribe = {};
     // verse-constrained beam search (qv_beam_decode, qv_beam_batch): independent of the batch state as well
     QvRowWs beam = {};
+    // exhaustive CTC scan (qv_scan_logprobs, qv_scan_batch): independent of the batch state too (layout: qv_scan_rows)
+    QvMirror scan = {};
 };
 
 struct qv_engine {
@@ -487,6 +499,7 @@ struct qv_engine {
     QvLongWs long_ws = {};
     QvAlignLongWs align_long_ws = {};
     QvBeamState *beam = nullptr;   // the trie of the beam search (qv_beam.hip), built by the first call that asks for it
+    QvScanState *scan = nullptr;   // the scan's host copies of the token table's offsets and prefix flags (qv_scan.hip)
     bool profile_stages;
     // measurement hook (qv_profile_inject_logprobs): caller-owned log-probs the post-logits stages of
     // qv_predict_batch_async() read INSTEAD of the forward's own output (the forward still runs in full)

@@ -198,6 +198,50 @@ def trie_stats(max_span: int = 3, tables_path: str | None = None) -> dict:
     return dict(zip(("nodes", "ends", "max_depth", "max_children"), (int(v.value) for v in out)))
 
 
+SCAN_MAX = 32        # include/qverse.h: QV_SCAN_MAX
+
+
+class QvScanEntry(C.Structure):
+    """include/qverse.h: qv_scan_entry"""
+    _fields_ = [("start_verse", C.c_int32), ("span", C.c_int32), ("surah", C.c_int32), ("ayah", C.c_int32), ("ayah_end", C.c_int32),
+                ("n_tokens", C.c_int32), ("loss", C.c_float), ("norm", C.c_float), ("final_score", C.c_double)]
+
+
+SCAN_ENTRY_DTYPE = np.dtype([("start_verse", "<i4"), ("span", "<i4"), ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"),
+                             ("n_tokens", "<i4"), ("loss", "<f4"), ("norm", "<f4"), ("final_score", "<f8")])
+SCAN_INFO_DTYPE = np.dtype([("n_entries", "<i4"), ("n_feasible", "<i4"), ("n_recursions", "<i4"), ("t_frames", "<i4")])
+assert SCAN_ENTRY_DTYPE.itemsize == C.sizeof(QvScanEntry) == 40 and SCAN_INFO_DTYPE.itemsize == 16
+
+
+def surah_mask(surahs) -> np.ndarray | None:
+    """the 128-bit surah mask of the scan as uint32[4]: bit s - 1 selects surah s; None = every surah"""
+    if surahs is None:
+        return None
+    m = np.zeros(4, np.uint32)
+    for s in surahs:
+        s = int(s)
+        if not 1 <= s <= 128:
+            raise ValueError(f"surah {s} outside 1..128")
+        m[(s - 1) >> 5] |= np.uint32(1 << ((s - 1) & 31))
+    return m
+
+
+def scan_stats(t_frames: int, max_span: int = 6, surahs=None, tables_path: str | None = None) -> dict:
+    """qv_scan_stats: {"n_feasible", "n_recursions", "state_steps"} of the exhaustive CTC scan for a row of t_frames frames,
+    from the tables file alone -- host only, no engine, no GPU."""
+    lib = load_library()
+    nf, nr, ss = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    m = surah_mask(surahs)
+    rc = lib.qv_scan_stats(str(tables_path or TABLES_PATH).encode(), int(t_frames), int(max_span),
+                           None if m is None else m.ctypes.data_as(C.c_void_p), C.byref(nf), C.byref(nr), C.byref(ss))
+    if rc != 0:
+        msg = lib.qv_last_error(None).decode()
+        if rc == 2:
+            raise FileNotFoundError(msg)
+        raise QvError(f"qv_scan_stats failed ({rc}): {msg}")
+    return {"n_feasible": int(nf.value), "n_recursions": int(nr.value), "state_steps": int(ss.value)}
+
+
 RESULT_DTYPE = np.dtype([
     ("surah", "<i4"), ("ayah", "<i4"), ("ayah_end", "<i4"), ("source", "<i4"),
     ("score", "<f8"), ("base_score", "<f8"), ("ctc_norm_loss", "<f4"),
@@ -271,6 +315,10 @@ def load_library(path: Path | str | None = None) -> C.CDLL:
     lib.qv_trie_node_tokens.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.qv_beam_decode.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]
     lib.qv_beam_batch.argtypes = [vp, vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, i32, vp]
+    lib.qv_scan_stats.argtypes = [C.c_char_p, i32, i32, vp, vp, vp, vp]
+    lib.qv_scan_logprobs.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, i32, vp, vp, vp, vp, vp]
+    lib.qv_scan_batch.argtypes = [vp, vp, vp, i32, i64, i32, C.c_double, i32, vp, vp, vp, vp, vp]
+    lib.qv_scan_kernel_times.argtypes = [vp, vp]
     lib.qv_tracker_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     lib.qv_match_verse.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.qv_debug_retrieve.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
@@ -1157,6 +1205,88 @@ class Engine:
                                     p(ids), pitch, self._stream())
         self._check(rc, "qv_beam_batch")
         return self._beam_rows(info, ent, ids, max_span)
+
+    # ------------------------------------------------ exhaustive CTC scan -----
+    def _scan_masks(self, surahs, B: int) -> np.ndarray | None:
+        """surahs: None (every surah), an iterable of surah numbers for all rows, or one such iterable (or None) per row
+        -> uint32 [B, 4] or None"""
+        if surahs is None:
+            return None
+        surahs = list(surahs)
+        per_row = len(surahs) == B and all(s is None or not isinstance(s, (int, np.integer)) for s in surahs)
+        rows = surahs if per_row else [surahs] * B
+        out = np.empty((B, 4), np.uint32)
+        for b, s in enumerate(rows):
+            m = surah_mask(s)
+            out[b] = 0xFFFFFFFF if m is None else m
+        return np.ascontiguousarray(out)
+
+    def _scan_rows(self, info, ent, losses) -> list[dict]:
+        out = []
+        for b in range(len(info)):
+            cands = [dict(zip(SCAN_ENTRY_DTYPE.names, e)) for e in ent[b, : int(info[b]["n_entries"])].tolist()]
+            row = {"t_frames": int(info[b]["t_frames"]), "n_feasible": int(info[b]["n_feasible"]),
+                   "n_recursions": int(info[b]["n_recursions"]), "candidates": cands}
+            if losses is not None:
+                row["losses"] = losses[b]
+            out.append(row)
+        return out
+
+    def scan_raw(self, log_probs, t_frames, k: int = 5, max_span: int = 6, span_penalty: float | None = None, surahs=None,
+                 return_losses: bool = False):
+        """qv_scan_logprobs as arrays: (info [B] of SCAN_INFO_DTYPE, entries [B, k] of SCAN_ENTRY_DTYPE, losses -- a float32
+        cuda tensor [B, n_verses * 6] with +inf at every key that was not scored, or None)."""
+        torch = self.torch
+        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        B, t_max, V = log_probs.shape
+        assert V == 1025 and len(t_frames) == B
+        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        info = np.zeros(B, dtype=SCAN_INFO_DTYPE)
+        ent = np.zeros((B, max(int(k), 1)), dtype=SCAN_ENTRY_DTYPE)
+        mask = self._scan_masks(surahs, B)
+        losses = torch.empty((B, self.tables.n_verses * 6), dtype=torch.float32, device=log_probs.device) if return_losses else None
+        pen = float(self.cfg.span_penalty if span_penalty is None else span_penalty)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_scan_logprobs(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, int(max_span), pen, int(k), p(mask),
+                                       p(info), p(ent), C.c_void_p(losses.data_ptr()) if return_losses else None, self._stream())
+        self._check(rc, "qv_scan_logprobs")
+        return info, ent, losses
+
+    def scan_logprobs(self, log_probs, t_frames, k: int = 5, max_span: int = 6, span_penalty: float | None = None, surahs=None,
+                      return_losses: bool = False) -> list[dict]:
+        """Exhaustive CTC scan (qv_scan_logprobs; definition in include/qverse.h) of float32 cuda log-probs [B, t_max, 1025]
+        with t_frames[b] valid frames: every verse and every run of up to max_span ayat whose 2 L + 1 states fit the frames
+        is CTC-scored, the best k by -loss / L - span_penalty * (span - 1) come back.  span_penalty None = the engine's
+        CTC_DIRECT_SPAN_PENALTY; surahs: None, surah numbers for all rows, or one list (or None) per row.  Per row
+        {"t_frames", "n_feasible", "n_recursions", "candidates": [{"start_verse", "span", "surah", "ayah", "ayah_end",
+        "n_tokens", "loss", "norm", "final_score"}]}, and with return_losses "losses": the row of the float32 cuda tensor
+        [B, n_verses * 6] that holds every scored key's loss at verse * 6 + span - 1 and +inf elsewhere."""
+        return self._scan_rows(*self.scan_raw(log_probs, t_frames, k, max_span, span_penalty, surahs, return_losses))
+
+    def scan_batch(self, audio, lengths, k: int = 5, max_span: int = 6, span_penalty: float | None = None, surahs=None,
+                   return_losses: bool = False) -> list[dict]:
+        """scan_logprobs behind the forward (qv_scan_batch): audio float32 cuda [B, N], zero padded"""
+        torch = self.torch
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
+        B, N = audio.shape
+        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        assert len(ln) == B and ln.max() <= N
+        info = np.zeros(B, dtype=SCAN_INFO_DTYPE)
+        ent = np.zeros((B, max(int(k), 1)), dtype=SCAN_ENTRY_DTYPE)
+        mask = self._scan_masks(surahs, B)
+        losses = torch.empty((B, self.tables.n_verses * 6), dtype=torch.float32, device=audio.device) if return_losses else None
+        pen = float(self.cfg.span_penalty if span_penalty is None else span_penalty)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = self.lib.qv_scan_batch(self.h, C.c_void_p(audio.data_ptr()), p(ln), B, N, int(max_span), pen, int(k), p(mask), p(info),
+                                    p(ent), C.c_void_p(losses.data_ptr()) if return_losses else None, self._stream())
+        self._check(rc, "qv_scan_batch")
+        return self._scan_rows(info, ent, losses)
+
+    def scan_kernel_times(self) -> dict:
+        """with profile_stages(True): seconds the last scan spent in its two kernels (qv_scan_kernel_times)"""
+        ms = np.zeros(2, np.float32)
+        self._check(self.lib.qv_scan_kernel_times(self.h, ms.ctypes.data_as(C.c_void_p)), "qv_scan_kernel_times")
+        return {"score": float(ms[0]) * 1e-3, "select": float(ms[1]) * 1e-3}
 
     # ------------------------------------------------ recordings of any length -----
     def _long_args(self, window_s, margin_s) -> tuple[int, int]:

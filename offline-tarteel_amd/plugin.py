@@ -157,6 +157,46 @@ def _trie_fallback(eng, out: list[dict], raw: list[dict], beam_rows) -> list[dic
     return out
 
 
+def scan_fallback_enabled() -> bool:
+    """QVERSE_SCAN_FALLBACK=1 (off by default): a row predict() / predict_batch() would return without a prediction takes the
+    first entry of the exhaustive CTC scan (Engine.scan_batch).  With QVERSE_TRIE_FALLBACK set as well the scan runs first and
+    the rows it leaves empty go to the trie route.  Unset, every output is what it was."""
+    return os.getenv("QVERSE_SCAN_FALLBACK", "") not in ("", "0", "false", "False")
+
+
+def _scan_candidates(cands: list[dict]) -> list[dict]:
+    """scan entries as "candidates": score = round(exp(-loss / L), 4), the reference's ctc_confidence; a single verse's
+    ayah_end is its ayah, as everywhere in the plugin"""
+    import math
+
+    return [{"surah": e["surah"], "ayah": e["ayah"], "ayah_end": e["ayah_end"], "score": round(math.exp(-e["norm"]), 4)} for e in cands]
+
+
+def _scan_fallback(eng, out: list[dict], raw: list[dict], scan_rows) -> tuple[list[dict], list[dict]]:
+    """scan_rows(indices) -> Engine.scan_batch rows of those clips.  A row without a prediction becomes the scan's first entry:
+    "source": "scan".  Returns (out, raw) with the filled rows marked in a copy of raw, so a later fallback skips them."""
+    missing = [i for i, r in enumerate(raw) if not r["surah"]]
+    if not missing:
+        return out, raw
+    raw = list(raw)
+    for i, row in zip(missing, scan_rows(missing)):
+        cands = _scan_candidates(row["candidates"])
+        if cands:
+            extra = {k: v for k, v in out[i].items() if k in ("words", "candidates", "correction")}
+            out[i] = {**cands[0], "transcript": out[i].get("transcript", ""), "source": "scan", **extra}
+            raw[i] = {**raw[i], "surah": cands[0]["surah"]}
+    return out, raw
+
+
+def _fallbacks(eng, part: list[dict], raw: list[dict], rows_of) -> list[dict]:
+    """the opt-in routes for rows without a prediction, the scan before the trie; rows_of(indices) -> (audio rows, lengths)"""
+    if scan_fallback_enabled():
+        part, raw = _scan_fallback(eng, part, raw, lambda idx: eng.scan_batch(*rows_of(idx), k=1))
+    if trie_fallback_enabled():
+        part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(*rows_of(idx)))
+    return part
+
+
 def predict_arrays(arrays, round_score: bool = True, words: bool = False, candidates: int | None = None,
                    corrections: bool = False, prefix: bool = False) -> list[dict]:
     """audio arrays (float32, 16 kHz) -> predict()-shaped dicts, one engine call per <= MAX_BATCH.
@@ -176,8 +216,7 @@ def predict_arrays(arrays, round_score: bool = True, words: bool = False, candid
         raw = eng.predict_batch(dev, lens, align=words, nbest=candidates, correct=corrections, correct_prefix=prefix)
         _last_raw[:] = raw
         part = _finish(eng, raw, round_score, words, candidates, corrections)
-        if trie_fallback_enabled():
-            part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(dev[idx].contiguous(), [lens[i] for i in idx]))
+        part = _fallbacks(eng, part, raw, lambda idx: (dev[idx].contiguous(), [lens[i] for i in idx]))
         out.extend(part)
     return out
 
@@ -193,8 +232,7 @@ def predict_device(dev, lens, round_score: bool = True, words: bool = False, can
         raw = eng.predict_batch(rows, chunk, align=words, nbest=candidates, correct=corrections, correct_prefix=prefix)
         _last_raw[:] = raw
         part = _finish(eng, raw, round_score, words, candidates, corrections)
-        if trie_fallback_enabled():
-            part = _trie_fallback(eng, part, raw, lambda idx: eng.beam_batch(rows[idx].contiguous(), [chunk[i] for i in idx]))
+        part = _fallbacks(eng, part, raw, lambda idx, rows=rows, chunk=chunk: (rows[idx].contiguous(), [chunk[i] for i in idx]))
         out.extend(part)
     return out
 
@@ -245,6 +283,24 @@ def predict_constrained(audio_path: str, beam: int = 8, k: int = 5) -> dict:
     audio = load_audio(audio_path)
     dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
     return eng.beam_batch(dev, [len(audio)], beam=beam, k=k)[0]
+
+
+def predict_exhaustive(audio_path: str, k: int = 5, surahs=None) -> dict:
+    """The exhaustive route on its own (the reference's brute force, experiments/fastconformer-nbest-bruteforce/run.py, without
+    its 10-surah limit): every verse and every span of up to six ayat -- of `surahs`, or of the whole Quran -- CTC-scored
+    against the clip, no transcript, no text matching.  {"surah", "ayah", "ayah_end", "score", "source": "scan",
+    "candidates": [up to k of {"surah", "ayah", "ayah_end", "score"}, best first]}; score = round(exp(-loss / L), 4), the
+    reference's ctc_confidence; the ranking uses the engine's CTC_DIRECT_SPAN_PENALTY.  Empty (surah 0) when the clip has
+    fewer frames than any verse's 2 L + 1 states."""
+    import torch
+
+    eng = _ensure_engine()
+    audio = load_audio(audio_path)
+    dev = torch.from_numpy(audio[None, :]).cuda(eng.device)
+    cands = _scan_candidates(eng.scan_batch(dev, [len(audio)], k=k, surahs=surahs)[0]["candidates"])
+    if not cands:
+        return {"surah": 0, "ayah": 0, "ayah_end": None, "score": 0.0, "source": "scan", "candidates": []}
+    return {**cands[0], "source": "scan", "candidates": cands}
 
 
 def predict_words(audio_path: str) -> dict:
