@@ -1,5 +1,5 @@
 """Reference-side helpers for the length tests and the per-layer tap tests of the acoustic forward
-(tests/test_gpu_forward_lengths.py, tests/test_gpu_layer_taps.py, tests/test_forward_ref_host.py).  Everything here runs on the CPU with oracle/fastconformer_ref.py alone.
+(tests/test_gpu_forward_lengths.py, tests/test_gpu_layer_taps.py, tests/test_gpu_ort_layers.py, tests/test_forward_ref_host.py).  Everything here runs on the CPU with oracle/fastconformer_ref.py alone.
 
   * the twin (`F16Ops`): the fp32 restatement with the ONE rounding the device design chooses -- float16 operands of every
     Linear / Conv, float32 accumulation and bias.  Its distance `e` from the fp32 restatement is the reference-side floor
@@ -13,6 +13,9 @@
   * `telltale_weights`, `PLANTS`, `layer_power`, `tap_floor` (second half of the file): the weight set on which one wrong
     tensor in one layer shows at the tap behind that layer, the 46 wrong tensors, what each does to each of the 17 taps,
     and the taps' own float16 floor.
+  * `ort_layer`, `OrtOps`, `ort_twins`, `ort_segments`, `telltale_ort_weights`, `PLANTS2` (last part of the file): precision 2 --
+    one layer of the OrtMixed oracle with the conv module cut out, the twins whose envelope bounds the device there, and the
+    precision-2 plants (tests/test_gpu_ort_layers.py).
   * `POISON_KINDS`, `poisoned`: the non-finite rows (and the harmless "loud" one) of tests/test_gpu_forward_isolation.py and
     tests/test_forward_isolation_host.py.
 """
@@ -25,6 +28,7 @@ import math
 import sys
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -514,3 +518,298 @@ def tap_floor(w, audio, lens, taps=None) -> dict:
 
 def bound_tap(e: float) -> float:
     return max(TAP_BOUND, FLOOR_K * e)
+
+
+# ------------------------------------------------------------------ precision 2: every layer, quantisers cut out -------
+# tests/test_gpu_ort_layers.py holds every layer of a QV_PREC_ORT_MIXED engine to the OrtMixed oracle; what follows is the
+# reference side of it.  A whole layer cannot be compared tightly: the three DynamicQuantizeLinear sites of the conv module
+# are rounding discontinuities, and two evaluations that differ by a float16 rounding flip a few activations across them
+# (0.8e-2 - 2.3e-2 at the layer output, measured oracle against oracle).  So the layer is cut where the device exposes its
+# tensors:  segment A  layer input -> norm_conv's output `lnc` (no quantiser in it);  the exact stages lnc -> GLU -> `dw`
+# (integer arithmetic, 1e-5 of range);  segment C  layer input AND the depthwise stage's output `dw` -> layer output, in which
+# pointwise_conv2 quantises the SAME tensor on both sides and nothing flips.
+
+ORT_CONVS = ("conv.pointwise_conv1.weight", "conv.depthwise_conv.weight", "conv.pointwise_conv2.weight")
+ORT_CONV_GAINS = (1.0, 1.5, 2.25)     # layer l: every ORT_CONVS weight x ORT_CONV_GAINS[l % 3].  See telltale_ort_weights().
+STAGE_REL = 1e-5                      # an exact stage: max |d| <= 1e-5 of the expected tensor's range (test_gpu_ort_mixed.py::_report)
+SUB_OUT = "encoder.pre_encode.out.weight"
+
+
+def telltale_ort_weights(w: dict) -> dict:
+    """telltale_weights(w), and each layer's three conv weights (pointwise_conv1, depthwise_conv, pointwise_conv2) times
+    ORT_CONV_GAINS[l % 3] = 1 / 1.5 / 2.25.  Biases are untouched.
+
+    Why: a precision-2 engine holds ONE int8 scale per conv tensor, max|w| / 127.  On the seeded weights the maxima of
+    neighbouring layers differ by 1 - 2 %, so a launch that rescales the right integers with the neighbour's scale moves the
+    layer output by 0.008 - 0.023 -- a few twin distances only.  With the gains a neighbour's scale (layer (l + 1) % 17; 16 -> 0
+    is 1.5 against 1) is 1.5x larger or 2.25x smaller, never within a third.
+
+    How the gains were chosen (33- and 129-frame clips, 17 layers; test_forward_ref_host.py prints the tables):
+      * no gain below 1: a zero point off by one is an error of s_x s_w sum(w_q) per output channel, proportional to the
+        gain.  It is the weakest plant: in the layers whose gain is 1, pointwise_conv2's lies 5.9 - 18 bounds from the oracle
+        at the layer output (4 are asked); a gain of 0.7 would take the weakest of them to about 4.
+      * 1 / 1.5 / 2.25, the only set measured in full: the twins' envelopes are 1.4e-3 - 4.7e-3 at `lnc` and 0.5e-3 - 4.7e-3 at
+        the layer output (largest bound 7.1e-3, below TAP_BOUND), every plant in front of `lnc` lies >= 40 bounds away there,
+        every plant outside the cut-out chain >= 5.9 bounds at the layer output (the next weakest after the zero point: 17),
+        and every plant inside the chain moves its stage tensor by >= 970 stage bounds.  Larger gains were not needed and not
+        tried: they would let the conv branch outweigh the residual stream that the feed_forward2 plants are measured on."""
+    out = telltale_weights(w)
+    for l in range(R.N_LAYERS):
+        for suffix in ORT_CONVS:
+            out[_p(l) + suffix] = (out[_p(l) + suffix] * ORT_CONV_GAINS[l % 3]).contiguous()
+    return out
+
+
+_INT4_CACHE = {}          # (mode, id(tensor)) -> (tensor, dequantised); the newest _INT4_KEEP entries (two layers' worth and more)
+_INT4_KEEP = 64
+
+
+def _int4_values(wt, mode):
+    key = (mode, id(wt))
+    hit = _INT4_CACHE.get(key)
+    if hit is None or hit[0] is not wt:
+        fn = R.quant_dequant_int4_f32scale if mode == "f32scale" else R.quant_dequant_int4
+        hit = (wt, torch.from_numpy(fn(wt.numpy())))
+        _INT4_CACHE[key] = hit
+        while len(_INT4_CACHE) > _INT4_KEEP:
+            _INT4_CACHE.pop(next(iter(_INT4_CACHE)))
+    return hit[1]
+
+
+class OrtOps(R.OrtMixed):
+    """R.OrtMixed (bit for bit, test_ort_ops_without_options_are_the_oracle) with
+      * prepared weights looked up by TENSOR, not by name, so that a weight dict with one entry misrouted can be evaluated
+        with the same object (OrtMixed caches by name);
+      * the perturbations the precision-2 twins are made of:
+          f16_inputs   every Linear input rounded to float16 -- ort_floor.make_f16_input_ops's rounding;
+          int4         "f32scale": the oracle's (q - 8) * scale, scale in float32;
+                       "f16scale": the block scale kept in float16 (R.quant_dequant_int4; fastconformer_ref.py:270-271);
+                       "device":   the operand the W4A16 GEMM multiplies by, half((q - 8) * half(scale)): dequant8 rounds the
+                                   product once to float16 (csrc/qv_gemm_dequant.h:17).  pre_encode.out is the exception: it is
+                                   dequantised with the float32 scale on the host and stored as float16,
+                                   half((q - 8) * scale) (csrc/qv_model_prep_host.h:291-296);
+          noise        (eps, seed): relative noise on every Linear input -- ort_floor.make_noise_ops's;
+      * `plant` = {conv weight name: (kind, neighbour's weight name)}: what a launch of that conv with a wrong quantisation
+        parameter computes, the integers right --
+          "scale"   the int32 sums rescaled with the NEIGHBOUR tensor's int8 scale;
+          "zp+1"    the activation zero point off by one (255 -> 254);
+          "nozp"    the zero-point correction dropped: sum(x_q w_q) instead of sum((x_q - zp) w_q)."""
+
+    def __init__(self, f16_inputs: bool = False, int4: str = "f32scale", noise=None, plant=None):
+        super().__init__()
+        assert int4 in ("f32scale", "f16scale", "device")
+        self.f16_inputs, self.int4, self.plant = f16_inputs, int4, dict(plant or {})
+        self.eps, self.g = (noise[0], torch.Generator().manual_seed(noise[1])) if noise else (0.0, None)
+
+    def _linear_weight(self, wt, name):
+        if name == SUB_OUT:
+            v = _int4_values(wt, "f32scale")
+            return v.half().float() if self.int4 == "device" else v
+        if not name.endswith(R.INT4_LINEAR_SUFFIXES):
+            return wt
+        if self.int4 == "f32scale":
+            return _int4_values(wt, "f32scale")
+        v = _int4_values(wt, "f16scale")
+        return v.half().float() if self.int4 == "device" else v
+
+    def linear(self, w, name, x, bias_name):
+        if self.g is not None:
+            x = x * (1 + self.eps * (torch.rand(x.shape, generator=self.g) * 2 - 1))
+        if self.f16_inputs:
+            x = x.half().float()
+        return F.linear(x, self._linear_weight(w[name], name), w[bias_name] if bias_name else None)
+
+    def _int8(self, wt):
+        hit = self._w8.get(id(wt))
+        if hit is None or hit[0] is not wt:
+            hit = (wt, R.quantize_weight_int8(wt))
+            self._w8[id(wt)] = hit
+        return hit[1]
+
+    def conv(self, w, name, x, bias_name, fn, **kw):
+        bias = w[bias_name] if bias_name else None
+        wq, sw = self._int8(w[name])
+        kind, other = self.plant.get(name, (None, None))
+        if kind == "scale":
+            sw = self._int8(w[other])[1]
+        outs = []
+        for b in range(x.shape[0]):
+            xq, sx, zp = R.dynamic_quantize_linear(x[b: b + 1])
+            if kind == "zp+1":
+                zp = zp + 1.0 if zp < 255.0 else zp - 1.0
+            elif kind == "nozp":
+                zp = 0.0
+            acc = fn(xq - zp, wq, None, **kw)
+            y = (acc * float(np.float32(sx) * np.float32(sw))).to(torch.float32)
+            outs.append(y + bias.view(1, -1, *([1] * (y.dim() - 2))) if bias is not None else y)
+        return torch.cat(outs, 0)
+
+
+ORT_PLANTS = {f"ort:{s.split('.')[1]}:{what}": (s, kind) for s in ORT_CONVS
+              for what, kind in (("neighbour's int8 scale", "scale"), ("zero point off by one", "zp+1"), ("zero-point correction dropped", "nozp"))}
+PLANTS2 = {**PLANTS, **{k: None for k in ORT_PLANTS}}          # the 46 + 9 plants of precision 2, by name
+# the plants inside the chain the cut removes (pointwise_conv1 -> GLU -> depthwise_conv -> BatchNorm -> Swish): with `dw`
+# handed over they cannot reach the layer output; the exact stage behind them owns them ("glu": lnc -> GLU, "dw": GLU -> dw)
+_CHAIN = {"conv.pointwise_conv1.": "glu", "conv.depthwise_conv.": "dw", "conv.batch_norm.": "dw", "depthwise:": "dw",
+          "batch_norm:": "dw", "ort:pointwise_conv1:": "glu", "ort:depthwise_conv:": "dw"}
+# ... and the tensors in front of norm_conv's output: a plant there shows at `lnc` already
+_FRONT = ("norm_feed_forward1.", "feed_forward1.", "norm_self_att.", "self_attn.", "norm_conv.", "swap:")
+
+
+def plant_stage(key: str):
+    """'glu' / 'dw' for a plant inside the cut-out chain (the stage tensor that shows it), None otherwise"""
+    body = key[len("next:"):] if key.startswith("next:") else key
+    return next((stage for prefix, stage in _CHAIN.items() if body.startswith(prefix)), None)
+
+
+def plant_shows_at_lnc(key: str) -> bool:
+    body = key[len("next:"):] if key.startswith("next:") else key
+    return key != BLIND and body.startswith(_FRONT)
+
+
+def plant_shows_at_out(key: str) -> bool:
+    """every observable plant outside the cut-out chain -- but norm_conv's weight and bias: norm_conv's output feeds the chain and
+    nothing else, so with `dw` handed over they cannot reach the layer output either.  `lnc` is their tensor (segment A)."""
+    body = key[len("next:"):] if key.startswith("next:") else key
+    return key != BLIND and plant_stage(key) is None and not body.startswith("norm_conv.")
+
+
+def planted2(key: str, w: dict, l: int):
+    """(weights, ops) with plant `key` in layer l, for the OrtMixed oracle"""
+    if key in ORT_PLANTS:
+        suffix, kind = ORT_PLANTS[key]
+        return w, OrtOps(plant={_p(l) + suffix: (kind, _p((l + 1) % R.N_LAYERS) + suffix)})
+    return {**w, **PLANTS[key](w, l)}, OrtOps()
+
+
+def ort_layer(w, p, x, ops, dw=None, att16: bool = False) -> dict:
+    """R.conformer_layer restated for ONE unpadded utterance x [1, T, 512] (no padding mask anywhere), with the conv module cut
+    open: returns {"lnc": norm_conv's output, "dw": the depthwise stage's output, "out": the layer's output}, each [1, T, 512],
+    and with `dw` given that tensor takes the place of pointwise_conv1 -> GLU -> depthwise_conv -> BatchNorm -> Swish.
+    Under OrtMixed it gives R.conformer_layer's bits, with nothing given and with its own `dw` given back
+    (test_forward_ref_host.py::test_cut_layer_restates_the_oracle_layer).  att16: the attention as
+    _layer_with_attention_roundings computes it (the attention kernels' float16 roundings)."""
+    assert x.dim() == 3 and x.shape[0] == 1
+    T = x.shape[1]
+
+    def ln(name, t):
+        return F.layer_norm(t, (R.D_MODEL,), w[p + name + ".weight"], w[p + name + ".bias"], 1e-5)
+
+    def ffn(name, t):
+        t = ops.linear(w, p + name + ".linear1.weight", t, p + name + ".linear1.bias")
+        t = t * torch.sigmoid(t)
+        return ops.linear(w, p + name + ".linear2.weight", t, p + name + ".linear2.bias")
+
+    h = _h if att16 else (lambda t: t)
+    r = x
+    r = r + 0.5 * ffn("feed_forward1", ln("norm_feed_forward1", r))
+    y = ln("norm_self_att", r)
+    a = p + "self_attn."
+    q = h(ops.linear(w, a + "linear_q.weight", y, a + "linear_q.bias")).view(1, T, R.N_HEADS, R.D_K)
+    k = h(ops.linear(w, a + "linear_k.weight", y, a + "linear_k.bias")).view(1, T, R.N_HEADS, R.D_K).transpose(1, 2)
+    v = h(ops.linear(w, a + "linear_v.weight", y, a + "linear_v.bias")).view(1, T, R.N_HEADS, R.D_K).transpose(1, 2)
+    pp = h(ops.linear(w, a + "linear_pos.weight", R.rel_pos_emb(T).unsqueeze(0), None)).view(1, -1, R.N_HEADS, R.D_K).transpose(1, 2)
+    qu = h(q + w[a + "pos_bias_u"]).transpose(1, 2)
+    qv = h(q + w[a + "pos_bias_v"]).transpose(1, 2)
+    bd = R.rel_shift(torch.matmul(qv, pp.transpose(-2, -1)))
+    ac = torch.matmul(qu, k.transpose(-2, -1))
+    bd = bd[:, :, :, : ac.size(-1)]
+    scores = (ac + bd) / math.sqrt(R.D_K)
+    if att16:
+        e = torch.exp(scores - scores.max(-1, keepdim=True).values)
+        ctx = torch.matmul(_h(e), v) / e.sum(-1, keepdim=True).clamp_min(1e-30)
+    else:
+        ctx = torch.matmul(torch.softmax(scores, dim=-1), v)
+    ctx = ctx.transpose(1, 2).reshape(1, T, R.D_MODEL)
+    r = r + ops.linear(w, a + "linear_out.weight", ctx, a + "linear_out.bias")
+    y = ln("norm_conv", r).transpose(1, 2)
+    out = {"lnc": y.transpose(1, 2).contiguous()}
+    c = p + "conv."
+    if dw is None:
+        out["glu"] = ort_stage(w, p, "glu", out["lnc"][0], ops).unsqueeze(0)
+        out["dw"] = ort_stage(w, p, "dw", out["glu"][0], ops).unsqueeze(0)
+        dw = out["dw"]
+    else:
+        out["dw"] = dw
+    y = ops.conv(w, c + "pointwise_conv2.weight", dw.transpose(1, 2), c + "pointwise_conv2.bias", F.conv1d).transpose(1, 2)
+    r = r + y
+    r = r + 0.5 * ffn("feed_forward2", ln("norm_feed_forward2", r))
+    out["out"] = ln("norm_out", r)
+    return out
+
+
+def ort_stage(w, p, stage: str, x, ops):
+    """one exact stage of layer `p`'s conv module on x [T, 512] -> [T, 512], as R.conformer_layer computes it for an unpadded
+    utterance: "glu" = pointwise_conv1 + GLU of norm_conv's output, "dw" = depthwise_conv + BatchNorm + Swish of GLU's output"""
+    c = p + "conv."
+    y = x.t().unsqueeze(0)
+    if stage == "glu":
+        y = F.glu(ops.conv(w, c + "pointwise_conv1.weight", y, c + "pointwise_conv1.bias", F.conv1d), dim=1)
+    else:
+        y = ops.conv(w, c + "depthwise_conv.weight", y, c + "depthwise_conv.bias", F.conv1d, padding=(R.CONV_K - 1) // 2, groups=R.D_MODEL)
+        y = F.batch_norm(y, w[c + "batch_norm.running_mean"], w[c + "batch_norm.running_var"], w[c + "batch_norm.weight"],
+                         w[c + "batch_norm.bias"], False, 0.0, 1e-5)
+        y = y * torch.sigmoid(y)
+    return y[0].t().contiguous()
+
+
+def ort_pre_encode(w, c2p, ops):
+    """pre_encode.out and the xscaling on the channels-last conv.6 output c2p [T, 10, 256] of one utterance -> [T, 512]: the
+    encoder's input as R.subsampling + R.forward compute it (NeMo flattens [C][F] as c * 10 + f)"""
+    x = c2p.permute(0, 2, 1).reshape(1, c2p.shape[0], R.SUB_CH * 10)
+    return ops.linear(w, SUB_OUT, x, "encoder.pre_encode.out.bias")[0] * math.sqrt(R.D_MODEL)
+
+
+def ort_twins() -> dict:
+    """name -> (ops, att16): the evaluations whose envelope around the OrtMixed oracle is `e`.  None of them is an error: each
+    is the oracle with roundings a precision-2 engine performs BY DESIGN, or with noise far below any tolerance.
+      f16in              Linear inputs rounded to float16: the f16-operand MFMA GEMM's A operand (LayerNorm, Swish and attention
+                         outputs are stored as float16: csrc/qv_model.hip ffn_half / attention_block write a.ln, a.hbuf, a.att)
+      f16in+f16scale     ... and the int4 block scales kept in float16 (csrc/qv_wpack_host.h::qv_pack_w4)
+      device             ... and the dequantised weight rounded once to the float16 B operand (csrc/qv_gemm_dequant.h:17)
+      device+attention   ... and the attention kernels' own roundings (attention_roundings(), csrc/qv_attention.hip)
+      noise1, noise2     the oracle with 1e-7 relative noise on every Linear input (ort_floor.make_noise_ops)"""
+    return {"f16in": (OrtOps(f16_inputs=True), False),
+            "f16in+f16scale": (OrtOps(f16_inputs=True, int4="f16scale"), False),
+            "device": (OrtOps(f16_inputs=True, int4="device"), False),
+            "device+attention": (OrtOps(f16_inputs=True, int4="device"), True),
+            "noise1": (OrtOps(noise=(1e-7, 1)), False), "noise2": (OrtOps(noise=(1e-7, 2)), False)}
+
+
+def _d(a, b) -> float:
+    return float((a.float() - b.float()).abs().max())
+
+
+@torch.no_grad()
+def ort_segments(w, l: int, x, dw, twins=None, plants=(), against=None) -> dict:
+    """Layer l of the OrtMixed oracle on ONE utterance's layer input x [T, 512] with the depthwise stage's output dw [T, 512]
+    handed over.  {"lnc", "out": the oracle's two tensors [T, 512];  "e_lnc", "e_out": the twins' envelope, max over `twins`
+    (ort_twins()) of max |twin - oracle|, and "rows": the same per twin;  "D": {plant: (distance at lnc, at out) of the planted
+    oracle from the true one};  with against = (lnc, out) of a device, "A": {plant: ...} the planted oracle's distances from
+    those}.  The twins get the same x and dw: `e` is measured on the very input the device is judged on."""
+    p = _p(l)
+    x, dw = x.unsqueeze(0), dw.unsqueeze(0)
+    ref = ort_layer(w, p, x, OrtOps(), dw)
+    out = {"lnc": ref["lnc"][0], "out": ref["out"][0], "rows": {}, "D": {}, "A": {}}
+    for name, (ops, att16) in (twins or {}).items():
+        t = ort_layer(w, p, x, ops, dw, att16)
+        out["rows"][name] = (_d(t["lnc"], ref["lnc"]), _d(t["out"], ref["out"]))
+    if twins:
+        out["e_lnc"] = max(r[0] for r in out["rows"].values())
+        out["e_out"] = max(r[1] for r in out["rows"].values())
+    for key in plants:
+        wp, ops = planted2(key, w, l)
+        bad = ort_layer(wp, p, x, ops, dw)
+        out["D"][key] = (_d(bad["lnc"], ref["lnc"]), _d(bad["out"], ref["out"]))
+        if against is not None:
+            out["A"][key] = (_d(bad["lnc"][0], against[0]), _d(bad["out"][0], against[1]))
+    return out
+
+
+@torch.no_grad()
+def ort_pre_encode_floor(w, c2p) -> dict:
+    """{"ref": the oracle's encoder input [T, 512] from c2p [T, 10, 256], "e", "rows"}: the envelope of the twins that touch a
+    Linear (ort_twins() without the attention one)"""
+    ref = ort_pre_encode(w, c2p, OrtOps())
+    rows = {name: _d(ort_pre_encode(w, c2p, ops), ref) for name, (ops, att16) in ort_twins().items() if not att16}
+    return {"ref": ref, "rows": rows, "e": max(rows.values())}

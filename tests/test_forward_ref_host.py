@@ -232,3 +232,120 @@ def test_sharp_weights_hide_a_wrong_vector_in_layer_0(refs, tell):
     assert hidden
     same = {k: tell["telltale"]["power"]["D"][k][0] for _, k in hidden}
     assert min(same.values()) >= 4.0 * FR.TAP_BOUND, same
+
+
+# ------------------------------------------------------------------ the instrument of tests/test_gpu_ort_layers.py ------
+# Precision 2 (OrtMixed): every layer from the oracle's OWN layer input, the conv module cut out.  Oracle against oracle.
+
+ORT_TAPS = ["sub", "c2p"] + [f"{k}{l}" for l in range(R.N_LAYERS) for k in ("layer", "lnc", "glu", "dw")]
+ORT_OUT_PLANTS = [k for k in FR.PLANTS2 if FR.plant_shows_at_out(k) or FR.plant_shows_at_lnc(k)]
+ORT_CHAIN_PLANTS = [k for k in FR.PLANTS2 if FR.plant_stage(k)]
+
+
+@pytest.fixture(scope="module")
+def ort(refs):
+    """the OrtMixed oracle on the telltale_ort weights, 33- and 129-frame clips, and per layer and clip: the cut layer's
+    bits against R.conformer_layer's, the twins' envelope, every plant's distance"""
+    rows = [FRAMES.index(t) for t in TELL_FRAMES]
+    audio, lens = FR._rows_of(refs["audio"], refs["lens"], rows)
+    w = FR.telltale_ort_weights(refs["plain_w"])
+    taps = FR._Keep(ORT_TAPS)
+    lp, t = R.forward(w, audio, lens, ort=FR.OrtOps(), taps=taps)
+    assert t.tolist() == TELL_FRAMES
+    out = {"w": w, "audio": audio, "lens": lens, "lp": lp, "taps": taps, "cells": {}}
+    for l in range(R.N_LAYERS):
+        for b, n in enumerate(TELL_FRAMES):
+            x = taps["sub"][b, :n] * R.D_MODEL ** 0.5 if l == 0 else taps[f"layer{l - 1}"][b, :n]
+            true = {k: taps[f"{k}{l}"][b, :n] for k in ("layer", "lnc", "glu", "dw")}
+            whole = FR.ort_layer(w, FR._p(l), x.unsqueeze(0), FR.OrtOps())
+            seg = FR.ort_segments(w, l, x, true["dw"], FR.ort_twins(), ORT_OUT_PLANTS)
+            call = R.conformer_layer(w, FR._p(l), x.unsqueeze(0), R.rel_pos_emb(n).unsqueeze(0), torch.zeros(1, n, dtype=torch.bool), R.OrtMixed())
+            seg["restated"] = [FR._d(whole["out"], call), FR._d(whole["out"][0], true["layer"]), FR._d(whole["lnc"][0], true["lnc"]),
+                               FR._d(whole["glu"][0], true["glu"]), FR._d(whole["dw"][0], true["dw"]), FR._d(seg["out"], true["layer"]),
+                               FR._d(seg["lnc"], true["lnc"])]
+            seg["stage"] = {}
+            for key in ORT_CHAIN_PLANTS:
+                stage = FR.plant_stage(key)
+                wp, ops = FR.planted2(key, w, l)
+                bad = FR.ort_stage(wp, FR._p(l), stage, true["lnc" if stage == "glu" else "glu"], ops)
+                seg["stage"][key] = FR._d(bad, true[stage]) / (FR.STAGE_REL * float(true[stage].abs().max()))
+            out["cells"][(l, n)] = seg
+    return out
+
+
+def test_ort_ops_without_options_are_the_oracle(refs, ort):
+    """OrtOps() is R.OrtMixed() bit for bit; its float16-input twin is ort_floor.make_f16_input_ops's, its noise ort_floor.make_noise_ops's"""
+    import ort_floor
+
+    audio, lens = ort["audio"][:1, : ort["lens"][0]].contiguous(), ort["lens"][:1]
+    assert torch.equal(R.forward(ort["w"], ort["audio"], ort["lens"], ort=R.OrtMixed())[0], ort["lp"])
+    for mine, theirs in ((FR.OrtOps(f16_inputs=True), ort_floor.make_f16_input_ops(R)), (FR.OrtOps(noise=(1e-7, 1)), ort_floor.make_noise_ops(R, 1e-7, 1))):
+        assert torch.equal(R.forward(ort["w"], audio, lens, ort=mine)[0], R.forward(ort["w"], audio, lens, ort=theirs)[0])
+
+
+def test_telltale_ort_weights_change_the_three_conv_weights_only(refs):
+    tell_w, ort_w = FR.telltale_weights(refs["plain_w"]), FR.telltale_ort_weights(refs["plain_w"])
+    assert len(set(FR.ORT_CONV_GAINS)) == 3 and min(FR.ORT_CONV_GAINS) >= 1.0
+    for k, t in ort_w.items():
+        if k.startswith("encoder.layers.") and k.endswith(FR.ORT_CONVS):
+            assert torch.equal(t, tell_w[k] * FR.ORT_CONV_GAINS[int(k.split(".")[2]) % 3]), k
+        else:
+            assert torch.equal(t, tell_w[k]), k
+    for l in range(R.N_LAYERS):          # what the gains are for: a neighbour's int8 scale is never within a third
+        for s in FR.ORT_CONVS:
+            a, b = (float(R.quantize_weight_int8(ort_w[FR._p(i) + s])[1]) for i in (l, (l + 1) % R.N_LAYERS))
+            assert max(a, b) / min(a, b) >= 4.0 / 3.0, (l, s, a, b)
+    assert len(FR.ORT_PLANTS) == 9 and len(FR.PLANTS2) == 46 + 9 and len(ORT_CHAIN_PLANTS) == 18
+    assert len([k for k in FR.PLANTS2 if FR.plant_shows_at_out(k)]) == 46 + 9 - 1 - 18 - 2
+
+
+def test_cut_layer_restates_the_oracle_layer(ort):
+    """ort_layer == R.conformer_layer under OrtMixed, bit for bit: called alone, against the oracle's own taps (layer output, lnc,
+    GLU, dw), and with the oracle's dw handed over -- all 17 layers, both clips"""
+    for cell, seg in ort["cells"].items():
+        assert seg["restated"] == [0.0] * 7, (cell, seg["restated"])
+
+
+def test_ort_segment_bounds_stay_below_the_tap_bound(ort):
+    """e per segment, layer and clip (printed), and FLOOR_K e <= TAP_BOUND: the bound asserted on the device is below the
+    project's 1.5e-2 everywhere.  (If a cell breaks this, change the weight set.)"""
+    names = list(FR.ort_twins())
+    for n in TELL_FRAMES:
+        print(f"[ort-ref] T = {n}: e at lnc | at the layer output, x 1e-3, per layer (and which twin sets it)")
+        for l in range(R.N_LAYERS):
+            seg = ort["cells"][(l, n)]
+            who = [max(names, key=lambda k: seg["rows"][k][i]) for i in (0, 1)]
+            print(f"[ort-ref]   layer {l:2d}: {seg['e_lnc'] * 1e3:5.2f} ({who[0]}) | {seg['e_out'] * 1e3:5.2f} ({who[1]})")
+    for cell, seg in ort["cells"].items():
+        for e in (seg["e_lnc"], seg["e_out"]):
+            assert 0.0 < FR.FLOOR_K * e <= FR.TAP_BOUND, (cell, e)
+
+
+def test_every_ort_plant_shows_where_its_check_looks(ort):
+    """The power of test_gpu_ort_layers.py, the ORACLE computing the wrong thing, in all 17 layers on both clips: a plant in front
+    of lnc lies >= 4 bounds (bound = FLOOR_K e of that cell) from the oracle at lnc; every plant outside the cut-out chain (and
+    not norm_conv's, whose only reader is the chain) >= 4 bounds at the layer output with the TRUE dw handed over; a plant inside
+    the chain moves its exact stage's tensor by >= 100 stage bounds (1e-5 of range each)."""
+    at_lnc, at_out, at_stage = [], [], []
+    for (l, n), seg in ort["cells"].items():
+        at_lnc += [(d[0] / (FR.FLOOR_K * seg["e_lnc"]), key, l, n) for key, d in seg["D"].items() if FR.plant_shows_at_lnc(key)]
+        at_out += [(d[1] / (FR.FLOOR_K * seg["e_out"]), key, l, n) for key, d in seg["D"].items() if FR.plant_shows_at_out(key)]
+        at_stage += [(r, key, l, n) for key, r in seg["stage"].items()]
+    assert len(at_out) == 34 * R.N_LAYERS * 2 and len(at_stage) == 18 * R.N_LAYERS * 2 and len(at_lnc) == 23 * R.N_LAYERS * 2
+    for name, rows, least in (("lnc", at_lnc, 4.0), ("layer output", at_out, 4.0), ("stage tensor", at_stage, 100.0)):
+        rows.sort()
+        for r, key, l, n in rows[:3]:
+            print(f"[ort-ref] {name}: {key} in layer {l}, T = {n}: {r:.1f} bounds")
+        low = [(key, l, n, round(r, 2)) for r, key, l, n in rows if r < least]
+        assert not low, (name, low)
+    worst = {k: min(r for r, key, _, _ in at_out if key == k) for k in FR.ORT_PLANTS if FR.plant_shows_at_out(k)}
+    print("[ort-ref] pointwise_conv2's precision-2 plants, fewest bounds at the layer output:", {k: round(v, 1) for k, v in worst.items()})
+
+
+def test_pre_encode_restatement_and_floor(ort):
+    """ort_pre_encode on the oracle's conv.6 output is the oracle's encoder input bit for bit, and its bound is below TAP_BOUND"""
+    for b, n in enumerate(TELL_FRAMES):
+        fl = FR.ort_pre_encode_floor(ort["w"], ort["taps"]["c2p"][b, :n])
+        assert torch.equal(fl["ref"], ort["taps"]["sub"][b, :n] * R.D_MODEL ** 0.5)
+        print(f"[ort-ref] pre_encode.out T = {n}: e {fl['e']:.2e} {fl['rows']}")
+        assert 0.0 < FR.FLOOR_K * fl["e"] <= FR.TAP_BOUND
