@@ -15,7 +15,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <fstream>
 #include <mutex>
 
 static std::string g_create_error;
@@ -62,6 +61,9 @@ static double probe_rounds(int ns) {
 
 // Device-side order between consecutive calls on different caller streams (two host threads, each with its own stream,
 // share the engine's workspace): wait for the previous call's tail on entry, leave a new tail on exit.
+// Placement, one rule: QV_ORDERED stands behind the checks that need no device and before the call's first enqueue, in
+// the entry point's own scope (the tail is recorded when that scope ends).  A call refused by those checks leaves the
+// previous call's tail in place; every call that enqueues waits for it and leaves its own.
 namespace {
 struct QvStreamOrder {
     qv_engine *e;
@@ -192,20 +194,11 @@ extern "C" int32_t qv_frames_for_samples(int64_t n) {
 
 #define QV_TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
-// the tables file: read it, let qv_tables_host.h check it and build the host arrays, upload each under its own name
+// the tables file: let qv_tables_host.h read and check it and build the host arrays, upload each under its own name
 static int load_tables(qv_engine *eng, const char *path) {
-    std::vector<uint8_t> file;
-    {
-        std::ifstream f(path, std::ios::binary | std::ios::ate);
-        if (!f) { qv_set_error(eng, std::string("cannot open tables file: ") + (path ? path : "(null)")); return QV_ERR_IO; }
-        const std::streamsize sz = f.tellg();
-        f.seekg(0);
-        file.resize(sz > 0 ? (size_t)sz : 0);
-        if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();   // refused below: bad magic
-    }
     HostTables h;
     std::string err;
-    if (int rc = qv_build_host_tables(file.data(), file.size(), h, err)) { qv_set_error(eng, err); return rc; }
+    if (int rc = qv_read_host_tables(path, h, err)) { qv_set_error(eng, err); return rc; }
     QvTables &t = eng->tab;
     t.n_verses = h.n_verses; t.n_surah = h.n_surah; t.n_tri = h.n_tri; t.n_text = h.n_text;
     eng->h_surah = std::move(h.h_surah);
@@ -423,12 +416,58 @@ extern "C" void qv_destroy(qv_engine *e) {
     delete e;
 }
 
+// ---- what the entry points that run the forward share ---------------------------------------------------------------
+static int need_model(qv_engine *eng) {
+    if (eng->model) return QV_OK;
+    qv_set_error(eng, "engine created without a model (with_model = 0)");
+    return QV_ERR_NO_MODEL;
+}
+
+// The capacity rules of a batch of audio rows (every context has the same capacities): `batch` against max_batch, the
+// longest row's frames -- *t_max -- against t_cap.  `prefix` opens the messages: "<entry point>: ", or "".
+static int batch_in_capacity(qv_engine *eng, const char *prefix, const int64_t *lengths_host, int batch, int *t_max) {
+    const QvWork &w = eng->ctx[0].work;
+    if (batch > w.max_batch) { qv_set_error(eng, std::string(prefix) + "batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    int64_t lmax = 0;
+    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
+    *t_max = qv_frames_for_samples(lmax);
+    if (*t_max > w.t_cap) { qv_set_error(eng, std::string(prefix) + "audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    return QV_OK;
+}
+
+// Entry points that run on the caller's stream through the workspace of ctx[cur_ctx] (a single text, a forward): with
+// batches in flight, wait until no internal stream is still using a workspace.
+static int quiesce_contexts(qv_engine *eng) {
+    if (eng->n_ctx > 1)
+        for (int k = 0; k < eng->n_ctx; ++k)
+            if (eng->ctx[k].busy) QV_HIP(hipEventSynchronize(eng->ctx[k].done));
+    return QV_OK;
+}
+
+// A forward on the caller's stream writes the current context's log-prob workspace: no batch may be in flight on it, and
+// the batch those log-probs belonged to can no longer be aligned.  Returns that context.
+static int claim_logprobs_ws(qv_engine *eng, QvCtx **c) {
+    QV_TRY(quiesce_contexts(eng));
+    *c = &eng->ctx[eng->cur_ctx];
+    if ((*c)->al_lp == (*c)->logprobs_ws) (*c)->al_lp = nullptr;
+    return QV_OK;
+}
+
+// ... and the forward itself: the rows' log-probs in (*c)->logprobs_ws, their frame counts in t_out
+static int forward_into_ws(qv_engine *eng, const float *audio_dev, const int64_t *lengths_host, int batch, int64_t n_max, int t_max,
+                           hipStream_t stream, QvCtx **c, std::vector<int32_t> &t_out) {
+    QV_TRY(claim_logprobs_ws(eng, c));
+    t_out.resize(batch);
+    return qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, (*c)->logprobs_ws, t_max, t_out.data(),
+                            stream, /*zero_pad_rows=*/false);
+}
+
 extern "C" int qv_forward(qv_engine *eng, const float *audio_dev, const int64_t *lengths_host, int32_t batch,
                           int64_t n_max, float *logprobs_dev, int32_t t_max, int32_t *t_out_host, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    QV_TRY(need_model(eng));
+    QV_ORDERED(eng, stream);
     return qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, logprobs_dev, t_max,
                             t_out_host, (hipStream_t)stream, /*zero_pad_rows=*/true);
 }
@@ -441,8 +480,8 @@ static void align_note(QvCtx &c, const float *lp, int t_max, int batch, hipStrea
 extern "C" int qv_decode_retrieve_rerank_async(qv_engine *eng, const float *lp, const int32_t *t_host, int32_t batch,
                                                int32_t t_max, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng || !lp || !t_host || batch < 1) return QV_ERR_ARG;
+    QV_ORDERED(eng, stream);
     QvCtx &c = eng->ctx[eng->cur_ctx];
     qv_stage_mark(eng, c, 0, (hipStream_t)stream);   // no forward in this call: forward = 0
     qv_stage_mark(eng, c, 1, (hipStream_t)stream);
@@ -514,8 +553,8 @@ static int fetch_results(qv_engine *eng, QvCtx &c, int batch, int t_max, qv_resu
 extern "C" int qv_fetch_results(qv_engine *eng, int32_t batch, int32_t t_max, qv_result *res, int32_t *greedy_host,
                                 void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
+    QV_ORDERED(eng, stream);
     return fetch_results(eng, eng->ctx[eng->cur_ctx], batch, t_max, res, greedy_host, (hipStream_t)stream);
 }
 
@@ -530,15 +569,11 @@ extern "C" int qv_decode_retrieve_rerank(qv_engine *eng, const float *lp, const 
 extern "C" int qv_predict_batch_async(qv_engine *eng, const float *audio_dev, const int64_t *lengths_host,
                                       int32_t batch, int64_t n_max, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
-    // (every context has the same capacities)
-    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
-    int64_t lmax = 0;
-    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
-    int t_max = qv_frames_for_samples(lmax);
-    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    QV_TRY(need_model(eng));
+    int t_max;
+    QV_TRY(batch_in_capacity(eng, "", lengths_host, batch, &t_max));
+    QV_ORDERED(eng, stream);
     std::vector<int32_t> t_out(batch);
     hipStream_t run = (hipStream_t)stream;
     if (eng->n_ctx > 1) {
@@ -598,8 +633,8 @@ static int fir_for(qv_engine *eng, const float *taps, int32_t n_taps, int32_t up
 extern "C" int qv_upfirdn(qv_engine *eng, const float *x_dev, int64_t n_in, const float *taps, int32_t n_taps, int32_t up,
                           int32_t down, int64_t m0, int64_t n_out, float *y_dev, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng || !x_dev || !taps || !y_dev || n_in < 1 || n_taps < 1 || up < 1 || down < 1 || m0 < 0 || n_out < 0) return QV_ERR_ARG;
+    QV_ORDERED(eng, stream);
     const qv_engine::Fir *fir = nullptr;
     QV_TRY(fir_for(eng, taps, n_taps, up, &fir));
     launch_upfirdn(x_dev, n_in, fir->hflip_dev, fir->P, up, down, m0, n_out, y_dev, (hipStream_t)stream);
@@ -626,11 +661,19 @@ static int fir_for(qv_engine *eng, const float *taps, int32_t n_taps, int32_t up
     return QV_OK;
 }
 
+// row table of a resampling call: [QV_RESAMPLE_ROWS] int64 lengths + int32 source rows, one slot of a small ring per call,
+// allocated on first use (the copies into it are issued from pageable memory: the runtime stages them before the entry
+// point returns, so the host vectors may go away)
+static int resample_slot(qv_engine *eng, unsigned char **slot) {
+    if (!eng->resample_tab) QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
+    *slot = eng->resample_tab + (size_t)(eng->resample_at++ % QV_RESAMPLE_SLOTS) * QV_RESAMPLE_ROWS * 12;
+    return QV_OK;
+}
+
 extern "C" int qv_upfirdn_batch(qv_engine *eng, const float *x_dev, int64_t x_pitch, const int32_t *src_rows_host,
                                 const int64_t *n_in_host, int32_t rows, const float *taps, int32_t n_taps, int32_t up, int32_t down,
                                 int64_t m0, float *y_dev, int64_t y_pitch, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng || !x_dev || !n_in_host || !taps || !y_dev || rows < 1 || rows > QV_RESAMPLE_ROWS || n_taps < 1 || up < 1 || down < 1 || m0 < 0 ||
         x_pitch < 1 || y_pitch < 1)
         return QV_ERR_ARG;
@@ -639,12 +682,11 @@ extern "C" int qv_upfirdn_batch(qv_engine *eng, const float *x_dev, int64_t x_pi
         if ((n_in_host[r] * up + down - 1) / down > y_pitch) { qv_set_error(eng, "qv_upfirdn_batch: y_pitch is shorter than a row's output"); return QV_ERR_ARG; }
         if (src_rows_host && src_rows_host[r] < 0) return QV_ERR_ARG;
     }
+    QV_ORDERED(eng, stream);
     const qv_engine::Fir *fir = nullptr;
     QV_TRY(fir_for(eng, taps, n_taps, up, &fir));
-    // row table: [QV_RESAMPLE_ROWS] int64 lengths + int32 source rows, one slot of a small ring per call (the copy is issued
-    // from pageable memory: the runtime stages it before this function returns, so the host vectors may go away)
-    if (!eng->resample_tab) QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
-    unsigned char *slot = eng->resample_tab + (size_t)(eng->resample_at++ % QV_RESAMPLE_SLOTS) * QV_RESAMPLE_ROWS * 12;
+    unsigned char *slot = nullptr;
+    QV_TRY(resample_slot(eng, &slot));
     hipStream_t s = (hipStream_t)stream;
     QV_HIP(hipMemcpyAsync(slot, n_in_host, sizeof(int64_t) * rows, hipMemcpyHostToDevice, s));
     int32_t *src_dev = nullptr;
@@ -660,15 +702,15 @@ extern "C" int qv_upfirdn_batch(qv_engine *eng, const float *x_dev, int64_t x_pi
 extern "C" int qv_mixdown_batch(qv_engine *eng, const float *x_dev, int64_t x_pitch, const int64_t *n_frames_host, int32_t rows,
                                 int32_t channels, float *y_dev, int64_t y_pitch, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng || !x_dev || !n_frames_host || !y_dev || rows < 1 || rows > QV_RESAMPLE_ROWS || channels < 1 || channels > 64) return QV_ERR_ARG;
     int64_t mx = 0;
     for (int r = 0; r < rows; ++r) {
         if (n_frames_host[r] < 0 || n_frames_host[r] * channels > x_pitch || n_frames_host[r] > y_pitch) return QV_ERR_ARG;
         mx = n_frames_host[r] > mx ? n_frames_host[r] : mx;
     }
-    if (!eng->resample_tab) QV_TRY(qv_dev_zeroed(eng, eng->allocs, (size_t)QV_RESAMPLE_SLOTS * QV_RESAMPLE_ROWS * 12, &eng->resample_tab));
-    unsigned char *slot = eng->resample_tab + (size_t)(eng->resample_at++ % QV_RESAMPLE_SLOTS) * QV_RESAMPLE_ROWS * 12;
+    QV_ORDERED(eng, stream);
+    unsigned char *slot = nullptr;
+    QV_TRY(resample_slot(eng, &slot));
     hipStream_t s = (hipStream_t)stream;
     QV_HIP(hipMemcpyAsync(slot, n_frames_host, sizeof(int64_t) * rows, hipMemcpyHostToDevice, s));
     launch_mixdown(x_dev, x_pitch, (const int64_t *)slot, rows, channels, y_dev, y_pitch, mx, s);
@@ -712,9 +754,20 @@ extern "C" int qv_fetch_results_ctx(qv_engine *eng, int32_t k, int32_t batch, in
     if (!eng || k < 0 || k >= eng->n_ctx) return QV_ERR_ARG;
     if (eng->n_ctx == 1) QV_HIP(hipDeviceSynchronize());  // the batch ran on a caller stream we were not given
     // on the context's own stream, so the copy is ordered after its batch
+    // (Not qv_rows.h::qv_stream_behind_batch, here and in qv_debug_transcript_codes: that rule also joins the device when
+    // the batch was decoded on a stream other than the context's own -- qv_decode_retrieve_rerank_async on an engine with
+    // batches in flight -- which these two calls never did.)
     hipStream_t stream = eng->n_ctx > 1 ? eng->ctx[k].stream : nullptr;
     QV_ORDERED(eng, stream);
     return fetch_results(eng, eng->ctx[k], batch, t_max, res, greedy_host, stream);
+}
+
+// How a call on context k's last batch opens: k names a context and `batch` rows fit its workspace.  `rest_ok` and `rule`
+// are the caller's other argument rules and the words for them; one QV_ERR_ARG message covers them and the context.
+static int ctx_batch_args(qv_engine *eng, const char *who, int k, int batch, bool rest_ok, const char *rule) {
+    if (k < 0 || k >= eng->n_ctx || batch < 1 || !rest_ok) { qv_set_error(eng, std::string(who) + ": " + rule); return QV_ERR_ARG; }
+    if (batch > eng->ctx[k].work.max_batch) { qv_set_error(eng, std::string(who) + ": batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    return QV_OK;
 }
 
 // the transcript k_decode left in the workspace (rows of eng->max_q codes: the pitch of the kernel set the engine runs)
@@ -722,12 +775,9 @@ extern "C" int qv_debug_transcript_codes(qv_engine *eng, int32_t k, int32_t batc
                                          int32_t *len_host, int32_t *words_host) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (k < 0 || k >= eng->n_ctx || batch < 1 || !codes_host || !len_host || !words_host || pitch < eng->max_q) {
-        qv_set_error(eng, "qv_debug_transcript_codes: bad context, null argument, empty batch or pitch < qv_max_transcript");
-        return QV_ERR_ARG;
-    }
+    QV_TRY(ctx_batch_args(eng, "qv_debug_transcript_codes", k, batch, codes_host && len_host && words_host && pitch >= eng->max_q,
+                          "bad context, null argument, empty batch or pitch < qv_max_transcript"));
     QvCtx &c = eng->ctx[k];
-    if (batch > c.work.max_batch) { qv_set_error(eng, "qv_debug_transcript_codes: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
     if (!c.al_lp || batch > c.al_batch) {
         qv_set_error(eng, "qv_debug_transcript_codes: the context holds no batch of that size (ask before the context is reused)");
         return QV_ERR_ARG;
@@ -755,9 +805,9 @@ extern "C" int qv_debug_retrieve(qv_engine *eng, const uint8_t *codes_host, int3
                                  double *cand_score, int32_t cand_cap, int32_t *n_cand, int32_t *runner_idx,
                                  double *runner_score, int32_t *n_runners, void *stream_) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream_);
     hipStream_t stream = (hipStream_t)stream_;
     if (!eng) return QV_ERR_ARG;
+    QV_ORDERED(eng, stream);
     QvCtx &c = eng->ctx[eng->cur_ctx];
     c.al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
     int rc = qv_post_debug_retrieve(eng, c, codes_host, n_codes, stream);
@@ -784,7 +834,6 @@ extern "C" int qv_tracker_match(qv_engine *eng, const uint8_t *codes_host, const
                                 const int32_t *n_words_host, const int32_t *bonus_verse_host, int32_t batch,
                                 qv_track_match *out_host, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (batch < 0 || !offsets_host || !n_words_host || !bonus_verse_host || !out_host || (batch > 0 && !codes_host)) {
         qv_set_error(eng, "qv_tracker_match: null argument");
@@ -798,24 +847,15 @@ extern "C" int qv_tracker_match(qv_engine *eng, const uint8_t *codes_host, const
         }
         if (n > eng->max_q) { qv_set_error(eng, "qv_tracker_match: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
     }
+    QV_ORDERED(eng, stream);
     return qv_post_tracker_match(eng, codes_host, offsets_host, n_words_host, bonus_verse_host, batch, out_host,
                                  (hipStream_t)stream);
-}
-
-// Entry points that run a single text through the workspace of ctx[cur_ctx] on the caller's
-// stream: with batches in flight, wait until no internal stream is still using a workspace.
-static int quiesce_contexts(qv_engine *eng) {
-    if (eng->n_ctx > 1)
-        for (int k = 0; k < eng->n_ctx; ++k)
-            if (eng->ctx[k].busy) QV_HIP(hipEventSynchronize(eng->ctx[k].done));
-    return QV_OK;
 }
 
 extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t n_codes, int32_t n_bonus,
                               const int32_t *bonus_verse, const double *bonus_value, int32_t max_span, int32_t *start,
                               int32_t *span, double *score, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (n_codes < 0 || (n_codes > 0 && !codes_host) || n_bonus < 0 || n_bonus > 3 || (n_bonus > 0 && (!bonus_verse || !bonus_value)) ||
         max_span < 2 || max_span > 8 || !start || !span || !score) {
@@ -825,6 +865,7 @@ extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t
     for (int i = 0; i < n_bonus; ++i)
         if (bonus_verse[i] < 0 || bonus_verse[i] >= eng->tab.n_verses) { qv_set_error(eng, "qv_match_verse: bonus verse out of range"); return QV_ERR_ARG; }
     if (n_codes > eng->max_q) { qv_set_error(eng, "qv_match_verse: text longer than the engine's max_transcript"); return QV_ERR_CAPACITY; }
+    QV_ORDERED(eng, stream);
     QV_TRY(quiesce_contexts(eng));
     QvCtx &c = eng->ctx[eng->cur_ctx];
     c.al_lp = nullptr;   // utt[0] of this workspace is about to be overwritten
@@ -839,8 +880,8 @@ extern "C" int qv_match_verse(qv_engine *eng, const uint8_t *codes_host, int32_t
 extern "C" int qv_debug_ctc_loss(qv_engine *eng, const float *lp, int32_t T, const uint16_t *tg, const int32_t *lens,
                                  int32_t n, float *loss_host, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng || n < 1) return QV_ERR_ARG;
+    QV_ORDERED(eng, stream);
     return qv_post_debug_ctc(eng, lp, T, tg, lens, n, loss_host, (hipStream_t)stream);
 }
 
@@ -849,7 +890,6 @@ extern "C" int qv_align(qv_engine *eng, const float *lp, const int32_t *t_host, 
                         const uint16_t *targets_host, const int32_t *lens_host, qv_align_info *info_host, int16_t *first_host,
                         int16_t *last_host, float *logp_host, int32_t pitch, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!lp || !t_host || !lens_host || !info_host || !first_host || !last_host || !logp_host || batch < 1 || t_max < 1 ||
         pitch < QV_ALIGN_MAX_TOKENS) {
@@ -859,6 +899,7 @@ extern "C" int qv_align(qv_engine *eng, const float *lp, const int32_t *t_host, 
     int64_t total = 0;
     for (int b = 0; b < batch; ++b) total += lens_host[b] > 0 ? lens_host[b] : 0;
     if (total > 0 && !targets_host) { qv_set_error(eng, "qv_align: targets_host is null"); return QV_ERR_ARG; }
+    QV_ORDERED(eng, stream);
     return qv_align_explicit(eng, eng->ctx[eng->cur_ctx], lp, t_host, batch, t_max, targets_host, lens_host, info_host, first_host,
                              last_host, logp_host, pitch, (hipStream_t)stream);
 }
@@ -867,12 +908,9 @@ extern "C" int qv_align_results_ctx(qv_engine *eng, int32_t k, int32_t batch, qv
                                     int16_t *first_host, int16_t *last_host, float *logp_host, int32_t pitch) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (k < 0 || k >= eng->n_ctx || batch < 1 || !info_host || !ids_host || !first_host || !last_host || !logp_host ||
-        pitch < QV_ALIGN_MAX_TOKENS) {
-        qv_set_error(eng, "qv_align_results_ctx: bad context, null argument, empty batch or pitch < QV_ALIGN_MAX_TOKENS");
-        return QV_ERR_ARG;
-    }
-    if (batch > eng->ctx[k].work.max_batch) { qv_set_error(eng, "qv_align_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    QV_TRY(ctx_batch_args(eng, "qv_align_results_ctx", k, batch,
+                          info_host && ids_host && first_host && last_host && logp_host && pitch >= QV_ALIGN_MAX_TOKENS,
+                          "bad context, null argument, empty batch or pitch < QV_ALIGN_MAX_TOKENS"));
     return qv_align_results(eng, k, batch, info_host, ids_host, first_host, last_host, logp_host, pitch);
 }
 
@@ -881,19 +919,15 @@ extern "C" int qv_nbest_results_ctx(qv_engine *eng, int32_t k_ctx, int32_t batch
                                     qv_nbest_entry *entries_host) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (k_ctx < 0 || k_ctx >= eng->n_ctx || batch < 1 || k < 1 || k > QV_NBEST_MAX || (flags & ~QV_NBEST_TEXT_RUNNERS) || !info_host ||
-        !entries_host) {
-        qv_set_error(eng, "qv_nbest_results_ctx: bad context, null argument, empty batch, k outside 1..QV_NBEST_MAX or unknown flags");
-        return QV_ERR_ARG;
-    }
-    if (batch > eng->ctx[k_ctx].work.max_batch) { qv_set_error(eng, "qv_nbest_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    QV_TRY(ctx_batch_args(eng, "qv_nbest_results_ctx", k_ctx, batch,
+                          k >= 1 && k <= QV_NBEST_MAX && !(flags & ~QV_NBEST_TEXT_RUNNERS) && info_host && entries_host,
+                          "bad context, null argument, empty batch, k outside 1..QV_NBEST_MAX or unknown flags"));
     return qv_nbest_results(eng, k_ctx, batch, k, flags, info_host, entries_host);
 }
 
 extern "C" int qv_nbest_select(qv_engine *eng, const double *final_host, const float *loss_host, const int32_t *n_host, int32_t rows,
                                int32_t pitch, int32_t k, int32_t *index_host, int32_t *count_host, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!final_host || !loss_host || !n_host || !index_host || !count_host || rows < 1 || pitch < 1 || pitch > QV_CAND_CAP || k < 1 ||
         k > QV_NBEST_MAX) {
@@ -904,6 +938,7 @@ extern "C" int qv_nbest_select(qv_engine *eng, const double *final_host, const f
     if (rows > c.work.max_batch) { qv_set_error(eng, "qv_nbest_select: rows exceed engine capacity"); return QV_ERR_CAPACITY; }
     for (int r = 0; r < rows; ++r)
         if (n_host[r] < 0 || n_host[r] > pitch) { qv_set_error(eng, "qv_nbest_select: n_host[r] outside 0..pitch"); return QV_ERR_ARG; }
+    QV_ORDERED(eng, stream);
     return qv_nbest_select_rows(eng, c, final_host, loss_host, n_host, rows, pitch, k, index_host, count_host, (hipStream_t)stream);
 }
 
@@ -918,7 +953,6 @@ extern "C" int qv_correct(qv_engine *eng, const uint8_t *pred_codes_host, const 
                           const int32_t *ref_off_host, int32_t rows, int32_t flags, qv_correct_info *info_host, uint8_t *ops_host,
                           int32_t ops_pitch, qv_correct_word *words_host, int32_t words_pitch, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!pred_codes_host || !pred_off_host || !ref_codes_host || !ref_off_host ||
         !correct_args_ok(eng, rows, flags, info_host, ops_host, ops_pitch, words_host, words_pitch)) {
@@ -934,6 +968,7 @@ extern "C" int qv_correct(qv_engine *eng, const uint8_t *pred_codes_host, const 
             return QV_ERR_ARG;
         }
     }
+    QV_ORDERED(eng, stream);
     return qv_correct_rows(eng, c, pred_codes_host, pred_off_host, ref_codes_host, ref_off_host, rows, flags, info_host, ops_host,
                            ops_pitch, words_host, words_pitch, (hipStream_t)stream);
 }
@@ -942,11 +977,9 @@ extern "C" int qv_correct_results_ctx(qv_engine *eng, int32_t k_ctx, int32_t bat
                                       uint8_t *ops_host, int32_t ops_pitch, qv_correct_word *words_host, int32_t words_pitch) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (k_ctx < 0 || k_ctx >= eng->n_ctx || !correct_args_ok(eng, batch, flags, info_host, ops_host, ops_pitch, words_host, words_pitch)) {
-        qv_set_error(eng, "qv_correct_results_ctx: bad context, null argument, empty batch, unknown flags or a pitch below its cap");
-        return QV_ERR_ARG;
-    }
-    if (batch > eng->ctx[k_ctx].work.max_batch) { qv_set_error(eng, "qv_correct_results_ctx: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
+    QV_TRY(ctx_batch_args(eng, "qv_correct_results_ctx", k_ctx, batch,
+                          correct_args_ok(eng, batch, flags, info_host, ops_host, ops_pitch, words_host, words_pitch),
+                          "bad context, null argument, empty batch, unknown flags or a pitch below its cap"));
     return qv_correct_results(eng, k_ctx, batch, flags, info_host, ops_host, ops_pitch, words_host, words_pitch);
 }
 
@@ -970,27 +1003,19 @@ extern "C" int qv_transcribe_batch(qv_engine *eng, const float *audio_dev, const
                                    int16_t *last_host, int32_t pitch, void *stream) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    QV_TRY(need_model(eng));
     if (!audio_dev || !lengths_host || !info_host || !ids_host || batch < 1) {
         qv_set_error(eng, "qv_transcribe_batch: null argument or empty batch");
         return QV_ERR_ARG;
     }
-    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "qv_transcribe_batch: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
-    int64_t lmax = 0;
-    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
-    const int t_max = qv_frames_for_samples(lmax);
-    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "qv_transcribe_batch: audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    int t_max;
+    QV_TRY(batch_in_capacity(eng, "qv_transcribe_batch: ", lengths_host, batch, &t_max));
     if (t_max < 1 || pitch < t_max) { qv_set_error(eng, "qv_transcribe_batch: pitch < qv_frames_for_samples(longest row)"); return QV_ERR_ARG; }
     QV_ORDERED(eng, stream);
-    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
-    QV_TRY(quiesce_contexts(eng));
-    QvCtx &c = eng->ctx[eng->cur_ctx];
-    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
-    std::vector<int32_t> t_out(batch);
-    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max, t_out.data(),
-                              (hipStream_t)stream, /*zero_pad_rows=*/false);
-    if (rc) return rc;
-    return qv_transcribe_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, info_host, ids_host, logp_host, first_host, last_host,
+    QvCtx *c;
+    std::vector<int32_t> t_out;
+    QV_TRY(forward_into_ws(eng, audio_dev, lengths_host, batch, n_max, t_max, (hipStream_t)stream, &c, t_out));
+    return qv_transcribe_rows(eng, *c, c->logprobs_ws, t_out.data(), batch, t_max, info_host, ids_host, logp_host, first_host, last_host,
                               pitch, (hipStream_t)stream);
 }
 
@@ -998,15 +1023,9 @@ extern "C" int qv_transcribe_batch(qv_engine *eng, const float *audio_dev, const
 extern "C" int qv_trie_stats(const char *tables_path, int32_t max_span, int32_t *nodes, int32_t *ends, int32_t *max_depth,
                              int32_t *max_children) {
     if (!tables_path || max_span < 1 || max_span > QV_TRIE_MAX_SPAN) { qv_set_error(nullptr, "qv_trie_stats: null path or max_span outside 1..6"); return QV_ERR_ARG; }
-    std::ifstream f(tables_path, std::ios::binary | std::ios::ate);
-    if (!f) { qv_set_error(nullptr, std::string("cannot open tables file: ") + tables_path); return QV_ERR_IO; }
-    const std::streamsize sz = f.tellg();
-    f.seekg(0);
-    std::vector<uint8_t> file(sz > 0 ? (size_t)sz : 0);
-    if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();   // refused below: bad magic
     HostTables h;
     std::string err;
-    if (int rc = qv_build_host_tables(file.data(), file.size(), h, err)) { qv_set_error(nullptr, err); return rc; }
+    if (int rc = qv_read_host_tables(tables_path, h, err)) { qv_set_error(nullptr, err); return rc; }
     QvTrie t;
     if (int rc = qv_trie_build(h.n_verses, h.tok_off.p, h.tok_off.n, h.tok.p, h.tok.n, max_span, t, err)) {
         qv_set_error(nullptr, err);
@@ -1054,25 +1073,17 @@ extern "C" int qv_beam_batch(qv_engine *eng, const float *audio_dev, const int64
                              int32_t *ids_host, int32_t pitch, void *stream) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    QV_TRY(need_model(eng));
     if (!audio_dev || !lengths_host || batch < 1) { qv_set_error(eng, "qv_beam_batch: null argument or empty batch"); return QV_ERR_ARG; }
-    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "qv_beam_batch: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
-    int64_t lmax = 0;
-    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
-    const int t_max = qv_frames_for_samples(lmax);
-    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "qv_beam_batch: audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    int t_max;
+    QV_TRY(batch_in_capacity(eng, "qv_beam_batch: ", lengths_host, batch, &t_max));
     if (t_max < 1) { qv_set_error(eng, "qv_beam_batch: no frames"); return QV_ERR_ARG; }
     QV_TRY(beam_args(eng, "qv_beam_batch", batch, max_span, beam, k, info_host, entries_host, ids_host, pitch, t_max));
     QV_ORDERED(eng, stream);
-    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
-    QV_TRY(quiesce_contexts(eng));
-    QvCtx &c = eng->ctx[eng->cur_ctx];
-    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
-    std::vector<int32_t> t_out(batch);
-    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max, t_out.data(),
-                              (hipStream_t)stream, /*zero_pad_rows=*/false);
-    if (rc) return rc;
-    return qv_beam_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, max_span, beam, k, info_host, entries_host, ids_host, pitch,
+    QvCtx *c;
+    std::vector<int32_t> t_out;
+    QV_TRY(forward_into_ws(eng, audio_dev, lengths_host, batch, n_max, t_max, (hipStream_t)stream, &c, t_out));
+    return qv_beam_rows(eng, *c, c->logprobs_ws, t_out.data(), batch, t_max, max_span, beam, k, info_host, entries_host, ids_host, pitch,
                         (hipStream_t)stream);
 }
 
@@ -1083,15 +1094,9 @@ extern "C" int qv_scan_stats(const char *tables_path, int32_t t_frames, int32_t 
         qv_set_error(nullptr, "qv_scan_stats: null path, t_frames outside 0..768, max_span outside 1..6 or a mask that selects nothing");
         return QV_ERR_ARG;
     }
-    std::ifstream f(tables_path, std::ios::binary | std::ios::ate);
-    if (!f) { qv_set_error(nullptr, std::string("cannot open tables file: ") + tables_path); return QV_ERR_IO; }
-    const std::streamsize sz = f.tellg();
-    f.seekg(0);
-    std::vector<uint8_t> file(sz > 0 ? (size_t)sz : 0);
-    if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();   // refused below: bad magic
     HostTables h;
     std::string err;
-    if (int rc = qv_build_host_tables(file.data(), file.size(), h, err)) { qv_set_error(nullptr, err); return rc; }
+    if (int rc = qv_read_host_tables(tables_path, h, err)) { qv_set_error(nullptr, err); return rc; }
     QvScanView v;
     v.n_verses = h.n_verses;
     v.tok_off = h.tok_off.p; v.n_tok_off = h.tok_off.n;
@@ -1136,25 +1141,17 @@ extern "C" int qv_scan_batch(qv_engine *eng, const float *audio_dev, const int64
                              qv_scan_entry *entries_host, float *loss_out_dev, void *stream) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    QV_TRY(need_model(eng));
     if (!audio_dev || !lengths_host || batch < 1) { qv_set_error(eng, "qv_scan_batch: null argument or empty batch"); return QV_ERR_ARG; }
-    if (batch > eng->ctx[0].work.max_batch) { qv_set_error(eng, "qv_scan_batch: batch exceeds engine capacity"); return QV_ERR_CAPACITY; }
-    int64_t lmax = 0;
-    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lengths_host[b]);
-    const int t_max = qv_frames_for_samples(lmax);
-    if (t_max > eng->ctx[0].work.t_cap) { qv_set_error(eng, "qv_scan_batch: audio longer than engine capacity"); return QV_ERR_CAPACITY; }
+    int t_max;
+    QV_TRY(batch_in_capacity(eng, "qv_scan_batch: ", lengths_host, batch, &t_max));
     if (t_max < 1) { qv_set_error(eng, "qv_scan_batch: no frames"); return QV_ERR_ARG; }
     QV_TRY(scan_args(eng, "qv_scan_batch", batch, max_span, k, surah_mask_host, info_host, entries_host));
     QV_ORDERED(eng, stream);
-    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
-    QV_TRY(quiesce_contexts(eng));
-    QvCtx &c = eng->ctx[eng->cur_ctx];
-    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
-    std::vector<int32_t> t_out(batch);
-    int rc = qv_model_forward(eng, eng->model, eng->cur_ctx, audio_dev, lengths_host, batch, n_max, c.logprobs_ws, t_max, t_out.data(),
-                              (hipStream_t)stream, /*zero_pad_rows=*/false);
-    if (rc) return rc;
-    return qv_scan_rows(eng, c, c.logprobs_ws, t_out.data(), batch, t_max, max_span, span_penalty, k, surah_mask_host, info_host,
+    QvCtx *c;
+    std::vector<int32_t> t_out;
+    QV_TRY(forward_into_ws(eng, audio_dev, lengths_host, batch, n_max, t_max, (hipStream_t)stream, &c, t_out));
+    return qv_scan_rows(eng, *c, c->logprobs_ws, t_out.data(), batch, t_max, max_span, span_penalty, k, surah_mask_host, info_host,
                         entries_host, loss_out_dev, (hipStream_t)stream);
 }
 
@@ -1183,20 +1180,17 @@ extern "C" int qv_transcribe_long(qv_engine *eng, const float *audio_dev, int64_
                                   float *logp_host, int32_t *first_host, int32_t *last_host, int32_t pitch, void *stream) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    QV_TRY(need_model(eng));
     if (!audio_dev || !lengths_host || !info_host || !ids_host || rows < 1 || audio_pitch < 1) {
         qv_set_error(eng, "qv_transcribe_long: null argument, no rows or audio_pitch < 1");
         return QV_ERR_ARG;
     }
     QV_ORDERED(eng, stream);
-    // the forward runs on the caller's stream into the current context's log-prob workspace: no batch may be in flight on it
-    QV_TRY(quiesce_contexts(eng));
-    QvCtx &c = eng->ctx[eng->cur_ctx];
+    QvCtx *c;
+    QV_TRY(claim_logprobs_ws(eng, &c));
     // (qv_long_run checks everything that can refuse the call before its first launch)
-    const int rc = qv_long_run(eng, c, audio_dev, audio_pitch, nullptr, 0, lengths_host, rows, window_samples, margin_frames, info_host,
-                               ids_host, logp_host, first_host, last_host, pitch, (hipStream_t)stream);
-    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
-    return rc;
+    return qv_long_run(eng, *c, audio_dev, audio_pitch, nullptr, 0, lengths_host, rows, window_samples, margin_frames, info_host,
+                       ids_host, logp_host, first_host, last_host, pitch, (hipStream_t)stream);
 }
 
 extern "C" int qv_transcribe_windows(qv_engine *eng, const float *logprobs_dev, int32_t t_max, const int64_t *n_samples_host, int32_t rows,
@@ -1220,19 +1214,16 @@ extern "C" int qv_align_long(qv_engine *eng, const float *audio_dev, int64_t aud
                              void *stream) {
     QV_SERIALISE(eng);
     if (!eng) return QV_ERR_ARG;
-    if (!eng->model) { qv_set_error(eng, "engine created without a model (with_model = 0)"); return QV_ERR_NO_MODEL; }
+    QV_TRY(need_model(eng));
     if (!audio_dev || !lengths_host || !lens_host || !info_host || !first_host || !last_host || !logp_host || rows < 1 || audio_pitch < 1) {
         qv_set_error(eng, "qv_align_long: null argument, no rows or audio_pitch < 1");
         return QV_ERR_ARG;
     }
     QV_ORDERED(eng, stream);
-    // as qv_transcribe_long: the forward runs into the current context's log-prob workspace, no batch may be in flight on it
-    QV_TRY(quiesce_contexts(eng));
-    QvCtx &c = eng->ctx[eng->cur_ctx];
-    const int rc = qv_align_long_run(eng, c, audio_dev, audio_pitch, nullptr, 0, lengths_host, rows, window_samples, margin_frames,
-                                     targets_host, lens_host, info_host, first_host, last_host, logp_host, pitch, (hipStream_t)stream);
-    if (c.al_lp == c.logprobs_ws) c.al_lp = nullptr;   // the batch those log-probs belonged to can no longer be aligned
-    return rc;
+    QvCtx *c;
+    QV_TRY(claim_logprobs_ws(eng, &c));
+    return qv_align_long_run(eng, *c, audio_dev, audio_pitch, nullptr, 0, lengths_host, rows, window_samples, margin_frames,
+                             targets_host, lens_host, info_host, first_host, last_host, logp_host, pitch, (hipStream_t)stream);
 }
 
 extern "C" int qv_align_windows(qv_engine *eng, const float *logprobs_dev, int32_t t_max, const int64_t *n_samples_host, int32_t rows,
@@ -1268,9 +1259,9 @@ extern "C" int qv_align_long_kernel_times(qv_engine *eng, float *ms2_host) {
 
 extern "C" int qv_debug_forward_tap(qv_engine *eng, int32_t what, int32_t layer, float *out_dev, void *stream) {
     QV_SERIALISE(eng);
-    QV_ORDERED(eng, stream);
     if (!eng) return QV_ERR_ARG;
     if (!eng->model) { qv_set_error(eng, "engine created without a model"); return QV_ERR_NO_MODEL; }
+    QV_ORDERED(eng, stream);
     return qv_model_tap(eng, eng->model, eng->cur_ctx, what, layer, out_dev, (hipStream_t)stream);
 }
 

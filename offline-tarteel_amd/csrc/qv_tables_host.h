@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <fstream>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -85,6 +86,7 @@ struct HostTables {
     // host copies the engine keeps
     std::vector<uint8_t> h_surah;
     std::vector<uint16_t> h_ayah;
+    std::vector<uint8_t> file;   // qv_read_host_tables: the file's bytes, which the views point into
 };
 
 // `data` must be aligned for uint64_t (a std::vector's or malloc's storage is) and outlive `out`, whose views point into it.
@@ -291,4 +293,22 @@ inline int qv_build_host_tables(const uint8_t *data, size_t size, HostTables &ou
     t.piece_codes.assign(pcodes.p, pcodes.p + t.piece_off[QV_VOCAB]);
     t.piece_codes.resize(t.piece_codes.size() + 16, 0);
     return QV_OK;
+}
+
+// The tables file at `path`, read whole and built: QV_OK with `out` filled (it owns the bytes its views point into), else
+// the code and `err`.  A file that is empty or cannot be read to its end is refused by the bad-magic rule above.
+inline int qv_read_host_tables(const char *path, HostTables &out, std::string &err) {
+    std::vector<uint8_t> file;
+    {
+        std::ifstream f;
+        if (path) f.open(path, std::ios::binary | std::ios::ate);
+        if (!path || !f) { err = std::string("cannot open tables file: ") + (path ? path : "(null)"); return QV_ERR_IO; }
+        const std::streamsize sz = f.tellg();
+        f.seekg(0);
+        file.resize(sz > 0 ? (size_t)sz : 0);
+        if (!f.read((char *)file.data(), (std::streamsize)file.size())) file.clear();
+    }
+    const int rc = qv_build_host_tables(file.data(), file.size(), out, err);
+    if (rc == QV_OK) out.file = std::move(file);   // (a moved vector keeps its storage: the views stay valid)
+    return rc;
 }

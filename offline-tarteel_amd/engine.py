@@ -38,6 +38,11 @@ class QvError(RuntimeError):
     pass
 
 
+def _p(a):
+    """a numpy array as the pointer the C ABI takes; None is a null pointer"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 class QvConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("device", C.c_int32),
@@ -233,7 +238,7 @@ def scan_stats(t_frames: int, max_span: int = 6, surahs=None, tables_path: str |
     nf, nr, ss = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     m = surah_mask(surahs)
     rc = lib.qv_scan_stats(str(tables_path or TABLES_PATH).encode(), int(t_frames), int(max_span),
-                           None if m is None else m.ctypes.data_as(C.c_void_p), C.byref(nf), C.byref(nr), C.byref(ss))
+                           _p(m), C.byref(nf), C.byref(nr), C.byref(ss))
     if rc != 0:
         msg = lib.qv_last_error(None).decode()
         if rc == 2:
@@ -467,6 +472,25 @@ class Engine:
     def frames_for(self, n_samples: int) -> int:
         return int(self.lib.qv_frames_for_samples(int(n_samples)))
 
+    def _audio_args(self, audio, lengths):
+        """(B, N, lengths as int64) of a zero-padded batch: audio a contiguous float32 cuda [B, N], one length per row, none
+        above N (the forward reads lengths[b] samples of row b)"""
+        assert audio.is_cuda and audio.dtype == self.torch.float32 and audio.is_contiguous() and audio.dim() == 2
+        B, N = audio.shape
+        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        assert len(ln) == B and ln.max() <= N
+        return B, N, ln
+
+    def _logprob_args(self, log_probs, t_frames=None, per_row: bool = True):
+        """(B, t_max, t_frames as int32 or None) of a contiguous float32 cuda [B, t_max, 1025]; per_row: one count per row"""
+        assert log_probs.is_cuda and log_probs.dtype == self.torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
+        B, t_max, V = log_probs.shape
+        assert V == 1025
+        if t_frames is None:
+            return B, t_max, None
+        assert not per_row or len(t_frames) == B
+        return B, t_max, np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+
     def _results(self, res: np.ndarray, greedy: np.ndarray | None) -> list[dict]:
         out = []
         for b in range(len(res)):
@@ -499,16 +523,12 @@ class Engine:
     def forward(self, audio, lengths):
         """audio: float32 cuda tensor [B, N] (zero padded); lengths: int sequence.
         Returns (log_probs [B, Tmax, 1025] cuda float32, T list)."""
-        torch = self.torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
-        B, N = audio.shape
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-        assert len(ln) == B and ln.max() <= N
+        B, N, ln = self._audio_args(audio, lengths)
         t_max = self.frames_for(int(ln.max()))
-        lp = torch.empty((B, t_max, 1025), dtype=torch.float32, device=audio.device)
+        lp = self.torch.empty((B, t_max, 1025), dtype=self.torch.float32, device=audio.device)
         t_out = np.zeros(B, dtype=np.int32)
-        rc = self.lib.qv_forward(self.h, C.c_void_p(audio.data_ptr()), ln.ctypes.data_as(C.c_void_p), B, N,
-                                 C.c_void_p(lp.data_ptr()), t_max, t_out.ctypes.data_as(C.c_void_p), self._stream())
+        rc = self.lib.qv_forward(self.h, C.c_void_p(audio.data_ptr()), _p(ln), B, N, C.c_void_p(lp.data_ptr()), t_max, _p(t_out),
+                                 self._stream())
         self._check(rc, "qv_forward")
         return lp, t_out.tolist()
 
@@ -518,33 +538,21 @@ class Engine:
         frames each of them occupies in `log_probs`.  nbest=K: every dict gains "nbest", the row's list of up to K ranked
         alternatives (nbest_results).  correct=True: every dict gains "correction", the row's word-level comparison of
         the transcript with the winner's text (correct_results with the two texts; correct_prefix=True: in prefix mode)."""
-        torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous()
-        B, t_max, V = log_probs.shape
-        assert V == 1025
-        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        B, t_max, t = self._logprob_args(log_probs, t_frames, per_row=False)
         res = np.zeros(B, dtype=RESULT_DTYPE)
         greedy = np.full((B, t_max), -1, dtype=np.int32) if want_text else None
-        rc = self.lib.qv_decode_retrieve_rerank(
-            self.h, C.c_void_p(log_probs.data_ptr()), t.ctypes.data_as(C.c_void_p), B, t_max,
-            res.ctypes.data_as(C.c_void_p),
-            greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
+        rc = self.lib.qv_decode_retrieve_rerank(self.h, C.c_void_p(log_probs.data_ptr()), _p(t), B, t_max, _p(res), _p(greedy),
+                                                self._stream())
         self._check(rc, "qv_decode_retrieve_rerank")
         return self._with_correction(self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest), correct, correct_prefix)
 
     def predict_batch(self, audio, lengths, want_text: bool = True, align: bool = False, nbest: int | None = None,
                       correct: bool = False, correct_prefix: bool = False) -> list[dict]:
-        torch = self.torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
-        B, N = audio.shape
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        B, N, ln = self._audio_args(audio, lengths)
         t_max = self.frames_for(int(ln.max()))
         res = np.zeros(B, dtype=RESULT_DTYPE)
         greedy = np.full((B, t_max), -1, dtype=np.int32) if want_text else None
-        rc = self.lib.qv_predict_batch(
-            self.h, C.c_void_p(audio.data_ptr()), ln.ctypes.data_as(C.c_void_p), B, N,
-            res.ctypes.data_as(C.c_void_p),
-            greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None, self._stream())
+        rc = self.lib.qv_predict_batch(self.h, C.c_void_p(audio.data_ptr()), _p(ln), B, N, _p(res), _p(greedy), self._stream())
         self._check(rc, "qv_predict_batch")
         return self._with_correction(self._with_nbest(self._with_alignment(self._results(res, greedy), align), nbest), correct, correct_prefix)
 
@@ -584,9 +592,8 @@ class Engine:
 
         (pc, po), (rc_, ro) = pack(pred_codes), pack(ref_codes)
         info, ops, words = self._correct_buffers(rows)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_correct(self.h, p(pc), p(po), p(rc_), p(ro), rows, CORRECT_PREFIX if prefix else 0, p(info), p(ops),
-                                 ops.shape[1], p(words), words.shape[1], self._stream())
+        rc = self.lib.qv_correct(self.h, _p(pc), _p(po), _p(rc_), _p(ro), rows, CORRECT_PREFIX if prefix else 0, _p(info), _p(ops),
+                                 ops.shape[1], _p(words), words.shape[1], self._stream())
         self._check(rc, "qv_correct")
         return info, ops, words
 
@@ -613,9 +620,8 @@ class Engine:
         if ctx is None:
             ctx = int(self.lib.qv_last_context(self.h))
         info, ops, words = self._correct_buffers(batch)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_correct_results_ctx(self.h, int(ctx), int(batch), CORRECT_PREFIX if prefix else 0, p(info), p(ops),
-                                             ops.shape[1], p(words), words.shape[1])
+        rc = self.lib.qv_correct_results_ctx(self.h, int(ctx), int(batch), CORRECT_PREFIX if prefix else 0, _p(info), _p(ops),
+                                             ops.shape[1], _p(words), words.shape[1])
         self._check(rc, "qv_correct_results_ctx")
         out = self._corrections(info, ops, words)
         if texts:
@@ -639,7 +645,7 @@ class Engine:
         info = np.zeros(batch, dtype=NBEST_INFO_DTYPE)
         ent = np.zeros((batch, max(int(k), 1)), dtype=NBEST_ENTRY_DTYPE)
         rc = self.lib.qv_nbest_results_ctx(self.h, int(ctx), int(batch), int(k), NBEST_TEXT_RUNNERS if runners else 0,
-                                           info.ctypes.data_as(C.c_void_p), ent.ctypes.data_as(C.c_void_p))
+                                           _p(info), _p(ent))
         self._check(rc, "qv_nbest_results_ctx")
         return info, ent
 
@@ -682,8 +688,7 @@ class Engine:
             los[r, : n[r]] = np.asarray(losses[r], np.float32)
         idx = np.zeros((rows, max(int(k), 1)), np.int32)
         cnt = np.zeros(rows, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_nbest_select(self.h, p(fin), p(los), p(n), rows, pitch, int(k), p(idx), p(cnt), self._stream())
+        rc = self.lib.qv_nbest_select(self.h, _p(fin), _p(los), _p(n), rows, pitch, int(k), _p(idx), _p(cnt), self._stream())
         self._check(rc, "qv_nbest_select")
         assert all((idx[r, cnt[r]:] == -1).all() for r in range(rows))
         return [idx[r, : cnt[r]].tolist() for r in range(rows)]
@@ -713,20 +718,16 @@ class Engine:
         (first / last encoder frame of every token, inclusive; a frame is 0.08 s), "logp" (mean log-prob of the token over
         its frames), "score" (log-prob of the whole path), "flags" (ALIGN_NO_TARGET / ALIGN_TOO_LONG / ALIGN_INFEASIBLE:
         the arrays are then empty and score is 0), "n_tokens", "t_frames"."""
-        torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
-        B, t_max, V = log_probs.shape
-        assert V == 1025 and len(targets) == B and len(t_frames) == B
-        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        B, t_max, t = self._logprob_args(log_probs, t_frames)
+        assert len(targets) == B
         lens = np.ascontiguousarray(np.array([len(x) for x in targets], np.int32))
         tg = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint16).reshape(-1) for x in targets] + [np.zeros(1, np.uint16)]))
         pitch = ALIGN_MAX_TOKENS
         info = np.zeros(B, dtype=ALIGN_INFO_DTYPE)
         first, last = np.zeros((B, pitch), np.int16), np.zeros((B, pitch), np.int16)
         logp = np.zeros((B, pitch), np.float32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_align(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, p(tg), p(lens), p(info), p(first), p(last),
-                               p(logp), pitch, self._stream())
+        rc = self.lib.qv_align(self.h, C.c_void_p(log_probs.data_ptr()), _p(t), B, t_max, _p(tg), _p(lens), _p(info), _p(first), _p(last),
+                               _p(logp), pitch, self._stream())
         self._check(rc, "qv_align")
         ids = np.full((B, pitch), -1, np.int32)
         for b, x in enumerate(targets):
@@ -747,17 +748,14 @@ class Engine:
         ids = np.zeros((batch, pitch), np.uint16)
         first, last = np.zeros((batch, pitch), np.int16), np.zeros((batch, pitch), np.int16)
         logp = np.zeros((batch, pitch), np.float32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_align_results_ctx(self.h, int(ctx), int(batch), p(info), p(ids), p(first), p(last), p(logp), pitch)
+        rc = self.lib.qv_align_results_ctx(self.h, int(ctx), int(batch), _p(info), _p(ids), _p(first), _p(last), _p(logp), pitch)
         self._check(rc, "qv_align_results_ctx")
         return self._alignments(info, ids, first, last, logp)
 
     def predict_batch_async(self, audio, lengths):
-        B, N = audio.shape
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        B, N, ln = self._audio_args(audio, lengths)
         ctx = C.c_int32(-1)
-        rc = self.lib.qv_predict_batch_async_ctx(self.h, C.c_void_p(audio.data_ptr()), ln.ctypes.data_as(C.c_void_p), B, N,
-                                                 self._stream(), C.byref(ctx))
+        rc = self.lib.qv_predict_batch_async_ctx(self.h, C.c_void_p(audio.data_ptr()), _p(ln), B, N, self._stream(), C.byref(ctx))
         self._check(rc, "qv_predict_batch_async_ctx")
         return int(ctx.value)     # (the id comes back from the call itself: another thread cannot get in between)
 
@@ -765,8 +763,7 @@ class Engine:
         """join context `ctx` (the value predict_batch_async returned) and copy its results out."""
         res = np.zeros(batch, dtype=RESULT_DTYPE)
         greedy = np.full((batch, t_max), -1, dtype=np.int32) if want_text else None
-        rc = self.lib.qv_fetch_results_ctx(self.h, ctx, batch, t_max, res.ctypes.data_as(C.c_void_p),
-                                           greedy.ctypes.data_as(C.c_void_p) if greedy is not None else None)
+        rc = self.lib.qv_fetch_results_ctx(self.h, ctx, batch, t_max, _p(res), _p(greedy))
         self._check(rc, "qv_fetch_results_ctx")
         return self._results(res, greedy)
 
@@ -807,7 +804,7 @@ class Engine:
         if up == down == 1:
             return x.clone()
         y = torch.empty(n_out, dtype=torch.float32, device=x.device)
-        rc = self.lib.qv_upfirdn(self.h, C.c_void_p(x.data_ptr()), n_in, taps.ctypes.data_as(C.c_void_p), len(taps),
+        rc = self.lib.qv_upfirdn(self.h, C.c_void_p(x.data_ptr()), n_in, _p(taps), len(taps),
                                  up, down, m0, n_out, C.c_void_p(y.data_ptr()), self._stream())
         self._check(rc, "qv_upfirdn")
         return y
@@ -835,8 +832,7 @@ class Engine:
         assert pitch >= max(n_out)
         y = torch.empty((rows, pitch), dtype=torch.float32, device=x.device)
         src = None if src_rows is None else np.ascontiguousarray(np.asarray(list(src_rows), dtype=np.int32))
-        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-        rc = self.lib.qv_upfirdn_batch(self.h, C.c_void_p(x.data_ptr()), int(x.stride(0)), p(src), p(lens), rows, p(taps), len(taps),
+        rc = self.lib.qv_upfirdn_batch(self.h, C.c_void_p(x.data_ptr()), int(x.stride(0)), _p(src), _p(lens), rows, _p(taps), len(taps),
                                        up_r, down_r, m0, C.c_void_p(y.data_ptr()), pitch, self._stream())
         self._check(rc, "qv_upfirdn_batch")
         return y, n_out
@@ -847,7 +843,7 @@ class Engine:
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
         nf = np.ascontiguousarray(np.asarray(n_frames, dtype=np.int64))
         y = torch.zeros((len(nf), int(nf.max())), dtype=torch.float32, device=x.device)
-        rc = self.lib.qv_mixdown_batch(self.h, C.c_void_p(x.data_ptr()), int(x.stride(0)), nf.ctypes.data_as(C.c_void_p), len(nf), int(channels),
+        rc = self.lib.qv_mixdown_batch(self.h, C.c_void_p(x.data_ptr()), int(x.stride(0)), _p(nf), len(nf), int(channels),
                                        C.c_void_p(y.data_ptr()), int(y.stride(0)), self._stream())
         self._check(rc, "qv_mixdown_batch")
         return y
@@ -922,8 +918,7 @@ class Engine:
         ms = np.zeros(21)
         fl = np.zeros(21)
         n = np.zeros(21, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._check(self.lib.qv_profile_gemm_read(self.h, p(ms), p(fl), p(n)), "qv_profile_gemm_read")
+        self._check(self.lib.qv_profile_gemm_read(self.h, _p(ms), _p(fl), _p(n)), "qv_profile_gemm_read")
         out = []
         for c in range(21):
             if n[c]:
@@ -940,11 +935,9 @@ class Engine:
             self._injected = None
             self._check(self.lib.qv_profile_inject_logprobs(self.h, None, 0, None, 0), "qv_profile_inject_logprobs")
             return
-        assert log_probs.is_cuda and log_probs.dtype == self.torch.float32 and log_probs.is_contiguous() and log_probs.shape[2] == 1025
-        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        B, t_max, t = self._logprob_args(log_probs, t_frames, per_row=False)
         self._injected = log_probs
-        self._check(self.lib.qv_profile_inject_logprobs(self.h, C.c_void_p(log_probs.data_ptr()), log_probs.shape[1],
-                                                        t.ctypes.data_as(C.c_void_p), log_probs.shape[0]), "qv_profile_inject_logprobs")
+        self._check(self.lib.qv_profile_inject_logprobs(self.h, C.c_void_p(log_probs.data_ptr()), t_max, _p(t), B), "qv_profile_inject_logprobs")
 
     def profile_stages(self, enable: bool):
         """device-side stage timers (the reference's C2C_DIRECT_MIXED_PROFILE split, mixed/run.py:117-124)"""
@@ -956,7 +949,7 @@ class Engine:
         if ctx is None:
             ctx = int(self.lib.qv_last_context(self.h))
         ms = np.zeros(4, np.float32)
-        self._check(self.lib.qv_stage_times(self.h, ctx, ms.ctypes.data_as(C.c_void_p)), "qv_stage_times")
+        self._check(self.lib.qv_stage_times(self.h, ctx, _p(ms)), "qv_stage_times")
         return {k: float(v) * 1e-3 for k, v in zip(("forward", "decode", "build", "rerank"), ms)}
 
     REPLAY_SHAPES = ["FFN-up [M,512]x[512,2048]+Swish", "FFN-down [M,2048]x[2048,512]+residual", "QKV [M,512]x[512,1536]",
@@ -1001,8 +994,7 @@ class Engine:
         nw = np.ascontiguousarray(np.array([len(t.split()) for t in texts], np.int32))
         bonus = np.ascontiguousarray(np.array([self.next_verse(*r) if r else -1 for r in last_refs], np.int32))
         out = (QvTrackMatch * n)()
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_tracker_match(self.h, p(codes), p(off), p(nw), p(bonus), n, C.cast(out, C.c_void_p),
+        rc = self.lib.qv_tracker_match(self.h, _p(codes), _p(off), _p(nw), _p(bonus), n, C.cast(out, C.c_void_p),
                                        self._stream())
         self._check(rc, "qv_tracker_match")
         return [None if m.verse < 0 else
@@ -1048,8 +1040,7 @@ class Engine:
         bv = np.ascontiguousarray(np.array([b[0] for b in bon] + [0] * (3 - len(bon)), np.int32))
         bb = np.ascontiguousarray(np.array([b[1] for b in bon] + [0.0] * (3 - len(bon)), np.float64))
         st, sp, sc = C.c_int32(), C.c_int32(), C.c_double()
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_match_verse(self.h, p(codes), len(codes), len(bon), p(bv), p(bb), int(max_span),
+        rc = self.lib.qv_match_verse(self.h, _p(codes), len(codes), len(bon), _p(bv), _p(bb), int(max_span),
                                      C.byref(st), C.byref(sp), C.byref(sc), self._stream())
         self._check(rc, "qv_match_verse")
         if st.value < 0 or not (sc.value >= threshold):
@@ -1082,20 +1073,16 @@ class Engine:
     def transcribe_raw(self, log_probs, t_frames, pitch: int | None = None):
         """qv_transcribe as arrays: (info [B] of TRANSCRIPT_INFO_DTYPE, ids int32 [B, pitch], logp float32, first / last
         int16 [B, pitch]); entries past a row's n_tokens hold -1 (ids, first, last) and 0 (logp)."""
-        torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
-        B, t_max, V = log_probs.shape
-        assert V == 1025 and len(t_frames) == B
-        pitch = t_max if pitch is None else int(pitch)
-        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        B, t_max, t = self._logprob_args(log_probs, t_frames)
+        head = (C.c_void_p(log_probs.data_ptr()), _p(t), B, t_max)
+        return self._transcribe_call(self.lib.qv_transcribe, "qv_transcribe", head, B, t_max if pitch is None else int(pitch))
+
+    def _transcribe_call(self, fn, what, head, B, pitch):
         info = np.zeros(B, dtype=TRANSCRIPT_INFO_DTYPE)
         ids = np.zeros((B, max(pitch, 1)), np.int32)
         logp = np.zeros((B, max(pitch, 1)), np.float32)
         first, last = np.zeros((B, max(pitch, 1)), np.int16), np.zeros((B, max(pitch, 1)), np.int16)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_transcribe(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, p(info), p(ids), p(logp), p(first),
-                                    p(last), pitch, self._stream())
-        self._check(rc, "qv_transcribe")
+        self._check(fn(self.h, *head, _p(info), _p(ids), _p(logp), _p(first), _p(last), pitch, self._stream()), what)
         return info, ids, logp, first, last
 
     def transcribe_logprobs(self, log_probs, t_frames) -> list[dict]:
@@ -1112,21 +1099,10 @@ class Engine:
         transcribe_logprobs returns it (qv_transcribe_batch: the forward into the engine's own workspace, argmax, collapse
         and confidence on the device) -- a reference-style {"text", "avg_logprob"} transcriber result."""
         if confidence:
-            torch = self.torch
-            assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
-            B, N = audio.shape
-            ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-            assert len(ln) == B and ln.max() <= N
-            pitch = self.frames_for(int(ln.max()))
-            info = np.zeros(B, dtype=TRANSCRIPT_INFO_DTYPE)
-            ids = np.zeros((B, pitch), np.int32)
-            logp = np.zeros((B, pitch), np.float32)
-            first, last = np.zeros((B, pitch), np.int16), np.zeros((B, pitch), np.int16)
-            p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-            rc = self.lib.qv_transcribe_batch(self.h, C.c_void_p(audio.data_ptr()), p(ln), B, N, p(info), p(ids), p(logp), p(first),
-                                              p(last), pitch, self._stream())
-            self._check(rc, "qv_transcribe_batch")
-            return self._transcripts(info, ids, logp, first, last)
+            B, N, ln = self._audio_args(audio, lengths)
+            head = (C.c_void_p(audio.data_ptr()), _p(ln), B, N)   # (the pitch: the longest row's frames, never below 1)
+            return self._transcripts(*self._transcribe_call(self.lib.qv_transcribe_batch, "qv_transcribe_batch", head, B,
+                                                            self.frames_for(int(ln.max()))))
         lp, T = self.forward(audio, lengths)
         ids = lp.argmax(-1).cpu().numpy()
         out = []
@@ -1142,25 +1118,22 @@ class Engine:
         """the tokens from the root to `node` of the trie for max_span (qv_trie_node_tokens)"""
         ids = np.zeros(1024, np.int32)
         n = C.c_int32(0)
-        rc = self.lib.qv_trie_node_tokens(self.h, int(max_span), int(node), ids.ctypes.data_as(C.c_void_p), len(ids), C.byref(n))
+        rc = self.lib.qv_trie_node_tokens(self.h, int(max_span), int(node), _p(ids), len(ids), C.byref(n))
         self._check(rc, "qv_trie_node_tokens")
         return ids[: n.value].tolist()
 
     def beam_raw(self, log_probs, t_frames, beam: int = 8, k: int = 5, max_span: int = 3):
         """qv_beam_decode as arrays: (info [B] of BEAM_INFO_DTYPE, entries [B, k] of BEAM_ENTRY_DTYPE, ids int32 [B, t_max] --
         the tokens of entry 0, -1 padded)."""
-        torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
-        B, t_max, V = log_probs.shape
-        assert V == 1025 and len(t_frames) == B
-        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
+        B, t_max, t = self._logprob_args(log_probs, t_frames)
+        head = (C.c_void_p(log_probs.data_ptr()), _p(t), B, t_max)
+        return self._beam_call(self.lib.qv_beam_decode, "qv_beam_decode", head, B, t_max, beam, k, max_span)
+
+    def _beam_call(self, fn, what, head, B, pitch, beam, k, max_span):
         info = np.zeros(B, dtype=BEAM_INFO_DTYPE)
         ent = np.zeros((B, max(int(k), 1)), dtype=BEAM_ENTRY_DTYPE)
-        ids = np.full((B, max(t_max, 1)), -1, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_beam_decode(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, int(max_span), int(beam), int(k), p(info),
-                                     p(ent), p(ids), t_max, self._stream())
-        self._check(rc, "qv_beam_decode")
+        ids = np.full((B, max(pitch, 1)), -1, np.int32)
+        self._check(fn(self.h, *head, int(max_span), int(beam), int(k), _p(info), _p(ent), _p(ids), pitch, self._stream()), what)
         return info, ent, ids
 
     def _beam_rows(self, info, ent, ids, max_span: int) -> list[dict]:
@@ -1191,20 +1164,10 @@ class Engine:
 
     def beam_batch(self, audio, lengths, beam: int = 8, k: int = 5, max_span: int = 3) -> list[dict]:
         """beam_logprobs behind the forward (qv_beam_batch): audio float32 cuda [B, N], zero padded"""
-        torch = self.torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
-        B, N = audio.shape
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-        assert len(ln) == B and ln.max() <= N
+        B, N, ln = self._audio_args(audio, lengths)
+        head = (C.c_void_p(audio.data_ptr()), _p(ln), B, N)
         pitch = max(self.frames_for(int(ln.max())), 1)
-        info = np.zeros(B, dtype=BEAM_INFO_DTYPE)
-        ent = np.zeros((B, max(int(k), 1)), dtype=BEAM_ENTRY_DTYPE)
-        ids = np.full((B, pitch), -1, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_beam_batch(self.h, C.c_void_p(audio.data_ptr()), p(ln), B, N, int(max_span), int(beam), int(k), p(info), p(ent),
-                                    p(ids), pitch, self._stream())
-        self._check(rc, "qv_beam_batch")
-        return self._beam_rows(info, ent, ids, max_span)
+        return self._beam_rows(*self._beam_call(self.lib.qv_beam_batch, "qv_beam_batch", head, B, pitch, beam, k, max_span), max_span)
 
     # ------------------------------------------------ exhaustive CTC scan -----
     def _scan_masks(self, surahs, B: int) -> np.ndarray | None:
@@ -1236,20 +1199,21 @@ class Engine:
                  return_losses: bool = False):
         """qv_scan_logprobs as arrays: (info [B] of SCAN_INFO_DTYPE, entries [B, k] of SCAN_ENTRY_DTYPE, losses -- a float32
         cuda tensor [B, n_verses * 6] with +inf at every key that was not scored, or None)."""
+        B, t_max, t = self._logprob_args(log_probs, t_frames)
+        head = (C.c_void_p(log_probs.data_ptr()), _p(t), B, t_max)
+        return self._scan_call(self.lib.qv_scan_logprobs, "qv_scan_logprobs", head, B, log_probs.device, k, max_span, span_penalty, surahs,
+                               return_losses)
+
+    def _scan_call(self, fn, what, head, B, device, k, max_span, span_penalty, surahs, return_losses):
         torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
-        B, t_max, V = log_probs.shape
-        assert V == 1025 and len(t_frames) == B
-        t = np.ascontiguousarray(np.asarray(t_frames, dtype=np.int32))
         info = np.zeros(B, dtype=SCAN_INFO_DTYPE)
         ent = np.zeros((B, max(int(k), 1)), dtype=SCAN_ENTRY_DTYPE)
         mask = self._scan_masks(surahs, B)
-        losses = torch.empty((B, self.tables.n_verses * 6), dtype=torch.float32, device=log_probs.device) if return_losses else None
+        losses = torch.empty((B, self.tables.n_verses * 6), dtype=torch.float32, device=device) if return_losses else None
         pen = float(self.cfg.span_penalty if span_penalty is None else span_penalty)
-        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_scan_logprobs(self.h, C.c_void_p(log_probs.data_ptr()), p(t), B, t_max, int(max_span), pen, int(k), p(mask),
-                                       p(info), p(ent), C.c_void_p(losses.data_ptr()) if return_losses else None, self._stream())
-        self._check(rc, "qv_scan_logprobs")
+        rc = fn(self.h, *head, int(max_span), pen, int(k), _p(mask), _p(info), _p(ent),
+                C.c_void_p(losses.data_ptr()) if return_losses else None, self._stream())
+        self._check(rc, what)
         return info, ent, losses
 
     def scan_logprobs(self, log_probs, t_frames, k: int = 5, max_span: int = 6, span_penalty: float | None = None, surahs=None,
@@ -1266,26 +1230,15 @@ class Engine:
     def scan_batch(self, audio, lengths, k: int = 5, max_span: int = 6, span_penalty: float | None = None, surahs=None,
                    return_losses: bool = False) -> list[dict]:
         """scan_logprobs behind the forward (qv_scan_batch): audio float32 cuda [B, N], zero padded"""
-        torch = self.torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous()
-        B, N = audio.shape
-        ln = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-        assert len(ln) == B and ln.max() <= N
-        info = np.zeros(B, dtype=SCAN_INFO_DTYPE)
-        ent = np.zeros((B, max(int(k), 1)), dtype=SCAN_ENTRY_DTYPE)
-        mask = self._scan_masks(surahs, B)
-        losses = torch.empty((B, self.tables.n_verses * 6), dtype=torch.float32, device=audio.device) if return_losses else None
-        pen = float(self.cfg.span_penalty if span_penalty is None else span_penalty)
-        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_scan_batch(self.h, C.c_void_p(audio.data_ptr()), p(ln), B, N, int(max_span), pen, int(k), p(mask), p(info),
-                                    p(ent), C.c_void_p(losses.data_ptr()) if return_losses else None, self._stream())
-        self._check(rc, "qv_scan_batch")
-        return self._scan_rows(info, ent, losses)
+        B, N, ln = self._audio_args(audio, lengths)
+        head = (C.c_void_p(audio.data_ptr()), _p(ln), B, N)
+        return self._scan_rows(*self._scan_call(self.lib.qv_scan_batch, "qv_scan_batch", head, B, audio.device, k, max_span, span_penalty,
+                                                surahs, return_losses))
 
     def scan_kernel_times(self) -> dict:
         """with profile_stages(True): seconds the last scan spent in its two kernels (qv_scan_kernel_times)"""
         ms = np.zeros(2, np.float32)
-        self._check(self.lib.qv_scan_kernel_times(self.h, ms.ctypes.data_as(C.c_void_p)), "qv_scan_kernel_times")
+        self._check(self.lib.qv_scan_kernel_times(self.h, _p(ms)), "qv_scan_kernel_times")
         return {"score": float(ms[0]) * 1e-3, "select": float(ms[1]) * 1e-3}
 
     # ------------------------------------------------ recordings of any length -----
@@ -1320,8 +1273,7 @@ class Engine:
         ids = np.zeros((rows, max(pitch, 1)), np.int32)
         logp = np.zeros((rows, max(pitch, 1)), np.float32)
         first, last = np.zeros((rows, max(pitch, 1)), np.int32), np.zeros((rows, max(pitch, 1)), np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = fn(self.h, *head, rows, int(window_samples), int(margin_frames), p(info), p(ids), p(logp), p(first), p(last), pitch,
+        rc = fn(self.h, *head, rows, int(window_samples), int(margin_frames), _p(info), _p(ids), _p(logp), _p(first), _p(last), pitch,
                 self._stream())
         self._check(rc, what)
         return info, ids, logp, first, last
@@ -1330,25 +1282,24 @@ class Engine:
         """qv_transcribe_windows as arrays: log_probs float32 cuda [windows of all recordings, t_max, 1025] in
         recording-then-window order, n_samples the recordings' lengths.  Returns (info [R] of LONG_INFO_DTYPE, ids int32
         [R, pitch], logp float32, first / last int32 [R, pitch])."""
-        torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
-        n = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64))
-        plans = [self.long_plan_raw(int(v), window_samples, margin_frames) for v in n]
-        if log_probs.shape[0] != sum(p["n_windows"] for p in plans) or log_probs.shape[2] != 1025:
-            raise QvError(f"transcribe_windows: log_probs {tuple(log_probs.shape)} does not hold the {sum(p['n_windows'] for p in plans)} planned windows")
-        head = (C.c_void_p(log_probs.data_ptr()), int(log_probs.shape[1]), n.ctypes.data_as(C.c_void_p))
+        head, n, plans = self._windows_head("transcribe_windows", log_probs, n_samples, window_samples, margin_frames)
         return self._long_call(self.lib.qv_transcribe_windows, "qv_transcribe_windows", head, len(n), max(p["t_frames"] for p in plans),
                                window_samples, margin_frames, pitch)
 
+    def _windows_head(self, what, log_probs, n_samples, window_samples, margin_frames):
+        """the head arguments of a call on the caller's window log-probs, the recordings' lengths (int64) and their plans"""
+        W, t_max, _ = self._logprob_args(log_probs)
+        n = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64))
+        plans = [self.long_plan_raw(int(v), window_samples, margin_frames) for v in n]
+        if W != sum(p["n_windows"] for p in plans):
+            raise QvError(f"{what}: log_probs {tuple(log_probs.shape)} does not hold the {sum(p['n_windows'] for p in plans)} planned windows")
+        return (C.c_void_p(log_probs.data_ptr()), t_max, _p(n)), n, plans
+
     def transcribe_long_raw(self, audio, lengths, window_samples: int = 0, margin_frames: int = -1, pitch: int | None = None):
         """qv_transcribe_long as arrays (audio: float32 cuda [R, N]); see transcribe_windows_raw"""
-        torch = self.torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous() and audio.dim() == 2
-        R, N = audio.shape
-        n = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-        assert len(n) == R and n.max() <= N
+        R, N, n = self._audio_args(audio, lengths)
         t_top = int(n.max()) // QV_LONG_HOP + 1
-        head = (C.c_void_p(audio.data_ptr()), int(N), n.ctypes.data_as(C.c_void_p))
+        head = (C.c_void_p(audio.data_ptr()), int(N), _p(n))
         return self._long_call(self.lib.qv_transcribe_long, "qv_transcribe_long", head, R, t_top, window_samples, margin_frames, pitch)
 
     def _long_transcripts(self, info, ids, logp, first, last) -> list[dict]:
@@ -1380,7 +1331,7 @@ class Engine:
         lt = np.ascontiguousarray(np.asarray(n_tokens, dtype=np.int32).reshape(-1))
         assert len(n) == len(lt)
         nw, nbytes = C.c_int32(), C.c_int64()
-        rc = self.lib.qv_align_long_plan(n.ctypes.data_as(C.c_void_p), lt.ctypes.data_as(C.c_void_p), len(n), self.max_samples,
+        rc = self.lib.qv_align_long_plan(_p(n), _p(lt), len(n), self.max_samples,
                                          int(window_samples), int(margin_frames), C.byref(nw), C.byref(nbytes))
         if rc != 0:
             raise QvError(f"qv_align_long_plan failed ({rc}): {len(n)} rows, {int(nbytes.value)} bytes")
@@ -1394,8 +1345,7 @@ class Engine:
         info = np.zeros(rows, dtype=ALIGN_LONG_INFO_DTYPE)
         first, last = np.zeros((rows, max(pitch, 1)), np.int32), np.zeros((rows, max(pitch, 1)), np.int32)
         logp = np.zeros((rows, max(pitch, 1)), np.float32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = fn(self.h, *head, rows, int(window_samples), int(margin_frames), p(tg), p(lens), p(info), p(first), p(last), p(logp), pitch,
+        rc = fn(self.h, *head, rows, int(window_samples), int(margin_frames), _p(tg), _p(lens), _p(info), _p(first), _p(last), _p(logp), pitch,
                 self._stream())
         self._check(rc, what)
         return info, first, last, logp
@@ -1404,23 +1354,13 @@ class Engine:
         """qv_align_windows as arrays: log_probs float32 cuda [windows of all recordings, t_max, 1025] in recording-then-window
         order (as transcribe_windows_raw), targets a list of id lists (0..1023), one per recording.  Returns (info [R] of
         ALIGN_LONG_INFO_DTYPE, first / last int32 [R, pitch] in frames of the whole recording, logp float32 [R, pitch])."""
-        torch = self.torch
-        assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.is_contiguous() and log_probs.dim() == 3
-        n = np.ascontiguousarray(np.asarray(n_samples, dtype=np.int64))
-        plans = [self.long_plan_raw(int(v), window_samples, margin_frames) for v in n]
-        if log_probs.shape[0] != sum(p["n_windows"] for p in plans) or log_probs.shape[2] != 1025:
-            raise QvError(f"align_windows: log_probs {tuple(log_probs.shape)} does not hold the {sum(p['n_windows'] for p in plans)} planned windows")
-        head = (C.c_void_p(log_probs.data_ptr()), int(log_probs.shape[1]), n.ctypes.data_as(C.c_void_p))
+        head, n, _ = self._windows_head("align_windows", log_probs, n_samples, window_samples, margin_frames)
         return self._align_long_call(self.lib.qv_align_windows, "qv_align_windows", head, len(n), targets, window_samples, margin_frames, pitch)
 
     def align_long_raw(self, audio, lengths, targets, window_samples: int = 0, margin_frames: int = -1, pitch: int | None = None):
         """qv_align_long as arrays (audio: float32 cuda [R, N]); see align_windows_raw"""
-        torch = self.torch
-        assert audio.is_cuda and audio.dtype == torch.float32 and audio.is_contiguous() and audio.dim() == 2
-        R, N = audio.shape
-        n = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-        assert len(n) == R and n.max() <= N
-        head = (C.c_void_p(audio.data_ptr()), int(N), n.ctypes.data_as(C.c_void_p))
+        R, N, n = self._audio_args(audio, lengths)
+        head = (C.c_void_p(audio.data_ptr()), int(N), _p(n))
         return self._align_long_call(self.lib.qv_align_long, "qv_align_long", head, R, targets, window_samples, margin_frames, pitch)
 
     @staticmethod
@@ -1471,9 +1411,8 @@ class Engine:
         csc = np.zeros(cap, np.float64)
         ri = np.zeros(128, np.int32)
         rs = np.zeros(128, np.float64)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_debug_retrieve(self.h, p(codes), len(codes), C.byref(bs), C.byref(bp), C.byref(bsc),
-                                        p(cs), p(cp), p(csc), cap, C.byref(nc), p(ri), p(rs), C.byref(nr),
+        rc = self.lib.qv_debug_retrieve(self.h, _p(codes), len(codes), C.byref(bs), C.byref(bp), C.byref(bsc),
+                                        _p(cs), _p(cp), _p(csc), cap, C.byref(nc), _p(ri), _p(rs), C.byref(nr),
                                         self._stream())
         self._check(rc, "qv_debug_retrieve")
         n = min(nc.value, cap)
@@ -1491,8 +1430,7 @@ class Engine:
         pitch = self.max_transcript
         codes = np.zeros((batch, pitch), np.uint8)
         n, words = np.zeros(batch, np.int32), np.zeros(batch, np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        rc = self.lib.qv_debug_transcript_codes(self.h, int(ctx), int(batch), p(codes), pitch, p(n), p(words))
+        rc = self.lib.qv_debug_transcript_codes(self.h, int(ctx), int(batch), _p(codes), pitch, _p(n), _p(words))
         self._check(rc, "qv_debug_transcript_codes")
         return [{"codes": codes[b, : n[b]].copy(), "n_chars": int(n[b]), "n_words": int(words[b])} for b in range(batch)]
 
@@ -1501,9 +1439,8 @@ class Engine:
         tg = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint16) for x in id_lists]))
         lens = np.ascontiguousarray(np.array([len(x) for x in id_lists], np.int32))
         out = np.zeros(len(id_lists), np.float32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
         rc = self.lib.qv_debug_ctc_loss(self.h, C.c_void_p(log_probs_2d.data_ptr()), log_probs_2d.shape[0],
-                                        p(tg), p(lens), len(id_lists), p(out), self._stream())
+                                        _p(tg), _p(lens), len(id_lists), _p(out), self._stream())
         self._check(rc, "qv_debug_ctc_loss")
         return out
 

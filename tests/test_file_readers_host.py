@@ -140,6 +140,21 @@ def test_malformed_tables_are_refused(checker, tmp_path, case):
     print(case, "->", msg)
 
 
+def test_a_tables_path_that_does_not_exist_is_refused(checker, tmp_path):
+    """the reader every caller shares (qv_read_host_tables): qv_create's message, with the path"""
+    missing = tmp_path / "no_such_tables.bin"
+    assert refused_with(checker("tables", missing), "cannot open tables file:") == f"cannot open tables file: {missing}"
+
+
+def test_an_empty_tables_file_is_refused_by_the_bad_magic_rule(checker, tmp_path):
+    (tmp_path / "tables.bin").write_bytes(b"")
+    p = checker("tables", tmp_path / "tables.bin")
+    assert refused_with(p, "bad magic") == "tables file malformed (bad magic)"
+    # ... the message a file with another magic gets, not one of its own
+    (tmp_path / "other.bin").write_bytes(b"QVTB0002" + bytes(64))
+    assert checker("tables", tmp_path / "other.bin").stdout == p.stdout
+
+
 # ---------------------------------------------------------------- malformed weights ----
 def tensor(name: bytes, numel: int, data: bytes | None = None) -> bytes:
     return struct.pack("<I", len(name)) + name + struct.pack("<I", numel) + (bytes(4 * numel) if data is None else data)

@@ -13,7 +13,6 @@
 #include <stdio.h>
 
 #include <fstream>
-#include <iterator>
 #include <string>
 #include <vector>
 
@@ -32,12 +31,9 @@ int refused(const std::string &err) {
 }
 
 int check_tables(const char *path, const char *dump_dir) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return refused(std::string("cannot open tables file: ") + path);
-    const std::vector<char> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     HostTables h;
     std::string err;
-    if (qv_build_host_tables((const uint8_t *)file.data(), file.size(), h, err) != QV_OK) return refused(err);
+    if (qv_read_host_tables(path, h, err) != QV_OK) return refused(err);
     printf("tables ok: n_verses %d n_surah %d n_tri %d n_text %d\n", h.n_verses, h.n_surah, h.n_tri, h.n_text);
     if (!dump_dir) return 0;
     const std::string d = dump_dir;

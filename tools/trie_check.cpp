@@ -13,8 +13,6 @@
 
 #include <stdio.h>
 
-#include <fstream>
-#include <iterator>
 #include <string>
 #include <vector>
 
@@ -124,12 +122,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "usage: trie_check <qverse_tables.bin>\n");
         return 2;
     }
-    std::ifstream f(argv[1], std::ios::binary);
-    if (!f) { printf("refused: cannot open tables file: %s\n", argv[1]); return 3; }
-    const std::vector<char> file((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     HostTables h;
     std::string err;
-    if (qv_build_host_tables((const uint8_t *)file.data(), file.size(), h, err) != QV_OK) { printf("refused: %s\n", err.c_str()); return 3; }
+    if (qv_read_host_tables(argv[1], h, err) != QV_OK) { printf("refused: %s\n", err.c_str()); return 3; }
     for (int S : {1, 2, 3, 6})
         if (int rc = check_trie(h, S)) return rc;
     if (int rc = check_refusals(h)) return rc;
