@@ -202,8 +202,12 @@ int qv_upfirdn(qv_engine *e, const float *x_dev, int64_t n_in, const float *taps
 int qv_upfirdn_batch(qv_engine *e, const float *x_dev, int64_t x_pitch, const int32_t *src_rows_host, const int64_t *n_in_host,
                      int32_t rows, const float *taps_host, int32_t n_taps, int32_t up, int32_t down, int64_t m0,
                      float *y_dev, int64_t y_pitch, void *stream);
-/* Interleaved multi-channel rows [frames][channels] (float32) -> mono rows: the float32 mean over the channel axis (sequential
- * sum, one division), i.e. numpy's x.reshape(-1, ch).mean(axis=1) -- the reference's mix-down (shared/audio.py:13-15). */
+/* Interleaved multi-channel rows [frames][channels] (float32) -> mono rows: the float32 mean over the channel axis, one
+ * division of the frame's sum by the channel count, i.e. numpy's x.reshape(-1, ch).mean(axis=1) -- the reference's mix-down
+ * (shared/audio.py:13-15) -- bit for bit.  The sum is taken in numpy's order: left to right from +0 below 8 channels; from 8
+ * up, eight running sums r[k] = x[k], r[k] += x[8 i + k] over the whole groups of eight, joined as
+ * ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the channels % 8 tail one by one.  A frame of -0.0 gives +0.0, as
+ * numpy's does.  1 <= channels <= 64, rows <= 1024; samples behind a row's n_frames are left as they are. */
 int qv_mixdown_batch(qv_engine *e, const float *x_dev, int64_t x_pitch, const int64_t *n_frames_host, int32_t rows,
                      int32_t channels, float *y_dev, int64_t y_pitch, void *stream);
 

@@ -1140,8 +1140,13 @@ __global__ __launch_bounds__(256) void k_upfirdn_rows(const float *__restrict__ 
     }
 }
 
-// interleaved [frames][channels] float32 -> mono: numpy's float32 mean over the channel axis (sequential sum, one
-// division by the channel count), what audio._read_wav / the reference's soundfile fallback do (shared/audio.py:13-15)
+// interleaved [frames][channels] float32 -> mono: numpy's float32 mean over the channel axis, what audio._read_wav / the
+// reference's soundfile fallback do (shared/audio.py:13-15): one division of the frame's sum by the channel count, the sum
+// taken in the order of numpy's float32 add-reduce along a contiguous axis.  Below 8 channels that is left to right from
+// +0 (so a frame of -0.0 gives +0.0, as numpy's does).  From 8 channels up (and to 128: the entry point stops at 64) it
+// keeps eight running sums r[k] = x[k], r[k] += x[8 i + k] over the whole groups of eight, joins them as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) and adds the channels % 8 tail one by one; the +0 goes in last, where
+// it changes nothing but the sign of a zero.
 __global__ __launch_bounds__(256) void k_mixdown(const float *__restrict__ x, int64_t x_pitch, const int64_t *__restrict__ n_frames,
                                                  int channels, float *__restrict__ y, int64_t y_pitch) {
     const int r = blockIdx.y;
@@ -1149,8 +1154,23 @@ __global__ __launch_bounds__(256) void k_mixdown(const float *__restrict__ x, in
     const float *xr = x + (size_t)r * x_pitch;
     float *yr = y + (size_t)r * y_pitch;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float acc = xr[i * channels];
-        for (int c = 1; c < channels; ++c) acc = __fadd_rn(acc, xr[i * channels + c]);
+        const float *f = xr + i * channels;
+        float acc = 0.f;
+        if (channels < 8) {
+            for (int c = 0; c < channels; ++c) acc = __fadd_rn(acc, f[c]);
+        } else {
+            float s[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s[k] = f[k];
+            int c = 8;
+            for (; c + 8 <= channels; c += 8)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s[k] = __fadd_rn(s[k], f[c + k]);
+            float t = __fadd_rn(__fadd_rn(__fadd_rn(s[0], s[1]), __fadd_rn(s[2], s[3])),
+                                __fadd_rn(__fadd_rn(s[4], s[5]), __fadd_rn(s[6], s[7])));
+            for (; c < channels; ++c) t = __fadd_rn(t, f[c]);
+            acc = __fadd_rn(t, 0.f);
+        }
         yr[i] = __fdiv_rn(acc, (float)channels);
     }
 }

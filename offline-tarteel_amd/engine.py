@@ -809,11 +809,14 @@ class Engine:
         self._check(rc, "qv_upfirdn")
         return y
 
+    RESAMPLE_ROWS = 1024   # rows per qv_upfirdn_batch / qv_mixdown_batch call (QV_RESAMPLE_ROWS)
+
     def resample_rows(self, x, lengths, up: int, down: int, src_rows=None, out_pitch: int | None = None):
-        """scipy.signal.resample_poly(row, up, down) for every row of a float32 cuda matrix in ONE launch (qv_upfirdn_batch):
-        x [R0, pitch] holds the clips zero-padded, ``lengths`` their sample counts; ``src_rows`` (optional) picks which rows
-        of x are resampled (output row r <- x[src_rows[r]], lengths[r] = that clip's length).  Returns (y [R, out_pitch]
-        zero-padded like x, list of output lengths).  Every output sample is bit-identical to resample_poly's float32 one."""
+        """scipy.signal.resample_poly(row, up, down) for every row of a float32 cuda matrix in ONE launch (qv_upfirdn_batch;
+        one launch per 1,024 rows, all into the same output): x [R0, pitch] holds the clips zero-padded, ``lengths`` their
+        sample counts; ``src_rows`` (optional) picks which rows of x are resampled (output row r <- x[src_rows[r]],
+        lengths[r] = that clip's length).  Returns (y [R, out_pitch] zero-padded like x, list of output lengths).  Every
+        output sample is bit-identical to resample_poly's float32 one."""
         from .audio import resample_plan
 
         torch = self.torch
@@ -832,20 +835,31 @@ class Engine:
         assert pitch >= max(n_out)
         y = torch.empty((rows, pitch), dtype=torch.float32, device=x.device)
         src = None if src_rows is None else np.ascontiguousarray(np.asarray(list(src_rows), dtype=np.int32))
-        rc = self.lib.qv_upfirdn_batch(self.h, C.c_void_p(x.data_ptr()), int(x.stride(0)), _p(src), _p(lens), rows, _p(taps), len(taps),
-                                       up_r, down_r, m0, C.c_void_p(y.data_ptr()), pitch, self._stream())
-        self._check(rc, "qv_upfirdn_batch")
+        x_pitch = int(x.stride(0))
+        for r0 in range(0, rows, self.RESAMPLE_ROWS):     # the C ABI takes 1,024 rows a call: chunks of one output tensor
+            r1 = min(rows, r0 + self.RESAMPLE_ROWS)
+            ln_c = lens[r0:r1]
+            src_c = None if src is None else src[r0:r1]
+            x_ptr = x.data_ptr() + (0 if src is not None else r0 * x_pitch * 4)   # without src_rows a chunk's row 0 is row r0 of x
+            rc = self.lib.qv_upfirdn_batch(self.h, C.c_void_p(x_ptr), x_pitch, _p(src_c), _p(ln_c), r1 - r0, _p(taps), len(taps),
+                                           up_r, down_r, m0, C.c_void_p(y.data_ptr() + r0 * pitch * 4), pitch, self._stream())
+            self._check(rc, "qv_upfirdn_batch")
         return y, n_out
 
     def mixdown_rows(self, x, n_frames, channels: int):
-        """interleaved [R, frames * channels] float32 cuda rows -> mono [R, max frames] (numpy's float32 mean over channels)"""
+        """interleaved [R, frames * channels] float32 cuda rows -> mono [R, max frames]: numpy's float32 mean over the channels,
+        the frame's sum taken in numpy's own order (left to right below 8 channels, eight running sums joined by a fixed tree
+        plus the tail from 8 up: k_mixdown), an all -0.0 frame giving +0.0 as numpy's does.  One launch per 1,024 rows."""
         torch = self.torch
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
         nf = np.ascontiguousarray(np.asarray(n_frames, dtype=np.int64))
         y = torch.zeros((len(nf), int(nf.max())), dtype=torch.float32, device=x.device)
-        rc = self.lib.qv_mixdown_batch(self.h, C.c_void_p(x.data_ptr()), int(x.stride(0)), _p(nf), len(nf), int(channels),
-                                       C.c_void_p(y.data_ptr()), int(y.stride(0)), self._stream())
-        self._check(rc, "qv_mixdown_batch")
+        x_pitch, y_pitch = int(x.stride(0)), int(y.stride(0))
+        for r0 in range(0, len(nf), self.RESAMPLE_ROWS):
+            nf_c = nf[r0:r0 + self.RESAMPLE_ROWS]
+            rc = self.lib.qv_mixdown_batch(self.h, C.c_void_p(x.data_ptr() + r0 * x_pitch * 4), x_pitch, _p(nf_c), len(nf_c), int(channels),
+                                           C.c_void_p(y.data_ptr() + r0 * y_pitch * 4), y_pitch, self._stream())
+            self._check(rc, "qv_mixdown_batch")
         return y
 
     def speed_perturb_rows(self, x, lengths, factor: float, src_rows=None):

@@ -208,3 +208,69 @@ def test_forward_calls_with_both_contexts_busy(model, clips):
         assert len(e.align_results(ctx=ctx[0], batch=2)) == 2
     finally:
         e.close()
+
+
+# ---------------------------------------------------------------- the ingest entry points ----
+def test_resampler_and_mixdown_refusals(bare):
+    """qv_upfirdn, qv_upfirdn_batch and qv_mixdown_batch refuse a bad argument with QV_ERR_ARG before any launch -- every
+    buffer here is large enough for what the refused call names, a refused negative source row included -- and the valid
+    call after each refusal returns the bytes it returned before the first."""
+    from offline_tarteel_amd.audio import resample_plan
+
+    e, lib, s = bare, bare.lib, bare._stream()
+    R, N, ARG = 1025, 64, 1
+    x = torch.from_numpy((np.random.default_rng(5).standard_normal((R + 1, N)) * 0.3).astype(np.float32)).cuda()
+    x1 = C.c_void_p(x.data_ptr() + N * 4)                  # row 1 of x: R rows behind it, one in front
+    up, down, taps, m0, n_out = resample_plan(9, 10, N)
+    assert (up, down, n_out) == (9, 10, 58)
+    y1, yb, ym = (torch.zeros((R, N), dtype=torch.float32, device="cuda") for _ in range(3))
+    lens, frames, src = np.full(R, N, np.int64), np.full(R, N // 2, np.int64), np.arange(R, dtype=np.int32)
+
+    def single(**k):
+        a = dict(e=e.h, x=x1, n_in=N, taps=ptr(taps), n_taps=len(taps), up=up, down=down, m0=m0, n_out=n_out, y=dev(y1))
+        a.update(k)
+        return lib.qv_upfirdn(a["e"], a["x"], a["n_in"], a["taps"], a["n_taps"], a["up"], a["down"], a["m0"], a["n_out"], a["y"], s)
+
+    def batch(**k):
+        a = dict(e=e.h, x=x1, x_pitch=N, src=ptr(src), lens=ptr(lens), rows=3, taps=ptr(taps), n_taps=len(taps), up=up, down=down,
+                 m0=m0, y=dev(yb), y_pitch=N)
+        a.update(k)
+        return lib.qv_upfirdn_batch(a["e"], a["x"], a["x_pitch"], a["src"], a["lens"], a["rows"], a["taps"], a["n_taps"], a["up"],
+                                    a["down"], a["m0"], a["y"], a["y_pitch"], s)
+
+    def mix(**k):
+        a = dict(e=e.h, x=x1, x_pitch=N, frames=ptr(frames), rows=3, channels=2, y=dev(ym), y_pitch=N)
+        a.update(k)
+        return lib.qv_mixdown_batch(a["e"], a["x"], a["x_pitch"], a["frames"], a["rows"], a["channels"], a["y"], a["y_pitch"], s)
+
+    def valid():
+        assert (single(), batch(), mix()) == (0, 0, 0)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy().tobytes() for t in (y1, yb, ym)]
+
+    want = valid()
+    assert any(want[0]) and any(want[1]) and any(want[2])
+    long_row, neg_src, neg_frames, wide_frames = lens.copy(), src.copy(), frames.copy(), frames.copy()
+    long_row[1], neg_src[2], neg_frames[1], wide_frames[0] = N + 1, -1, -1, N // 2 + 1
+    refused = {
+        "qv_upfirdn": (single, [dict(e=None), dict(x=None), dict(taps=None), dict(y=None), dict(n_in=0), dict(n_taps=0), dict(up=0),
+                                dict(down=0), dict(m0=-1), dict(n_out=-1)]),
+        "qv_upfirdn_batch": (batch, [dict(e=None), dict(x=None), dict(lens=None), dict(taps=None), dict(y=None), dict(rows=0),
+                                     dict(rows=R), dict(n_taps=0), dict(up=0), dict(down=0), dict(m0=-1), dict(x_pitch=0),
+                                     dict(y_pitch=0), dict(lens=ptr(long_row)), dict(y_pitch=n_out - 1), dict(src=ptr(neg_src))]),
+        "qv_mixdown_batch": (mix, [dict(e=None), dict(x=None), dict(frames=None), dict(y=None), dict(rows=0), dict(rows=R),
+                                   dict(channels=0), dict(channels=65), dict(frames=ptr(neg_frames)), dict(frames=ptr(wide_frames)),
+                                   dict(y_pitch=N // 2 - 1)]),
+    }
+    text = {"lens": "qv_upfirdn_batch: a row's length is outside [1, x_pitch]", "y_pitch": "qv_upfirdn_batch: y_pitch is shorter than a row's output"}
+    for name, (call, cases) in refused.items():
+        for k in cases:
+            assert call(**k) == ARG, (name, list(k))
+            key = next(iter(k))
+            if name == "qv_upfirdn_batch" and key in text and k[key]:
+                assert e.lib.qv_last_error(e.h).decode() == text[key], (name, key)
+            assert valid() == want, (name, list(k))
+    # the largest table a call takes is taken: 1,024 rows
+    assert batch(rows=R - 1) == 0 and mix(rows=R - 1) == 0
+    torch.cuda.synchronize()
+    assert yb.cpu().numpy()[:3].tobytes() == np.frombuffer(want[1], np.float32).reshape(R, N)[:3].tobytes()

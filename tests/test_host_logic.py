@@ -158,21 +158,7 @@ def test_load_audio_wav_mono_and_resample(tmp_path):
         load_audio(str(tmp_path / "c.mp3"))
 
 
-def upfirdn_restatement(x, taps, up, down, m0, n_out):
-    """numpy restatement of k_upfirdn's arithmetic (include/qverse.h: qv_upfirdn): per output
-    sample, products accumulated in float32 in ascending input order."""
-    P = (len(taps) + up - 1) // up
-    hp = np.zeros(up * P, np.float32)
-    hp[: len(taps)] = taps
-    m = np.arange(m0, m0 + n_out, dtype=np.int64)
-    xi, t = (m * down) // up, (m * down) % up
-    acc = np.zeros(n_out, np.float32)
-    for j in range(P):
-        i = xi - (P - 1) + j
-        ok = (i >= 0) & (i < len(x))
-        prod = (x[np.clip(i, 0, len(x) - 1)] * hp[t + up * (P - 1 - j)]).astype(np.float32)
-        acc = np.where(ok, (acc + prod).astype(np.float32), acc)
-    return acc
+from audio_ref import upfirdn_restatement  # noqa: E402  (its one definition)
 
 
 def test_resample_plan_and_fir_order_match_scipy_bitwise():
