@@ -1,8 +1,24 @@
-// qv_dev_util.h -- small device helpers shared by qv_layers.hip and qv_ort.hip (one definition, so that the two
-// translation units normalise a row / a mel feature with the very same float32 operations).
+// qv_dev_util.h -- small device helpers shared by qv_frontend.hip, qv_layers.hip and qv_ort.hip (one definition, so that
+// the translation units normalise a row / a mel feature with the very same float32 operations).
 #pragma once
 
 #include "qv_kernels.h"
+
+// a thread's eight consecutive channels as two 16-byte accesses
+static __device__ __forceinline__ void load_c8(const float *p, float o[8]) {
+    const f32x4 a = *(const f32x4 *)p, b = *(const f32x4 *)(p + 4);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { o[c] = a[c]; o[4 + c] = b[c]; }
+}
+static __device__ __forceinline__ void store_c8(float *q, const float o[8]) {
+    *(f32x4 *)q = f32x4{o[0], o[1], o[2], o[3]};
+    *(f32x4 *)(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
+}
+// the nine taps of a depthwise filter for channels c0 .. c0 + 7; wt is tap-major [9][pitch]
+static __device__ __forceinline__ void load_taps9_c8(const float *wt, int pitch, int c0, float w[9][8]) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) load_c8(wt + k * pitch + c0, w[k]);
+}
 
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -39,6 +55,18 @@ static __device__ __forceinline__ void mel_mean_rstd(const double *acc, int b, i
     mean = (float)mu;
     rstd = 1.f / (sqrtf((float)(var > 0.0 ? var : 0.0)) + 1e-5f);
 }
+// N mel rows from frame first_frame on into LDS rows[N][QV_NMEL + 2] (bin f in column f + 1; a block of 256 threads), as
+// f(normalised feature): per-feature normalisation (NeMo normalize_batch "per_feature") applied on load; frames outside
+// [0, tin) and the two padding columns -- the convolution's padding -- are 0.  The stride is the constant 256, not
+// blockDim.x, as in the three loops this replaced: a caller must be a __launch_bounds__(256) kernel launched with 256 threads
+template <int N, typename F>
+static __device__ __forceinline__ void stage_mel_rows(float (*rows)[QV_NMEL + 2], const float *x, int first_frame, int tin,
+                                                      const float *mean_s, const float *rstd_s, F f) {
+    for (int i = threadIdx.x; i < N * (QV_NMEL + 2); i += 256) {
+        const int r = i / (QV_NMEL + 2), c = i % (QV_NMEL + 2) - 1, t = first_frame + r;
+        rows[r][c + 1] = (t >= 0 && t < tin && c >= 0 && c < QV_NMEL) ? f((x[t * QV_NMEL + c] - mean_s[c]) * rstd_s[c]) : 0.f;
+    }
+}
 
 // LayerNorm parameters of one lane (8 channels), requested before the row statistics so that
 // their latency overlaps the reductions
@@ -48,6 +76,13 @@ static __device__ __forceinline__ LnParam ln_param(const float *__restrict__ gam
     p.g0 = *(const f32x4 *)(gam + lane * 8); p.g1 = *(const f32x4 *)(gam + lane * 8 + 4);
     p.b0 = *(const f32x4 *)(bet + lane * 8); p.b1 = *(const f32x4 *)(bet + lane * 8 + 4);
     return p;
+}
+// a lane's 8 values of ROWS consecutive rows of 512 from row0 on, all loads in flight at once; a row past the last one
+// re-reads row M - 1 (no branch around the load; the caller drops it)
+template <int ROWS>
+static __device__ __forceinline__ void ln_load_rows(const float *x, int row0, int M, int lane, float v[ROWS][8]) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) load_c8(x + (size_t)(row0 + r < M ? row0 + r : M - 1) * QV_D + lane * 8, v[r]);
 }
 // one wave, one row of 512 (8 values per lane): two-pass variance in registers
 static __device__ __forceinline__ void ln_row_p(const float v[8], const LnParam &p, float o[8]) {

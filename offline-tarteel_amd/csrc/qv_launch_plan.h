@@ -1,5 +1,5 @@
 // qv_launch_plan.h -- which kernel a launch gets and how long its blocks' runs are: pure integer functions of the launch
-// shape and a snapshot of the switches (qv_switches.h).  No HIP here: the launchers (qv_gemm.hip, qv_layers.hip,
+// shape and a snapshot of the switches (qv_switches.h).  No HIP here: the launchers (qv_gemm.hip, qv_frontend.hip,
 // qv_attention.hip) turn a plan into launches, tools/launch_plan_check.cpp runs the plans on a CPU.
 #pragma once
 

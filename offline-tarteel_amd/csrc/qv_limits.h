@@ -27,7 +27,7 @@ static_assert(QV_FRAME_CAP >= QV_MAX_T_CAP, "the LDS frame arrays hold the frame
 #define QV_SUBC 256
 #define QV_N_LAYERS 17
 
-// launch-shape constants the kernels (qv_layers.hip, qv_attention.hip) and the host's launch plans (qv_launch_plan.h) share
+// launch-shape constants the kernels (qv_frontend.hip, qv_attention.hip) and the host's launch plans (qv_launch_plan.h) share
 #define SUB_TT 4            // k_sub01: c1 frames per tile
 #define SUB_MAX_RUN 16      // k_sub01: tiles a block walks at most
 #define SUB_RES_RUN 4       // k_sub01: tiles a block walks at most with the run's mel rows resident in LDS

@@ -1,13 +1,13 @@
 // qv_logmel_reg.h -- the log-mel kernel with its 256-point FFT in registers (round 5).
 //
-// Same transform, same butterflies on the same operands in the same order as k_logmel (qv_layers.hip: radix-2 Stockham,
+// Same transform, same butterflies on the same operands in the same order as k_logmel (qv_frontend.hip: radix-2 Stockham,
 // N = 256 on the packed real frame), hence the same bits -- only the data movement differs: a lane holds four complex
 // points, the two in-lane strides are local butterflies and the six cross-lane strides are exchanges over DPP
 // (quad_perm, row_half_mirror, row_ror) and v_permlane16/32_swap, i.e. VALU instructions; LDS memory is not touched before
 // the power spectrum.  Why: a co-running kernel of another engine (f16 MFMA fed from LDS at full rate, tools/withdrawn/)
 // was seen to disturb the LDS-exchanging kernel (tools/interference_probe.hip); this one has no LDS
 // exchange to disturb, and it is VALU-bound instead of LDS-latency-bound.
-// Included by qv_layers.hip (the product kernel) and by tools/logmel_variants.h (the probe's victim 7).
+// Included by qv_frontend.hip (the product kernel) and by tools/logmel_variants.h (the probe's victim 7).
 #pragma once
 
 #include "qv_layers.h"

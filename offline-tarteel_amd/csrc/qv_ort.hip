@@ -5,7 +5,7 @@
 // partial sum is an integer below 2^24 -- fmaf on integer-valued floats IS the int32 accumulation of ConvInteger.
 // (The GEMM-shaped convolutions run on the i8 MFMA instead: k_gemm<.., WQ = 88, ..> in qv_gemm.hip.)
 // All of these are HBM-bound elementwise / small-stencil kernels; they keep the tiling of their f16 counterparts in
-// qv_layers.hip (a lane owns 8 channels, weights in registers, sliding windows), only the element type changes.
+// qv_frontend.hip / qv_layers.hip (a lane owns 8 channels, weights in registers, sliding windows), only the element type changes.
 
 #include "qv_ort.h"
 #include "qv_dev_util.h"
@@ -89,13 +89,8 @@ __global__ __launch_bounds__(256) void k_ln_ort(const float *__restrict__ x, con
     __shared__ float s_mn[4 * LNQ_ROWS], s_mx[4 * LNQ_ROWS];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row0 = (xcd_order(blockIdx.x, gridDim.x) * 4 + wave) * LNQ_ROWS;   // XCD-affine row order (qv_dev_util.h)
-    f32x4 a[LNQ_ROWS], c[LNQ_ROWS];
-#pragma unroll
-    for (int r = 0; r < LNQ_ROWS; ++r) {
-        const int row = row0 + r < M ? row0 + r : M - 1;
-        const float *p = x + (size_t)row * QV_D + lane * 8;
-        a[r] = *(const f32x4 *)p; c[r] = *(const f32x4 *)(p + 4);
-    }
+    float v[LNQ_ROWS][8], o[8];
+    ln_load_rows<LNQ_ROWS>(x, row0, M, lane, v);
     const LnParam pr = ln_param(gam, bet, lane);
 #pragma unroll
     for (int r = 0; r < LNQ_ROWS; ++r) {
@@ -105,8 +100,7 @@ __global__ __launch_bounds__(256) void k_ln_ort(const float *__restrict__ x, con
             continue;
         }
         const int utt = row_map[row] >> 16;
-        float v[8] = {a[r][0], a[r][1], a[r][2], a[r][3], c[r][0], c[r][1], c[r][2], c[r][3]}, o[8];
-        ln_row_p(v, pr, o);
+        ln_row_p(v[r], pr, o);
         if (!QUANT) {
             float mn = o[0], mx = o[0];
 #pragma unroll
@@ -114,11 +108,7 @@ __global__ __launch_bounds__(256) void k_ln_ort(const float *__restrict__ x, con
             mn = wave_min(mn);
             mx = wave_max(mx);
             if (lane == 0) { s_utt[wave * LNQ_ROWS + r] = utt; s_mn[wave * LNQ_ROWS + r] = mn; s_mx[wave * LNQ_ROWS + r] = mx; }
-            if (y32) {
-                float *q = y32 + (size_t)row * QV_D + lane * 8;
-                *(f32x4 *)q = f32x4{o[0], o[1], o[2], o[3]};
-                *(f32x4 *)(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
-            }
+            if (y32) store_c8(y32 + (size_t)row * QV_D + lane * 8, o);
         } else {
             const QParam p = dql_param(mm + QV_MM_STRIDE * utt);
             uint32_t w[2] = {0, 0};
@@ -186,12 +176,7 @@ __global__ __launch_bounds__(256) void k_dwconv1d_ort(const float *__restrict__ 
     float mn = INFINITY, mx = -INFINITY;
     if (t0 < T) {
     float w[9][8];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        f32x4 w0 = *(const f32x4 *)(wq + k * QV_D + c0), w1 = *(const f32x4 *)(wq + k * QV_D + c0 + 4);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { w[k][c] = w0[c]; w[k][4 + c] = w1[c]; }
-    }
+    load_taps9_c8(wq, QV_D, c0, w);
     float acc[DWQ_TT][8];
 #pragma unroll
     for (int j = 0; j < DWQ_TT; ++j)
@@ -201,11 +186,10 @@ __global__ __launch_bounds__(256) void k_dwconv1d_ort(const float *__restrict__ 
     for (int i = 0; i < DWQ_TT + 8; ++i) {
         const int tt = t0 - 4 + i;
         if (tt < 0 || tt >= T) continue;
-        const float *px = x + (row0 + tt) * QV_D + c0;
-        const f32x4 v0 = *(const f32x4 *)px, v1 = *(const f32x4 *)(px + 4);
         float vf[8];
+        load_c8(x + (row0 + tt) * QV_D + c0, vf);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { vf[c] = quant_c(v0[c], p); vf[4 + c] = quant_c(v1[c], p); }
+        for (int c = 0; c < 8; ++c) vf[c] = quant_c(vf[c], p);
 #pragma unroll
         for (int j = 0; j < DWQ_TT; ++j) {
             const int k = i - j;  // tap index: tt = (t0 + j) + k - 4
@@ -215,13 +199,9 @@ __global__ __launch_bounds__(256) void k_dwconv1d_ort(const float *__restrict__ 
         }
     }
     float bs[8], al[8], be[8];
-    {
-        f32x4 b0 = *(const f32x4 *)(bias + c0), b1 = *(const f32x4 *)(bias + c0 + 4);
-        f32x4 a0 = *(const f32x4 *)(bn_alpha + c0), a1 = *(const f32x4 *)(bn_alpha + c0 + 4);
-        f32x4 e0 = *(const f32x4 *)(bn_beta + c0), e1 = *(const f32x4 *)(bn_beta + c0 + 4);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { bs[c] = b0[c]; bs[4 + c] = b1[c]; al[c] = a0[c]; al[4 + c] = a1[c]; be[c] = e0[c]; be[4 + c] = e1[c]; }
-    }
+    load_c8(bias + c0, bs);
+    load_c8(bn_alpha + c0, al);
+    load_c8(bn_beta + c0, be);
 #pragma unroll
     for (int j = 0; j < DWQ_TT; ++j) {
         if (t0 + j >= T) break;
@@ -234,9 +214,7 @@ __global__ __launch_bounds__(256) void k_dwconv1d_ort(const float *__restrict__ 
             mn = fminf(mn, o[c]);
             mx = fmaxf(mx, o[c]);
         }
-        float *q = y + (row0 + t0 + j) * QV_D + c0;
-        *(f32x4 *)q = f32x4{o[0], o[1], o[2], o[3]};
-        *(f32x4 *)(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
+        store_c8(y + (row0 + t0 + j) * QV_D + c0, o);
     }
     }
     block_fold(mm_out + QV_MM_STRIDE * b, mn, mx, s_fold);
@@ -265,7 +243,7 @@ __global__ __launch_bounds__(320) void k_mel_minmax(const float *__restrict__ fe
 }
 
 // conv.0 (Conv2d 1 -> 256, 3x3, s2, p1) + ReLU and conv.2 (depthwise 3x3, s2, p1) as integer convolutions; k_sub01's
-// tiling (qv_layers.hip): block = (64-channel group, 4 output frames, utterance), the 19 mel rows it needs sit in LDS
+// tiling (qv_frontend.hip): block = (64-channel group, 4 output frames, utterance), the 19 mel rows it needs sit in LDS
 // -- here as x_q - zp --, the 9 x 40 x 64 conv.0 tile is computed into LDS and the depthwise conv reads it from there.
 //   PASS 0: only the range of ReLU(conv.0) over the valid frames (its DynamicQuantizeLinear needs the max first);
 //   PASS 1: conv.0 again, quantised with that range into the tile (integers 0..255: exact as f16), then conv.2 ->
@@ -302,26 +280,13 @@ __global__ __launch_bounds__(256) void k_sub01_ort(const float *__restrict__ fea
     __syncthreads();
     const QParam pm = dql_param(mm_mel + QV_MM_STRIDE * b);
     const int t1_0 = 2 * t2_0 - 1;         // first conv.0 row of the tile
-    const int tm_0 = 2 * t1_0 - 1;         // first mel row
-    for (int i = tid; i < SQ_RM * (QV_NMEL + 2); i += 256) {
-        int r = i / (QV_NMEL + 2), f = i % (QV_NMEL + 2) - 1, t = tm_0 + r;
-        // frames past the utterance and the conv padding are real zeros = the zero point
-        rows[r][f + 1] = (t >= 0 && t < tin && f >= 0 && f < QV_NMEL) ? quant_c((x[t * QV_NMEL + f] - mean_s[f]) * rstd_s[f], pm) : 0.f;
-    }
+    // the tile's mel rows as x_q - zp; frames past the utterance and the conv padding are real zeros = the zero point
+    stage_mel_rows<SQ_RM>(rows, x, 2 * t1_0 - 1, tin, mean_s, rstd_s, [&](float v) { return quant_c(v, pm); });
     const int c8 = (tid & 7) * 8, pl = tid >> 3;   // 8 channels per thread, 32 positions per pass
     float w[9][8], bs[8];
-    auto load_w = [&](const float *wt, const float *bias) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            f32x4 wa = *(const f32x4 *)(wt + k * QV_SUBC + cg + c8), wb = *(const f32x4 *)(wt + k * QV_SUBC + cg + c8 + 4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { w[k][c] = wa[c]; w[k][4 + c] = wb[c]; }
-        }
-        f32x4 ba = *(const f32x4 *)(bias + cg + c8), bb = *(const f32x4 *)(bias + cg + c8 + 4);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { bs[c] = ba[c]; bs[4 + c] = bb[c]; }
-    };
-    load_w(w0q, b0);
+    // (the group's offset goes into the pointer: as a column, cg + c8, the address arithmetic costs k_sub01_ort<1> two VGPRs)
+    load_taps9_c8(w0q + cg, QV_SUBC, c8, w);
+    load_c8(b0 + cg + c8, bs);
     __syncthreads();
     const float s0 = pm.scale * w0_scale;
     QParam p0 = {1.f, 0.f, 1.f};
@@ -360,7 +325,8 @@ __global__ __launch_bounds__(256) void k_sub01_ort(const float *__restrict__ fea
         block_fold(mm_c0 + QV_MM_STRIDE * b, mn, mx, s_fold);
         return;
     }
-    load_w(w1q, b1);
+    load_taps9_c8(w1q + cg, QV_SUBC, c8, w);
+    load_c8(b1 + cg + c8, bs);
     __syncthreads();
     const float s1 = p0.scale * w1_scale;
     const int l2 = len2[b];
@@ -387,9 +353,7 @@ __global__ __launch_bounds__(256) void k_sub01_ort(const float *__restrict__ fea
             o[c] = acc[c] * s1 + bs[c];
             if (t2 < l2) { mn = fminf(mn, o[c]); mx = fmaxf(mx, o[c]); }
         }
-        float *q = out + (((size_t)b * t2_max + t2) * 20 + fo) * QV_SUBC + cg + c8;
-        *(f32x4 *)q = f32x4{o[0], o[1], o[2], o[3]};
-        *(f32x4 *)(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
+        store_c8(out + (((size_t)b * t2_max + t2) * 20 + fo) * QV_SUBC + cg + c8, o);
     }
     block_fold(mm_c1 + QV_MM_STRIDE * b, mn, mx, s_fold);
 }
@@ -397,7 +361,7 @@ __global__ __launch_bounds__(256) void k_sub01_ort(const float *__restrict__ fea
 // Round 5: conv.0 on the FLOAT32 matrix pipe, all four channel groups in one block (the re-landed form of the withdrawn
 // kernel above: tools/withdrawn/qv_ort_conv0_mfma.hip with PROBE_ABL=8192, which leaves a co-running k_logmel undisturbed
 // in tools/interference_probe -- tests/test_gpu_interference.py runs that probe).  [channels] x [9 taps] x [positions] as
-// five v_mfma_f32_32x32x2_f32 per 32 x 32 tile like k_sub01 (qv_layers.hip), on the integer-valued operands x_q - zp and
+// five v_mfma_f32_32x32x2_f32 per 32 x 32 tile like k_sub01 (qv_frontend.hip), on the integer-valued operands x_q - zp and
 // w_q: every product and partial sum is an integer below 2^24, so the instruction's internal summation order cannot
 // change a bit and the VALU kernel above stays the bit-exact cross-check (QVERSE_ORT_SUB=0 /
 // qv_debug_kernel_variant(1, 0); tests/test_gpu_ort_mixed.py compares the two and both with the oracle).
@@ -425,12 +389,8 @@ __global__ __launch_bounds__(256) void k_sub01_ort_mx(const float *__restrict__ 
     __syncthreads();
     const QParam pm = dql_param(mm_mel + QV_MM_STRIDE * b);
     const int t1_0 = 2 * t2_0 - 1;         // first conv.0 row of the tile
-    const int tm_0 = 2 * t1_0 - 1;         // first mel row
-    for (int i = tid; i < SQ_RM * (QV_NMEL + 2); i += 256) {
-        int r = i / (QV_NMEL + 2), f = i % (QV_NMEL + 2) - 1, t = tm_0 + r;
-        // frames past the utterance and the conv padding are real zeros = the zero point
-        rows[r][f + 1] = (t >= 0 && t < tin && f >= 0 && f < QV_NMEL) ? quant_c((x[t * QV_NMEL + f] - mean_s[f]) * rstd_s[f], pm) : 0.f;
-    }
+    // the tile's mel rows as x_q - zp; frames past the utterance and the conv padding are real zeros = the zero point
+    stage_mel_rows<SQ_RM>(rows, x, 2 * t1_0 - 1, tin, mean_s, rstd_s, [&](float v) { return quant_c(v, pm); });
     const int l31 = lane & 31, hi = lane >> 5;
     int koff[5];
     conv0_tap_offsets(hi, koff);
@@ -487,17 +447,8 @@ __global__ __launch_bounds__(256) void k_sub01_ort_mx(const float *__restrict__ 
         if (PASS == 0) continue;
         const int c8 = (tid & 7) * 8, pl = tid >> 3;   // depthwise conv: 8 channels per thread, 32 positions per pass
         float w[9][8], bs[8];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            f32x4 wa4 = *(const f32x4 *)(w1q + k * QV_SUBC + cg + c8), wb4 = *(const f32x4 *)(w1q + k * QV_SUBC + cg + c8 + 4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { w[k][c] = wa4[c]; w[k][4 + c] = wb4[c]; }
-        }
-        {
-            f32x4 ba = *(const f32x4 *)(b1 + cg + c8), bb = *(const f32x4 *)(b1 + cg + c8 + 4);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { bs[c] = ba[c]; bs[4 + c] = bb[c]; }
-        }
+        load_taps9_c8(w1q + cg, QV_SUBC, c8, w);
+        load_c8(b1 + cg + c8, bs);
         __syncthreads();
         // ---- depthwise 3x3 stride 2 over the tile
         for (int p = pl; p < SQ_TT * 20; p += 32) {
@@ -523,9 +474,7 @@ __global__ __launch_bounds__(256) void k_sub01_ort_mx(const float *__restrict__ 
                 o[c] = acc[c] * s1 + bs[c];
                 if (t2 < l2) { mn = fminf(mn, o[c]); mx = fmaxf(mx, o[c]); }
             }
-            float *q = out + (((size_t)b * t2_max + t2) * 20 + fo) * QV_SUBC + cg + c8;
-            *(f32x4 *)q = f32x4{o[0], o[1], o[2], o[3]};
-            *(f32x4 *)(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
+            store_c8(out + (((size_t)b * t2_max + t2) * 20 + fo) * QV_SUBC + cg + c8, o);
         }
         __syncthreads();                       // the tile is rewritten by the next channel group
     }
@@ -547,17 +496,8 @@ __global__ __launch_bounds__(256) void k_dwconv2d_ort(const float *__restrict__ 
     const QParam p = dql_param(mm_in + QV_MM_STRIDE * b);
     const float sxw = p.scale * w_scale;
     float w[9][8], bs[8];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        f32x4 w0 = *(const f32x4 *)(wq + k * QV_SUBC + c0), w1 = *(const f32x4 *)(wq + k * QV_SUBC + c0 + 4);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { w[k][c] = w0[c]; w[k][4 + c] = w1[c]; }
-    }
-    {
-        f32x4 b0 = *(const f32x4 *)(bias + c0), b1 = *(const f32x4 *)(bias + c0 + 4);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { bs[c] = b0[c]; bs[4 + c] = b1[c]; }
-    }
+    load_taps9_c8(wq, QV_SUBC, c0, w);
+    load_c8(bias + c0, bs);
     float mn = INFINITY, mx = -INFINITY;
     for (int pp = fl; pp < DWQ2_TT * fout; pp += 8) {
         const int to = to0 + pp / fout, fo = pp % fout;
@@ -574,13 +514,10 @@ __global__ __launch_bounds__(256) void k_dwconv2d_ort(const float *__restrict__ 
             for (int df = 0; df < 3; ++df) {
                 int f = 2 * fo - 1 + df;
                 if (f < 0 || f >= fin) continue;
-                const float *px = in + (((size_t)b * tin_max + t) * fin + f) * QV_SUBC + c0;
-                const f32x4 v0 = *(const f32x4 *)px, v1 = *(const f32x4 *)(px + 4);
+                float v[8];
+                load_c8(in + (((size_t)b * tin_max + t) * fin + f) * QV_SUBC + c0, v);
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    acc[c] = __builtin_fmaf(w[dt * 3 + df][c], quant_c(v0[c], p), acc[c]);
-                    acc[4 + c] = __builtin_fmaf(w[dt * 3 + df][4 + c], quant_c(v1[c], p), acc[4 + c]);
-                }
+                for (int c = 0; c < 8; ++c) acc[c] = __builtin_fmaf(w[dt * 3 + df][c], quant_c(v[c], p), acc[c]);
             }
         }
         float o[8];
@@ -589,9 +526,7 @@ __global__ __launch_bounds__(256) void k_dwconv2d_ort(const float *__restrict__ 
             o[c] = acc[c] * sxw + bs[c];
             if (valid) { mn = fminf(mn, o[c]); mx = fmaxf(mx, o[c]); }
         }
-        float *q = out + (((size_t)b * tout_max + to) * fout + fo) * QV_SUBC + c0;
-        *(f32x4 *)q = f32x4{o[0], o[1], o[2], o[3]};
-        *(f32x4 *)(q + 4) = f32x4{o[4], o[5], o[6], o[7]};
+        store_c8(out + (((size_t)b * tout_max + to) * fout + fo) * QV_SUBC + c0, o);
     }
     block_fold(mm_out + QV_MM_STRIDE * b, mn, mx, s_fold);
 }

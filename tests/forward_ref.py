@@ -168,7 +168,7 @@ def _h(x):
 
 def _layer_with_attention_roundings(w, p, x, pos_emb, pad, ops=None, taps=None, tag=""):
     """R.conformer_layer restated with the roundings the attention kernels perform on top of the f16 GEMM operands
-    (csrc/qv_layers.hip: k_attention*): q, k, v and the projected position rows are STORED as float16, q + u and q + v are
+    (csrc/qv_attention.hip: k_attention*): q, k, v and the projected position rows are STORED as float16, q + u and q + v are
     rounded to float16 MFMA operands, and exp(score - row max) is rounded to float16 before the P.V product while the row
     sum stays float32.  Everything outside the attention is R.conformer_layer's, line for line."""
     B, T, _ = x.shape

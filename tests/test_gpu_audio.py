@@ -144,7 +144,7 @@ def test_device_ingest_equals_host_load_audio(eng, tmp_path):
 # each differ from the references on these inputs.
 
 def _lds_bytes(up, down):
-    """the 60 KB rule of launch_upfirdn_rows (csrc/qv_layers.hip), restated: the per-phase filter (up * P taps) and the
+    """the 60 KB rule of launch_upfirdn_rows (csrc/qv_ingest.hip), restated: the per-phase filter (up * P taps) and the
     window of x a block of 256 outputs reads (256 * down / up + P + 2 samples), as float32"""
     from offline_tarteel_amd.audio import resample_plan
 

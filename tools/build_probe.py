@@ -3,8 +3,9 @@ tests/test_gpu_interference.py: does a kernel on one stream change what the log-
 
     python tools/build_probe.py [--force]
 
-`current` links the product's own translation units (qv_layers.hip, qv_ort.hip) as they are in the tree, `withdrawn`
-replaces qv_ort.hip by tools/withdrawn/qv_ort_conv0_mfma.hip, the round-4 kernel that was seen to disturb k_logmel.
+`current` links the product's own translation units (qv_frontend.hip, qv_attention.hip, qv_ort.hip) as they are in
+the tree, `withdrawn` replaces qv_ort.hip by tools/withdrawn/qv_ort_conv0_mfma.hip, the round-4 kernel that was seen
+to disturb k_logmel.
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ SRC = ROOT / "tools" / "interference_probe.hip"
 DEPS = [Path(__file__).resolve(), ROOT / "offline-tarteel_amd" / "build.py", SRC, ROOT / "tools" / "logmel_variants.h", ROOT / "tools" / "withdrawn" / "qv_ort_conv0_mfma.hip",
         *sorted((ROOT / "offline-tarteel_amd" / "csrc").glob("*.h")), *sorted((ROOT / "offline-tarteel_amd" / "csrc").glob("*.inc")),
         ROOT / "offline-tarteel_amd" / "csrc" / "qv_gemm.hip", ROOT / "offline-tarteel_amd" / "csrc" / "qv_gemm256.hip",
-        ROOT / "offline-tarteel_amd" / "csrc" / "qv_layers.hip", ROOT / "offline-tarteel_amd" / "csrc" / "qv_attention.hip",
+        ROOT / "offline-tarteel_amd" / "csrc" / "qv_frontend.hip", ROOT / "offline-tarteel_amd" / "csrc" / "qv_attention.hip",
         ROOT / "offline-tarteel_amd" / "csrc" / "qv_ort.hip"]
 
 

@@ -20,7 +20,7 @@
 //                                   99 print what the DPP / permlane primitives do on this chip and exit]
 // Round 5: every run prints the device's identity (uuid, PCI bus, clocks as HIP reports them), checks that a variant
 // reproduces the shipped kernel bit for bit before anything else runs, and times the victim kernel alone.
-#include "../offline-tarteel_amd/csrc/qv_layers.hip"
+#include "../offline-tarteel_amd/csrc/qv_frontend.hip"
 #include "../offline-tarteel_amd/csrc/qv_attention.hip"
 #ifdef PROBE_WITHDRAWN
 #include "withdrawn/qv_ort_conv0_mfma.hip"

@@ -6,7 +6,7 @@
 //   tools/logmel_bench_f4 [iters] [B] [N]
 // The tables are made here (Hann(400) centred in 512, exp(-2 pi i m / 512), 80 triangular filters on the HTK mel scale up
 // to 8 kHz): the shapes of the product's tables, which is what the time depends on; the compare needs no particular values.
-#include "../offline-tarteel_amd/csrc/qv_layers.hip"
+#include "../offline-tarteel_amd/csrc/qv_frontend.hip"
 
 #include <cmath>
 #include <cstdio>

@@ -1,4 +1,4 @@
-// logmel_variants.h -- copies of k_logmel (csrc/qv_layers.hip) that differ in HOW the lanes of a wave exchange FFT data, for
+// logmel_variants.h -- copies of k_logmel (csrc/qv_frontend.hip) that differ in HOW the lanes of a wave exchange FFT data, for
 // tools/interference_probe.hip (round 5: which part of the log-mel kernel is it that a co-running kernel can disturb?).
 // Every variant performs the SAME butterflies on the same operands in the same order as the shipped kernel, so all of
 // them must reproduce its output bit for bit when nothing else runs (the probe checks that first).

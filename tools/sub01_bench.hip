@@ -9,9 +9,9 @@
 //         -I offline-tarteel_amd/csrc -I include tools/sub01_bench.hip -o tools/sub01_bench
 //   tools/sub01_bench [iters] [B] [Tm]
 // Built with -DQV_SUB01_STAMPS (-o tools/sub01_bench_stamps) the kernel also records where wave 0 of one block in the
-// middle of the grid spends its clock (see SUB_STAMP in qv_layers.hip) and the tool prints each phase's share; the times
+// middle of the grid spends its clock (see SUB_STAMP in qv_frontend.hip) and the tool prints each phase's share; the times
 // of that build are not the product's.
-#include "../offline-tarteel_amd/csrc/qv_layers.hip"
+#include "../offline-tarteel_amd/csrc/qv_frontend.hip"
 
 #include <cstdio>
 #include <cstdlib>

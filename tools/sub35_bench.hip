@@ -5,7 +5,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I offline-tarteel_amd/csrc -I include \
 //         tools/sub35_bench.hip -o tools/sub35_bench
 //   tools/sub35_bench [iters] [B] [T2]
-#include "../offline-tarteel_amd/csrc/qv_layers.hip"
+#include "../offline-tarteel_amd/csrc/qv_frontend.hip"
 #include "../offline-tarteel_amd/csrc/qv_gemm256.hip"
 
 #include <cstdio>
